@@ -2,6 +2,7 @@
 """Headline benchmark: gridworld env-steps/s over tens of thousands of parallel agent-env instances.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3|C2|C4] [--instances n]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -19,6 +20,15 @@ instance count.  Global instance ids key the random streams and the world of an 
 results do not depend on N.  The only collective is the reduction of the monitor buffers after
 the last launch (one all-gather, inside the timed region).
 
+A plain run measures the headline configuration only: set-up, warm-up and pre-training, the K
+timed launches, the result line.  `--full` adds everything else: the configurations of --also
+(C2, C4, C6) and the legs (C5, Dyna-DQN, Dyna-DSR, C1, grid search, general kernels), the CPU
+baselines, the headline window repeated for --min-seconds (3) and the full objects in
+bench_full.json.  `--dump-outputs DIR` writes the state the headline's last timed launch left —
+Q (or SR) tables, the Dyna-Q model, instance words of a fixed, seeded sample of the instances and
+the monitor sums — as DIR/<name>.npy (float32 / float64, at most 64 MB), so that two builds can be
+compared output for output; the inputs are the same from run to run.
+
 Workloads, all synthetic, tables zero-initialised as the reference does:
   C3 (default, the configuration the metric is quoted on): 65 536 instances over 64 distinct
      32x32 obstacle mazes, Dyna-Q alpha .99 gamma .99 eps .1 model-lr .9, B = 50 planning
@@ -35,9 +45,9 @@ DESIGN.md §4.2; §8d's eight-row figure of 32 817 B is reported beside it as `s
 per launch / mean launch duration, the latter measured with HIP events on the launch stream.
 `roofline.traffic` = HBM bytes per launch from the committed rocprofv3 PMC passes and
 `roofline.frac_measured` = traffic / launch duration / peak — the PHYSICAL HBM utilisation;
-`roofline.limiter` names what bounds the kernel.  `cpu_baseline` = the NumPy
-restatement of the reference's single-instance loop (oracle/ref_loop.py), one core, on a bounded
-sample of the same workload (rank 0, N = 1).
+`roofline.limiter` names what bounds the kernel.  `cpu_baseline` (--full) = the
+NumPy restatement of the reference's single-instance loop (oracle/ref_loop.py), one core, on a
+bounded sample of the same workload (rank 0, N = 1).
 """
 from __future__ import annotations
 
@@ -729,7 +739,60 @@ def pmc_traffic_leg(key, kernel):
     return entry['hbm_bytes_per_launch']
 
 
-def run_config(cfg_name, args, rank, world_size, device, dist, repeat_for=0.0):
+DUMP_INSTANCES = 256            # instances sampled by --dump-outputs (fewer where a table is large)
+DUMP_BYTES = 64 * 10 ** 6       # bound of everything --dump-outputs writes
+
+
+def collect_outputs(cfg, agent, base, n, n_global, sums):
+    """--dump-outputs: what the timed path hands its caller after its last launch, for a fixed,
+    seeded sample of global instance ids (the same sample for any split over ranks) — this rank's
+    share of the agents' tables and instance words, and the global monitor sums.  Integers are
+    written as float64 (exact), the float32 tables as they are."""
+    S = int(agent.n_states)
+    per_instance = S * S * 4 if cfg['agent'] == 'sr' else S * 4 * 4 * 4
+    k = max(1, min(DUMP_INSTANCES, n_global, DUMP_BYTES // 2 // per_instance))
+    ids = np.sort(np.random.default_rng(SEED).choice(n_global, size=k, replace=False))
+    mine = ids[(ids >= base) & (ids < base + n)]
+    sel = torch.as_tensor(mine - base, dtype=torch.int64, device=agent.inst.device)
+    out = {'instance_ids': mine.astype(np.float64),
+           'instance_words': agent.inst[sel].cpu().numpy().astype(np.float64)}
+    if cfg['agent'] == 'sr':
+        out['sr'] = agent._sr[sel].cpu().numpy()
+        out['sr_rewards'] = agent._rw[sel].cpu().numpy()
+        out['sr_transitions'] = agent._T[sel].cpu().numpy().astype(np.float32)
+    else:
+        out['q'] = agent._q[sel].cpu().numpy()
+    if cfg['agent'] == 'dynaq':      # the model's packed records (memory/dyna_q.py), decoded
+        raw = agent.M.table[sel].cpu().numpy()
+        out['model_reward'] = (raw & 0xFFFFFFFF).astype(np.uint32).view(np.float32)
+        out['model_next'] = ((raw >> 32) & 0xFFFF).astype(np.float32)
+        out['model_terminal'] = ((raw >> 48) & 1).astype(np.float32)
+    out['monitor_lat_sum'] = np.asarray(sums.lat_sum, dtype=np.float64)
+    out['monitor_lat_cnt'] = np.asarray(sums.lat_cnt, dtype=np.float64)
+    out['monitor_reward_sum'] = np.asarray(sums.reward_sum, dtype=np.float64)
+    out['monitor_steps_done'] = np.array([sums.steps_done], dtype=np.float64)
+    return out
+
+
+def write_outputs(path, outputs, rank, dist):
+    """Rank 0 writes the sampled instances of every rank (in global id order) and the monitor
+    sums (already global) as path/<name>.npy."""
+    parts = [outputs]
+    if dist is not None and dist.get_world_size() > 1:
+        parts = [None] * dist.get_world_size()
+        dist.all_gather_object(parts, outputs)
+    if rank != 0:
+        return
+    merged = {name: (a if name.startswith('monitor_') else np.concatenate([p[name] for p in parts]))
+              for name, a in parts[0].items()}
+    assert sum(a.nbytes for a in merged.values()) <= DUMP_BYTES
+    os.makedirs(path, exist_ok=True)
+    for name, a in merged.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(path, name + '.npy'), a)
+
+
+def run_config(cfg_name, args, rank, world_size, device, dist, repeat_for=0.0, outputs=None):
     from cobel_amd.misc.sharding import shard_instances
     cfg = dict(CONFIGS[cfg_name])
     if args.instances:
@@ -837,6 +900,8 @@ def run_config(cfg_name, args, rank, world_size, device, dist, repeat_for=0.0):
         replays = int(agent.replays_done.item()) - replays_before
     if cfg['agent'] == 'sr':
         sr_moved = (agent.traffic - sr_before).cpu().numpy().astype(np.int64)
+    if outputs is not None:     # (--dump-outputs: the state after the last timed launch)
+        outputs.update(collect_outputs(cfg, agent, base, n, n_global, sums))
     # The reported window is the one above.  With --min-seconds the same window is repeated
     # (untimed for `value`) so that an outside observer sampling GPU utilisation every few seconds
     # sees the job; the spread of the repeats is reported next to the headline.
@@ -1113,11 +1178,13 @@ def main():
     # C2 (4 096) and C4 (512), twice that for C3 (2 048)
     ap.add_argument('--steps', type=int, default=4)
     ap.add_argument('--warmup', type=int, default=1)
-    ap.add_argument('--min-seconds', type=float, default=3.0,
+    ap.add_argument('--min-seconds', type=float, default=None,
                     help='repeat the headline window until this much GPU time has been spent '
-                         '(0: one window only); the reported value is always the first window')
+                         '(0: one window only; default 3 with --full, else 0); the reported value '
+                         'is always the first window')
     ap.add_argument('--config', default='C3', choices=sorted(CONFIGS))
-    ap.add_argument('--also', default='C2,C4,C6', help='extra configs reported under "other_configs"')
+    ap.add_argument('--also', default=None,
+                    help='with --full: extra configs reported under "other_configs" (default C2,C4,C6)')
     ap.add_argument('--weak', action='store_true',
                     help='every rank runs the full instance count (default: the instances of the '
                          'configuration are split over the ranks, BASELINE config 3)')
@@ -1135,18 +1202,33 @@ def main():
                     help='with one rank: initialise the process group all the same, so that the '
                          'barriers, the MIN all-reduce of the pre-training and the monitor all-gather '
                          'go through the backend (RCCL on a one-GPU box)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--full', action='store_true',
+                    help='also measure everything beside the headline: the --also configs, the legs, '
+                         'the CPU baselines, repeated windows (--min-seconds 3) and bench_full.json; '
+                         'without it a run sets up, warms up, times --steps launches and reports')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: no CPU baselines')
+    ap.add_argument('--print-full', action='store_true',
                     help='print the full result object as the one stdout line (profiling scripts) '
                          'instead of the compact one')
-    ap.add_argument('--full-out', default='bench_full.json',
-                    help='where rank 0 writes the full result object ("" = nowhere)')
-    ap.add_argument('--no-c5', action='store_true', help='skip the network legs (profiling runs)')
+    ap.add_argument('--full-out', default=None,
+                    help='where rank 0 writes the full result object ("" = nowhere; default '
+                         'bench_full.json with --full, else nowhere)')
+    ap.add_argument('--no-c5', action='store_true', help='with --full: skip the legs (profiling runs)')
     ap.add_argument('--legs', default=None,
-                    help='comma-separated subset of the legs behind --also (C5_f64, C5_f32, dyna_dqn, '
-                         'dyna_dsr, C1, grid_search, general_hex_q, general_wide_q, general_wide_q_lane, '
-                         'general_dynaq_b100); default: all')
+                    help='comma-separated subset of the legs (C5_f64, C5_f32, dyna_dqn, dyna_dsr, C1, '
+                         'grid_search, general_hex_q, general_wide_q, general_wide_q_lane, '
+                         'general_dynaq_b100) to run; default: all of them with --full, none without')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed launches, write what the headline configuration computed '
+                         'in the last one (a fixed, seeded sample of its instances) as DIR/<name>.npy')
     args = ap.parse_args()
+    if args.min_seconds is None:
+        args.min_seconds = 3.0 if args.full else 0.0
+    if args.also is None:
+        args.also = 'C2,C4,C6' if args.full else ''
+    if args.full_out is None:
+        args.full_out = 'bench_full.json' if args.full else ''
+    cpu_baselines = args.full and not args.no_cpu_baseline
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(spawn_ranks(sys.argv[1:], args.gpus))   # (nothing here has touched the GPU yet)
@@ -1186,7 +1268,9 @@ def main():
 
     for c in CONFIGS.values():
         c['instances'] = scaled(c['instances'])
-    res, cfg = run_config(args.config, args, rank, world_size, device, dist, args.min_seconds)
+    outputs = {} if args.dump_outputs else None
+    res, cfg = run_config(args.config, args, rank, world_size, device, dist, args.min_seconds,
+                          outputs=outputs)
     others = {}
     if world_size == 1 and not args.instances and (args.also or args.legs):
         for name in [c for c in args.also.split(',') if c and c != args.config]:
@@ -1203,18 +1287,18 @@ def main():
                     others[name]['reactivations_per_s'] = r['reactivations_per_s']
                 # the reference's single-process loop on the same world, timed beside
                 # every leg that has one (C2 / C4 / C6; >= 2 000 env steps each)
-                if rank == 0 and not args.no_cpu_baseline:
+                if rank == 0 and cpu_baselines:
                     others[name]['cpu_baseline'] = cpu_baseline(name, CONFIGS[name], 8.0)
             except Exception as e:  # e.g. not enough HBM for C4 on a shared device
                 others[name] = {'error': '%s: %s' % (type(e).__name__, e)}
         gc.collect()
         torch.cuda.empty_cache()
-        legs = [] if (args.no_c5 and args.legs is None) else [
+        legs = [] if ((args.no_c5 or not args.full) and args.legs is None) else [
             ('C5_f64', lambda: run_c5(device, 'f64', n=scaled(8192))),
             ('C5_f32', lambda: run_c5(device, 'f32', n=scaled(8192))),
             ('dyna_dqn', lambda: run_dyna_dqn(device, scaled(8192))),
             ('dyna_dsr', lambda: run_dyna_dsr(device, scaled(8192))),
-            ('C1', lambda: run_c1(device, not args.no_cpu_baseline)),
+            ('C1', lambda: run_c1(device, cpu_baselines)),
             ('grid_search', lambda: run_grid_search(device, 16 if args.scale == 1.0 else 4)),
             ('general_hex_q', lambda: run_general(device, 'hex_q', scaled(65536))),
             ('general_wide_q', lambda: run_general(device, 'wide_q', scaled(65536))),
@@ -1232,8 +1316,10 @@ def main():
                 others[name] = {'error': '%s: %s' % (type(e).__name__, e)}
             gc.collect()
             torch.cuda.empty_cache()
+    if outputs is not None:
+        write_outputs(args.dump_outputs, outputs, rank, dist)
     if rank == 0:
-        if world_size == 1 and not args.no_cpu_baseline:
+        if world_size == 1 and cpu_baselines:
             res['cpu_baseline'] = cpu_baseline(args.config, cfg)
         if others:
             res['other_configs'] = others
@@ -1248,7 +1334,7 @@ def main():
                 args.full_out = ''
         print('bench.py full result: ' + full, file=sys.stderr)
         sys.stderr.flush()
-        line = full if args.full else compact(res, args.full_out or None)
+        line = full if args.print_full else compact(res, args.full_out or None)
         os.write(json_fd, (line + '\n').encode())
     if dist is not None:
         dist.destroy_process_group()

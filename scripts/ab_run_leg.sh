@@ -4,7 +4,7 @@
 LEGS=${1:-grid_search}
 for k in 1 2; do
   for L in A B; do
-    COBEL_LIB=$PWD/cobel-rl_amd/lib/libcobel_$L.so timeout -k 10 300 python bench.py --full --also "" --legs $LEGS --no-cpu-baseline --min-seconds 0 --steps 4 --full-out "" 2>/dev/null | python -c "
+    COBEL_LIB=$PWD/cobel-rl_amd/lib/libcobel_$L.so timeout -k 10 300 python bench.py --full --print-full --also "" --legs $LEGS --no-cpu-baseline --min-seconds 0 --steps 4 --full-out "" 2>/dev/null | python -c "
 import json,sys
 r=json.load(sys.stdin)
 for k,v in r.get('other_configs',{}).items():

@@ -1,4 +1,4 @@
-"""From a rocprofv3 kernel trace of `python3 bench.py --no-cpu-baseline --min-seconds 0`: the
+"""From a rocprofv3 kernel trace of `python3 bench.py --full --no-cpu-baseline --min-seconds 0`: the
 durations of the launches bench.py TIMES for each headline kernel — the last `--steps` (4)
 dispatches of that kernel inside its leg; the dispatches before them are the untimed warm-up /
 pre-training launches (C3 pre-trains for dozens of launches on younger, cheaper agents, so the

@@ -1,9 +1,9 @@
 """Reduce the two rocprofv3 PMC passes of bench.py to profiles/rNN_pmc_traffic.json.
 
     rocprofv3 --kernel-trace --pmc FETCH_SIZE -d gpurun_out/pmc_fetch -o f --output-format csv \
-        -- python3 bench.py --no-cpu-baseline --no-c5
+        -- python3 bench.py --full --no-cpu-baseline --no-c5
     rocprofv3 --kernel-trace --pmc WRITE_SIZE -d gpurun_out/pmc_write -o w --output-format csv \
-        -- python3 bench.py --no-cpu-baseline --no-c5
+        -- python3 bench.py --full --no-cpu-baseline --no-c5
     python scripts/pmc_summary.py <fetch counter_collection.csv> <write counter_collection.csv> NN
 
 Per launch of the dominant kernel of each config (mean over the TIMED launches: the last four

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Generate the golden vectors in this directory from the REAL reference.
 
-Runs only in the build container (needs /root/reference); the .npz files it
-writes are committed and are the only thing that travels to the GPU box.
+Needs a checkout of the reference (CoBeL-RL 3.0.1), whose ``src`` directory is named by
+COBEL_REFERENCE_SRC; the .npz files it writes are committed, and the tests read only them.
 
 The reference targets Python >= 3.11 with gymnasium/PyQt6/pyqtgraph installed;
 this container has Python 3.10 and none of them, so a small import shim
@@ -11,7 +11,7 @@ GUI / space modules.  No reference arithmetic is replaced: worlds, env, policy,
 memory and agents below are the reference's own classes, driven by
 ``oracle.philox.TapeRNG`` so that they consume the build's Philox streams.
 
-    python tests/golden/gen_golden.py            # rewrite every fixture
+    COBEL_REFERENCE_SRC=<reference>/src python tests/golden/gen_golden.py   # rewrite every fixture
 """
 from __future__ import annotations
 
@@ -27,8 +27,8 @@ import typing_extensions as te
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
-# Where the fixtures are written: this directory, or a scratch directory for the test that
-# re-generates them and compares with the committed files (tests/test_golden_regen.py).
+# Where the fixtures are written: this directory, or a scratch directory to compare a fresh
+# generation with the committed files.
 OUT = os.environ.get('COBEL_GOLDEN_OUT', HERE)
 
 
@@ -85,7 +85,10 @@ def load_reference():
         m = _Any(name)
         m.__path__ = []
         sys.modules[name] = m
-    sys.path.insert(0, '/root/reference/src')
+    src = os.environ.get('COBEL_REFERENCE_SRC')
+    if not src or not os.path.isdir(os.path.join(src, 'cobel')):
+        sys.exit('gen_golden.py: set COBEL_REFERENCE_SRC to the src directory of the reference')
+    sys.path.insert(0, src)
     import cobel  # noqa: F401
     return cobel
 

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import free_port
@@ -23,17 +24,35 @@ def _line(out: str) -> dict:
     return json.loads(lines[0])
 
 
+def _dumped(path) -> dict:
+    """The arrays of a --dump-outputs directory: float32 / float64 only, 64 MB at most."""
+    arrays = {f[:-4]: np.load(os.path.join(str(path), f)) for f in sorted(os.listdir(str(path)))}
+    assert arrays and all(f.endswith('.npy') for f in os.listdir(str(path)))
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+    assert sum(a.nbytes for a in arrays.values()) <= 64 * 10 ** 6
+    return arrays
+
+
+def _same_outputs(a: dict, b: dict) -> None:
+    assert set(a) == set(b)
+    for name in a:
+        assert a[name].shape == b[name].shape and np.array_equal(a[name], b[name], equal_nan=True), name
+
+
 @pytest.mark.parametrize('config,instances', [('C3', 768), ('C4', 96)])
-def test_two_ranks_split_the_instances_and_report_the_same_monitors(config, instances):
+def test_two_ranks_split_the_instances_and_report_the_same_monitors(config, instances, tmp_path):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0')
     args = ['--config', config, '--instances', str(instances), '--env-steps', '64'] + COMMON
-    one = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1'] + args,
+    one = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1'] + args
+                         + ['--dump-outputs', str(tmp_path / 'one')],
                          capture_output=True, text=True, timeout=900, env=env)
     assert one.returncode == 0, one.stderr[-3000:]
     two = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1',
                           '--nproc-per-node', '2', '--master-addr', '127.0.0.1', '--master-port',
                           str(free_port()), os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--backend',
-                          'gloo'] + args, capture_output=True, text=True, timeout=900, env=env)
+                          'gloo'] + args + ['--dump-outputs', str(tmp_path / 'two')],
+                         capture_output=True, text=True, timeout=900, env=env)
     assert two.returncode == 0, two.stderr[-3000:]
     a, b = _line(one.stdout), _line(two.stdout)
     for r, n in ((a, 1), (b, 2)):
@@ -47,6 +66,8 @@ def test_two_ranks_split_the_instances_and_report_the_same_monitors(config, inst
     for key in ('trials_finished', 'escape_latency_sum', 'trial_reward_sum'):
         assert a['monitors'][key] == b['monitors'][key], key
     assert a['monitors']['trials_finished'] > 0
+    # the dumped sample is keyed by global instance ids: the same arrays for any split
+    _same_outputs(_dumped(tmp_path / 'one'), _dumped(tmp_path / 'two'))
 
 
 def test_weak_scaling_option_runs_the_full_count_per_rank():
@@ -129,13 +150,13 @@ def test_two_gpus_over_rccl_report_the_same_monitors():
 
 
 def test_every_default_leg_runs_and_carries_a_roofline(tmp_path):
-    """The default command at 1/50 of the instance counts: no leg may end in an "error" key (round
+    """The --full command at 1/50 of the instance counts: no leg may end in an "error" key (round
     2's C6 leg did, unnoticed) and every leg states its roofline.  The stdout line is the COMPACT
     object (round 4's full line of 22 KB was not taken by the driver's parser): under 6 000 bytes,
     every key of the contract, a dtype on every leg; the full objects are in --full-out."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0')
     full_path = str(tmp_path / 'bench_full.json')
-    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--scale', '0.02',
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--scale', '0.02',
                           '--steps', '2', '--warmup', '1', '--min-seconds', '0', '--max-pretrain',
                           '24', '--full-out', full_path], capture_output=True, text=True, timeout=1500,
                          env=env)
@@ -219,3 +240,37 @@ def test_one_rank_process_group_over_rccl():
     assert a['pretraining']['untimed_launches_in_all'] == b['pretraining']['untimed_launches_in_all'] == 17
     for key in ('trials_finished', 'escape_latency_sum', 'trial_reward_sum'):
         assert a['monitors'][key] == b['monitors'][key], key
+
+
+def test_plain_run_times_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """Without --full a run sets up, warms up, times exactly --steps launches and prints its line:
+    no other configuration, leg, CPU baseline, repeated window or bench_full.json.  --dump-outputs
+    writes the state of the last timed launch, the same in a second run with the same arguments."""
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0')
+    n, budget, steps = 1024, 64, 3
+    args = ['--config', 'C3', '--instances', str(n), '--env-steps', str(budget), '--steps', str(steps),
+            '--warmup', '1', '--max-pretrain', '9']
+    lines, dumps = [], []
+    for k in range(2):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py')] + args
+                             + ['--dump-outputs', str(tmp_path / ('out%d' % k))],
+                             capture_output=True, text=True, timeout=900, env=env, cwd=str(tmp_path))
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines.append(_line(out.stdout))
+        dumps.append(_dumped(tmp_path / ('out%d' % k)))
+    r = lines[0]
+    for key in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert key in r, key
+    assert r['steps'] == steps and r['value'] > 0 and r['ms_per_step'] > 0
+    for key in ('cpu_baseline', 'other_configs', 'repeat_windows', 'full'):
+        assert key not in r, key
+    assert not (tmp_path / 'bench_full.json').exists()
+    _same_outputs(dumps[0], dumps[1])
+    d = dumps[0]
+    assert {'q', 'model_reward', 'model_next', 'model_terminal', 'instance_ids', 'instance_words',
+            'monitor_lat_sum', 'monitor_steps_done'} <= set(d)
+    assert d['q'].shape == (256, 1024, 4) and np.count_nonzero(d['q']) > 0
+    assert np.array_equal(d['instance_ids'], np.unique(d['instance_ids']))
+    # every launch the run made is in the dumped monitors: the untimed ones and exactly --steps more
+    launches = r['pretraining']['untimed_launches_in_all'] + steps
+    assert int(d['monitor_steps_done'][0]) == n * budget * launches
