@@ -119,14 +119,33 @@ int cobel_world_check4(const cobel_world* w, const char* who);  // ... and a fou
 
 // Packed 8-byte records.
 //   model entry  : lo = f32 reward estimate, hi = next_state | nonterminal << 16
-//   replay entry : lo = f32 reward,          hi = state | next_state << 14 | action << 28 | nonterminal << 30
 __host__ __device__ __forceinline__ uint64_t cobel_model_pack(float r, uint32_t ns, uint32_t nt) {
   return (uint64_t)__builtin_bit_cast(uint32_t, r) | ((uint64_t)(ns | (nt << 16)) << 32);
 }
+//   replay entry (QAgent experience log, worlds of A actions): lo = f32 reward, hi =
+//     A <= 4      : state | next_state << 14 | action << 28 | nonterminal << 30  (16 384 states)
+//     A = 5 .. 8  : state | next_state << 14 | action << 28 | nonterminal << 31  (16 384 states)
+//     A = 9 .. 32 : state | next_state << 13 | action << 26 | nonterminal << 31  ( 8 192 states)
+//   (worlds whose states or actions do not fit keep two words per entry: general.hip)
+// A is a compile-time constant, or at least known to the compiler to lie on one side of 8 (e.g.
+// min(A, 8)), wherever the layout should fold to constant shifts.
 __host__ __device__ __forceinline__ uint64_t cobel_log_pack(float r, uint32_t s, uint32_t a,
-                                                            uint32_t ns, uint32_t nt) {
-  return (uint64_t)__builtin_bit_cast(uint32_t, r) |
-         ((uint64_t)(s | (ns << 14) | (a << 28) | (nt << 30)) << 32);
+                                                            uint32_t ns, uint32_t nt, int A) {
+  const uint32_t hi = A <= 8 ? (s | (ns << 14) | (a << 28) | (nt << (A <= 4 ? 30 : 31)))
+                             : (s | (ns << 13) | (a << 26) | (nt << 31));
+  return (uint64_t)__builtin_bit_cast(uint32_t, r) | ((uint64_t)hi << 32);
+}
+struct cobel_log_rec {
+  uint32_t s, a, ns, nt;
+  float r;
+};
+__host__ __device__ __forceinline__ cobel_log_rec cobel_log_unpack(uint64_t rec, int A) {
+  const uint32_t hi = (uint32_t)(rec >> 32);
+  const float r = __builtin_bit_cast(float, (uint32_t)rec);
+  if (A <= 8)
+    return {hi & 0x3fffu, (hi >> 28) & (A <= 4 ? 3u : 7u), (hi >> 14) & 0x3fffu,
+            (hi >> (A <= 4 ? 30 : 31)) & 1u, r};
+  return {hi & 0x1fffu, (hi >> 26) & 31u, (hi >> 13) & 0x1fffu, hi >> 31, r};
 }
 
 // Device-side view of the epsilon-greedy CDF table (cobel_policy_table), passed by value.
@@ -134,12 +153,49 @@ struct cobel_cdf_table {
   double cdf[16][16][4];
 };
 
+#if defined(__HIPCC__)
+// ---- wavefront helpers ------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t rl(uint32_t v, int lane) {
+  return (uint32_t)__builtin_amdgcn_readlane((int)v, lane);
+}
+__device__ __forceinline__ float rlf(float v, int lane) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane));
+}
+__device__ __forceinline__ uint32_t rfl(uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+}
+__device__ __forceinline__ float rflf(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+}
+__device__ __forceinline__ uint32_t fbits(float x) { return __builtin_bit_cast(uint32_t, x); }
+// successor a of a four-action world record: next[0..3] packed as two words of two u16
+__device__ __forceinline__ uint32_t next_of(uint32_t w0, uint32_t w1, int a) {
+  const uint32_t w = (a & 2) ? w1 : w0;
+  return (a & 1) ? (w >> 16) : (w & 0xffffu);
+}
+// max of a Q row in two instructions (fmaxf() costs two more: it first quiets each operand)
+__device__ __forceinline__ float max4(const float4 v) {
+  float m;
+  asm("v_max_f32 %0, %1, %2\n\tv_max3_f32 %0, %0, %3, %4"
+      : "=&v"(m)
+      : "v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w));
+  return m;
+}
+// Orders this wave's LDS traffic across lanes: a memory fence for the compiler, no instruction
+// (fences at wavefront scope emit none on gfx950; __builtin_amdgcn_wave_barrier alone does not
+// order memory accesses).  Enough only where the LDS is the wave's own or one wave per workgroup
+// touches it — no s_barrier.
+__device__ __forceinline__ void wsync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // Per-trial monitors are striped: workgroup b adds into copy b % mon_stripes of each array, so
 // that the atomics of thousands of workgroups finishing the same trial indices do not all queue on
 // the same few cache lines of one L2 channel (measured on C2: 600 000 atomics per launch onto ~150
 // hot addresses cost 1.1 ms of a 2.8 ms launch; Dyna-Q on 65 536 5x5 worlds ran 2x slower).  The
 // caller sums the copies.
-#if defined(__HIPCC__)
 __device__ __forceinline__ size_t cobel_mon_offset(int32_t mon_stripes, int32_t trial_cap) {
   const unsigned stripes = mon_stripes > 1 ? (unsigned)mon_stripes : 1u;
   return (size_t)((unsigned)blockIdx.x % stripes) * (size_t)trial_cap;

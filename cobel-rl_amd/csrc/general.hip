@@ -39,23 +39,6 @@ struct gen_args {
   float alpha_f, gamma_f, model_lr_f;
 };
 
-// QAgent replay record: lo = f32 reward, hi = s | ns << 14 | action << 28 | nonterminal << 30 for
-// up to four actions (the layout of the fast kernels), nonterminal << 31 up to eight, and beyond
-// eight actions (up to 32; worlds of at most 8 192 states) s | ns << 13 | action << 26 |
-// nonterminal << 31.
-// (worlds whose states or actions do not fit the packed word — cobel_hip.h COBEL_LOG_WORDS — keep
-//  TWO words per entry: {f32 reward, action | nonterminal << 8}, {state, next state})
-__device__ __forceinline__ uint64_t log_pack_n(float r, uint32_t s, uint32_t a, uint32_t ns,
-                                               uint32_t nt, int A) {
-  const uint32_t hi = A <= 8 ? (s | (ns << 14) | (a << 28) | (nt << (A <= 4 ? 30 : 31)))
-                             : (s | (ns << 13) | (a << 26) | (nt << 31));
-  return (uint64_t)__builtin_bit_cast(uint32_t, r) | ((uint64_t)hi << 32);
-}
-
-}  // namespace
-
-namespace {
-
 // The action mask of row i (bit a = action a allowed; policy/greedy.py:79-81): one byte per row in
 // worlds of up to eight actions, one 32-bit word per row beyond (the AMAX = 16 / 32 instantiations).
 template <int AMAX>
@@ -273,7 +256,11 @@ __global__ __launch_bounds__(64) void k_tab_general(const gen_args G) {
   uint64_t* const model = AGENT == COBEL_AGENT_DYNAQ ? G.r.model + (size_t)i * S * A : nullptr;
   uint16_t* const mindex =
       (AGENT == COBEL_AGENT_DYNAQ && G.r.model_index) ? G.r.model_index + (size_t)i * S * A : nullptr;
+  // replay records: ONE packed word (cobel_log_pack; A_log: this instantiation's rows of AMAX
+  // values serve A <= AMAX, said so to fold the layout), or two where the world does not fit it:
+  // {f32 reward, action | nonterminal << 8}, {state, next state}
   const bool wide = COBEL_LOG_WORDS(A, S) == 2;
+  const int A_log = AMAX > 8 ? A : min(A, 8);
   uint64_t* const rlog = (AGENT == COBEL_AGENT_Q && G.r.replay_log)
                              ? G.r.replay_log + (size_t)i * G.r.log_cap * (wide ? 2 : 1)
                              : nullptr;
@@ -499,7 +486,7 @@ __global__ __launch_bounds__(64) void k_tab_general(const gen_args G) {
                               ((uint64_t)((uint32_t)a | (nt << 8)) << 32);
           rlog[2u * loglen + 1u] = (uint64_t)(uint32_t)state | ((uint64_t)(uint32_t)ns << 32);
         } else {
-          rlog[loglen] = log_pack_n(r, (uint32_t)state, (uint32_t)a, (uint32_t)ns, nt, A);
+          rlog[loglen] = cobel_log_pack(r, (uint32_t)state, (uint32_t)a, (uint32_t)ns, nt, A_log);
         }
         loglen += 1u;
       }
@@ -535,17 +522,13 @@ __global__ __launch_bounds__(64) void k_tab_general(const gen_args G) {
                 return rec_t{idx, rlog[idx], 0ull};
               },
               [&](const rec_t& rc) -> upd_t {
-                const uint32_t hi = (uint32_t)(rc.bits >> 32);
-                if (wide)
+                if (wide) {
+                  const uint32_t hi = (uint32_t)(rc.bits >> 32);
                   return upd_t{(int)(uint32_t)rc.bits2, (int)(hi & 0xffu), (int)(rc.bits2 >> 32),
                                __builtin_bit_cast(float, (uint32_t)rc.bits), (hi >> 8) & 1u};
-                if (AMAX > 8 && A > 8)   // (s | ns << 13 | action << 26 | nonterminal << 31)
-                  return upd_t{(int)(hi & 0x1fffu), (int)((hi >> 26) & 31u), (int)((hi >> 13) & 0x1fffu),
-                               __builtin_bit_cast(float, (uint32_t)rc.bits), (hi >> 31) & 1u};
-                const uint32_t ra = A <= 4 ? (hi >> 28) & 3u : (hi >> 28) & 7u;
-                const uint32_t rnt = A <= 4 ? (hi >> 30) & 1u : (hi >> 31) & 1u;
-                return upd_t{(int)(hi & 0x3fffu), (int)ra, (int)((hi >> 14) & 0x3fffu),
-                             __builtin_bit_cast(float, (uint32_t)rc.bits), rnt};
+                }
+                const cobel_log_rec u = cobel_log_unpack(rc.bits, A_log);
+                return upd_t{(int)u.s, (int)u.a, (int)u.ns, u.r, u.nt};
               },
               false);
         }

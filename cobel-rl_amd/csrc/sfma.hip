@@ -90,20 +90,6 @@ __device__ __forceinline__ sfma_lds carve(unsigned char* base, int S) {
   return L;
 }
 
-// Orders this wave's LDS traffic across lanes (one wave per workgroup: no s_barrier needed).
-__device__ __forceinline__ void wsync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ uint32_t rfl(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
-}
-__device__ __forceinline__ uint32_t next_of(uint32_t w0, uint32_t w1, int a) {
-  const uint32_t w = (a & 2) ? w1 : w0;
-  return (a & 1) ? (w >> 16) : (w & 0xffffu);
-}
 // Cross-lane data movement on the VALU (DPP) instead of ds_bpermute through the LDS crossbar: a
 // reactivation is a chain of five dependent wave-wide reductions / scans, so their latency is the
 // critical path.  Controls: quad_perm 0x00-0xff, row_shr:n 0x110+n, wave_shr:1 0x138, row_mirror

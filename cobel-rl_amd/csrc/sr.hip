@@ -272,17 +272,6 @@ __device__ __forceinline__ uint64_t t_set(uint64_t row, int k, uint32_t v) {
   return (row & ~(0xffffull << (16 * k))) | ((uint64_t)v << (16 * k));
 }
 
-__device__ __forceinline__ uint32_t rl(uint32_t v, int lane) {
-  return (uint32_t)__builtin_amdgcn_readlane((int)v, lane);
-}
-__device__ __forceinline__ uint32_t rfl(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
-}
-__device__ __forceinline__ uint32_t next_of(uint32_t w0, uint32_t w1, int a) {
-  const uint32_t w = (a & 2) ? w1 : w0;
-  return (a & 1) ? (w >> 16) : (w & 0xffffu);
-}
-
 // PRE (VEC and S <= 1024): as soon as the action is known, wave a starts loading the value row it
 // will need in the NEXT step (row T[ns][a]) into registers, so the HBM latency of the four value
 // rows overlaps the row update of this step.  The one row that cannot be prefetched — SR[s], which

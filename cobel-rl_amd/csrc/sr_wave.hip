@@ -53,22 +53,6 @@ __device__ __forceinline__ int t_of(uint64_t row, int k) { return (int)((row >> 
 __device__ __forceinline__ uint64_t t_set(uint64_t row, int k, uint32_t v) {
   return (row & ~(0xffffull << (16 * k))) | ((uint64_t)v << (16 * k));
 }
-__device__ __forceinline__ uint32_t rl(uint32_t v, int lane) {
-  return (uint32_t)__builtin_amdgcn_readlane((int)v, lane);
-}
-__device__ __forceinline__ float rlf(float v, int lane) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane));
-}
-__device__ __forceinline__ uint32_t rfl(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
-}
-__device__ __forceinline__ float rflf(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
-}
-__device__ __forceinline__ uint32_t next_of(uint32_t w0, uint32_t w1, int a) {
-  const uint32_t w = (a & 2) ? w1 : w0;
-  return (a & 1) ? (w >> 16) : (w & 0xffffu);
-}
 // A load that is served by L2, never by this CU's L1: single elements of rows that OTHER lanes
 // of the wave wrote in an earlier step.
 __device__ __forceinline__ float ld_l2(const float* p) {

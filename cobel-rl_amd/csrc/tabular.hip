@@ -27,6 +27,7 @@
 
 #include "cobel_common.h"
 #include "cobel_policy.h"
+#include "cobel_tab_batch.h"
 
 namespace {
 
@@ -48,25 +49,6 @@ struct tab_args {
 
 __device__ __forceinline__ size_t mon_stripe_offset(const cobel_tab_run_t& r) {
   return cobel_mon_offset(r.mon_stripes, r.trial_cap);
-}
-
-__device__ __forceinline__ uint32_t rl(uint32_t v, int lane) {
-  return (uint32_t)__builtin_amdgcn_readlane((int)v, lane);
-}
-__device__ __forceinline__ uint32_t rfl(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
-}
-// max of a Q row in two instructions (fmaxf() costs two more: it first quiets each operand)
-__device__ __forceinline__ float max4(const float4 v) {
-  float m;
-  asm("v_max_f32 %0, %1, %2\n\tv_max3_f32 %0, %0, %3, %4"
-      : "=&v"(m)
-      : "v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w));
-  return m;
-}
-__device__ __forceinline__ uint32_t next_of(uint32_t w0, uint32_t w1, int a) {
-  const uint32_t w = (a & 2) ? w1 : w0;
-  return (a & 1) ? (w >> 16) : (w & 0xffffu);
 }
 
 // LDS carve-up (bytes): Q 16*S | M16 8*S (Dyna-Q) | H 2048 (replay) | world 16*S (WLDS) | occ 4*S
@@ -152,6 +134,7 @@ __global__ __launch_bounds__(64) void k_tab_wpi(const tab_args A) {
   }
   float4* const Qs = L.Qs;
   float* const Qf = L.Qf;
+  uint32_t* const Qu = reinterpret_cast<uint32_t*>(lds_raw);   // (the planning batch's view)
 
   const int lane = (int)threadIdx.x;
   const int i = (int)blockIdx.x;
@@ -322,34 +305,12 @@ __global__ __launch_bounds__(64) void k_tab_wpi(const tab_args A) {
     mask_cur = amask ? (uint32_t)amask[s] & 15u : 15u;
   };
 
-  // ---- B sequential TD updates, executed as speculative rounds / conflict-free prefixes ------
-  // Lane j < B holds replay j = (idx -> (s, a), r, ns, nt).  The reference applies them in order
-  // (agent/dyna_q.py:329-330); j may run once every earlier lane that writes a cell j reads —
-  // s_i == ns_j (row of the max) or idx_i == idx_j (the cell itself) — has written.
+  // ---- B sequential TD updates (cobel_tab_batch.h) -------------------------------------------
+  // Lane j < B holds replay j = (idx -> (s, a), r, ns, nt).
   // (inside == true: the caller already runs under `lane < B`; one predicated region instead of
   //  one per table access)
   auto run_batch = [&](uint32_t idx, uint32_t ns, uint32_t nt, float r, bool inside = false) {
-    const bool on = inside || lane < BP;
-#if defined(COBEL_ABLATE) && COBEL_ABLATE == 3
-    return;
-#endif
-    // The rounds are speculative: every remaining lane computes its update from the table as it
-    // stands; a lane's result holds unless an earlier lane of this round that writes a cell it
-    // reads has CHANGED that cell — an update that leaves its cell as it was (all-zero regions
-    // of Q, converged entries) blocks nobody.  The lanes before the first one whose inputs moved
-    // are committed (only changed cells are written, so two lanes of one round never write the
-    // same cell), the rest goes again.  Same order of effects as the reference's loop; never
-    // fewer lanes per round than the conflict-free prefix.
-    // Who is held back is found IN the table (round 6, as in k_tab_pwg; until then two tables of
-    // lane masks keyed by the pair index, exact up to 1 024 states, and buckets with a verifying
-    // loop beyond): a lane that changes its cell raises it to the TAG ~lane with ds_max_u32 —
-    // tags are the bit patterns 0xffffffc0 .. 0xffffffff, above every float that is not a NaN of
-    // exactly that payload, so the cell then holds the tag of the EARLIEST lane that writes it —,
-    // every lane reads its five inputs again and is held back iff one of them is a tag above its
-    // own: an earlier writer of a cell it reads.  The earliest writer of a cell then stores the new
-    // value (committed) or puts the old one back (held back).  Exact for any state count, no byte
-    // of LDS beside the table.
-    auto td_of = [&](float q, float m) -> float {
+    cobel_tab_batch<4>(Qu, idx, ns, inside || lane < BP, BP, lane, [&](float q, float m) -> float {
       if (AGENT == COBEL_AGENT_DYNAQ) {
         // planning TD in float64, one rounding on store (NumPy promotion of the reference's
         // expression with a float32 table; see include/cobel_hip.h)
@@ -362,61 +323,7 @@ __global__ __launch_bounds__(64) void k_tab_wpi(const tab_args A) {
       float td = r + gnt * m;
       td = td - q;
       return q + alpha_f * td;
-    };
-    uint32_t* const Qu = reinterpret_cast<uint32_t*>(Qf);
-    const uint4* const Qs4u = reinterpret_cast<const uint4*>(Qs);
-    const uint32_t tag_mine = ~(uint32_t)lane;
-    // (`lo` = the first lane of the round: only a table that held a tag pattern to begin with — a NaN
-    //  no arithmetic produces — can hold it back; it is committed regardless, so every round ends
-    //  one lane further: garbage in, garbage out, never a batch that does not end)
-    auto tag_round = [&](bool act, bool ch, float q, float qn, int lo) -> int {
-      if (ch) atomicMax(&Qu[idx], tag_mine);
-      __builtin_amdgcn_wave_barrier();
-      uint32_t t = 0u, c2 = 0u;
-      if (act) {
-        const uint4 r2 = Qs4u[ns];
-        c2 = Qu[idx];
-        t = max(max(max(r2.x, r2.y), r2.z), max(r2.w, c2));
-      }
-#if defined(COBEL_ABLATE) && COBEL_ABLATE == 1
-      t = 0u;
-#endif
-      const unsigned long long blocked = __builtin_amdgcn_ballot_w64(act && t > tag_mine);
-      const int stop = max(blocked ? __ffsll((long long)blocked) - 1 : BP, lo + 1);
-      if (ch && c2 == tag_mine) Qf[idx] = lane < stop ? qn : q;
-      __builtin_amdgcn_wave_barrier();
-      return stop;
-    };
-    // (the first round written out in front of the loop over the rounds — most batches end with
-    //  it —, as in k_tab_pwg §4.1d: trained agents on 16 x 16 / 24 x 24 mazes +1.3 / +0.7 %,
-    //  scripts/experiments/exp_occ_trained.py)
-    int first;
-    {
-      float q = 0.0f, qn = 0.0f;
-      if (on) {
-        const float4 row = Qs[ns];
-        q = Qf[idx];
-        qn = td_of(q, max4(row));
-      }
-      const bool ch = on && __builtin_bit_cast(uint32_t, qn) != __builtin_bit_cast(uint32_t, q);
-      if (!__builtin_amdgcn_ballot_w64(ch)) {
-        STAMP(4);
-        return;
-      }
-      first = tag_round(on, ch, q, qn, 0);
-    }
-    while (first < BP) {
-      const bool act = on && lane >= first;
-      float q = 0.0f, qn = 0.0f;
-      if (act) {
-        const float4 row = Qs[ns];
-        q = Qf[idx];
-        qn = td_of(q, max4(row));
-      }
-      const bool ch = act && __builtin_bit_cast(uint32_t, qn) != __builtin_bit_cast(uint32_t, q);
-      if (!__ballot(ch)) break;
-      first = tag_round(act, ch, q, qn, first);
-    }
+    });
     STAMP(4);
   };
   // Dyna-Q batch drawn with x: model entries from LDS, reward estimates from HBM where flagged.
@@ -451,9 +358,8 @@ __global__ __launch_bounds__(64) void k_tab_wpi(const tab_args A) {
     }
   };
   auto replay_log = [&](uint64_t rec) {
-    const uint32_t lo = (uint32_t)rec, hi = (uint32_t)(rec >> 32);
-    run_batch((hi & 0x3fffu) * 4u + ((hi >> 28) & 3u), (hi >> 14) & 0x3fffu, (hi >> 30) & 1u,
-              __builtin_bit_cast(float, lo));
+    const cobel_log_rec u = cobel_log_unpack(rec, 4);
+    run_batch(u.s * 4u + u.a, u.ns, u.nt, u.r);
   };
 
   // interface/gridworld.py:142 — draw the start state of the next trial (false: all trials done)
@@ -668,7 +574,7 @@ __global__ __launch_bounds__(64) void k_tab_wpi(const tab_args A) {
         fix_r = Rn;
       } else if (rlog) {
         if (loglen < (uint32_t)A.r.log_cap) {
-          fresh_rec = cobel_log_pack(r, (uint32_t)state, (uint32_t)a, (uint32_t)ns, nt);
+          fresh_rec = cobel_log_pack(r, (uint32_t)state, (uint32_t)a, (uint32_t)ns, nt, 4);
           fresh_idx = loglen;
         }
       }
@@ -691,7 +597,7 @@ __global__ __launch_bounds__(64) void k_tab_wpi(const tab_args A) {
       }
       if (AGENT == COBEL_AGENT_Q && rlog && fresh_idx != ~0u) loglen += 1u;
       td_online = td;
-      __builtin_amdgcn_wave_barrier();
+      wsync();   // (lane 0's stores before the planning lanes read)
     }
     if (!FAST && A.r.last_exp && lane == 0) {
       int32_t* const e = A.r.last_exp + (size_t)i * 6;
@@ -1075,7 +981,7 @@ __global__ __launch_bounds__(64) void k_tab_lpi(const tab_args A) {
         Qlf[cell] = qsa + alpha_f * td;
         td_online = td;
         if (LOG && loglen < (uint32_t)A.r.log_cap) {
-          rlog[loglen] = cobel_log_pack(r, (uint32_t)state, (uint32_t)a, (uint32_t)ns, nt);
+          rlog[loglen] = cobel_log_pack(r, (uint32_t)state, (uint32_t)a, (uint32_t)ns, nt, 4);
           loglen += 1u;
         }
       }
@@ -1119,7 +1025,7 @@ __global__ __launch_bounds__(64) void k_tab_lpi(const tab_args A) {
     }
   }
   if (MON) {
-    __builtin_amdgcn_wave_barrier();
+    wsync();
     for (int k = lane; k < kMonSlots; k += 64)
       to_global(mon_base + k, wsum[k], wcnt[k] & 0xffffu, wcnt[k] >> 16, wrew[k]);
   }

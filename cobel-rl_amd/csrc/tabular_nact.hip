@@ -21,7 +21,7 @@
 //     one lane per update; the logged records are gathered from HBM one step ahead (the memory
 //     stream is counter based) and patched with the two records the gather cannot have seen; the
 //     B sequential float32 TD updates run as speculative rounds, the lanes to hold back found in
-//     the Q table itself (tags, round 6), as in k_tab_wpi / k_tab_pwg.
+//     the Q table itself (cobel_tab_batch.h, shared with k_tab_wpi).
 // Same streams, counters, arithmetic and order of effects as k_tab_general: identical Q tables,
 // logs, counters and monitors (tests/test_gpu_general.py, scripts/fuzz_topology.py).
 //
@@ -44,6 +44,7 @@
 
 #include "cobel_common.h"
 #include "cobel_policy.h"
+#include "cobel_tab_batch.h"
 
 namespace {
 
@@ -61,24 +62,6 @@ struct nact_args {
 };
 
 
-__device__ __forceinline__ uint32_t rl(uint32_t v, int lane) {
-  return (uint32_t)__builtin_amdgcn_readlane((int)v, lane);
-}
-__device__ __forceinline__ uint32_t rfl(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
-}
-__device__ __forceinline__ uint32_t fbits(float x) { return __builtin_bit_cast(uint32_t, x); }
-__device__ __forceinline__ float max8(const float4 a, const float4 b) {
-  return fmaxf(fmaxf(fmaxf(a.x, a.y), fmaxf(a.z, a.w)), fmaxf(fmaxf(b.x, b.y), fmaxf(b.z, b.w)));
-}
-
-// QAgent replay record of the general kernel (general.hip, log_pack_n): lo = f32 reward,
-// hi = s | ns << 14 | action << 28 | nonterminal << 30 up to four actions, << 31 beyond
-__device__ __forceinline__ uint64_t log_pack8(float r, uint32_t s, uint32_t a, uint32_t ns,
-                                              uint32_t nt, uint32_t nt_shift) {
-  return (uint64_t)fbits(r) | ((uint64_t)(s | (ns << 14) | (a << 28) | (nt << nt_shift)) << 32);
-}
-
 __host__ __device__ inline size_t nact_thr_words(int A) {
   return A > 1 ? ((size_t)1 << A) * (size_t)(A - 1) : 1;
 }
@@ -93,11 +76,6 @@ __host__ __device__ inline size_t nact_lds_bytes(int S, int A, int wpg, bool sha
   const size_t world = (size_t)S * (2 * W + 8);
   return thr + (shared ? world : world * wpg) + (size_t)wpg * ((size_t)S * W * 4);
 }
-// QAgent replay record of nine to 32 actions (general.hip): hi = s | ns << 13 | action << 26 | nt << 31
-__device__ __forceinline__ uint64_t log_pack32(float r, uint32_t s, uint32_t a, uint32_t ns, uint32_t nt) {
-  return (uint64_t)fbits(r) | ((uint64_t)(s | (ns << 13) | (a << 26) | (nt << 31)) << 32);
-}
-
 // PLAIN: training with a replay batch on a world of more than one action — what the step's
 // wave-uniform tests (learn, B > 0, A > 1) are compiled away for (as k_tab_lpi's EXTRA: a taken
 // branch is an instruction-buffer refill the wave waits for).
@@ -130,7 +108,8 @@ __global__ __launch_bounds__(512) void k_tab_wqn(const nact_args G) {
   uint16_t* const nextL = reinterpret_cast<uint16_t*>(wl);               // [S][W]
   uint2* const RT = reinterpret_cast<uint2*>(wl + (size_t)S * 2 * W);    // [S] {reward bits, terminal}
   unsigned char* const mine = lds_raw + off + (size_t)wave * ((size_t)S * W * 4);
-  float4* const Qs = reinterpret_cast<float4*>(mine);                    // [S][W / 4]
+  uint32_t* const Qu = reinterpret_cast<uint32_t*>(mine);                // [S][W] (replay batch)
+  const uint4* const Q4 = reinterpret_cast<const uint4*>(mine);          // [S][W / 4] (row maxima)
   float* const Qf = reinterpret_cast<float*>(mine);
 
   // ---- the threshold table (whole workgroup) ----------------------------------------------------
@@ -252,18 +231,12 @@ __global__ __launch_bounds__(512) void k_tab_wqn(const nact_args G) {
     eps_sel = P->epsilon;
   }
   asm volatile("" : "+v"(alpha_f), "+v"(gamma_f));
+  // the replay records' layout (cobel_log_pack): rows of 8 serve at most eight actions — said so
+  // here, that the layout folds to constant shifts.  (The batch decodes the records with the
+  // fields of the narrow layout hoisted out of the step loop: cobel_log_unpack(rec, A_log) there
+  // costs k_tab_wqn<true, 8, false> two more scalar spills.)
+  const int A_log = W == 8 ? min(A, 8) : W;
   const uint32_t nt_shift = A <= 4 ? 30u : 31u, a_mask = A <= 4 ? 3u : 7u;
-  // the maximum of a row of W values (pad cells hold -inf)
-  auto row_max = [&](uint32_t row) -> float {
-    float4 v = Qs[row * (WU / 4u)];
-    float m = fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w));
-#pragma unroll
-    for (uint32_t j = 1; j < WU / 4u; ++j) {
-      v = Qs[row * (WU / 4u) + j];
-      m = fmaxf(m, fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w)));
-    }
-    return m;
-  };
 
   // Cached Philox output: lanes < B hold memory block mb_idx (four consecutive batches), lanes 62
   // and 63 the policy blocks 2 pb_idx and 2 pb_idx + 1 (action draws 4 pb_idx .. 4 pb_idx + 3).
@@ -291,7 +264,7 @@ __global__ __launch_bounds__(512) void k_tab_wqn(const nact_args G) {
     return rec;
   };
 
-  // ---- B sequential float32 TD updates (q.py:305-313), speculative rounds ------------------------
+  // ---- B sequential float32 TD updates (q.py:305-313), cobel_tab_batch.h ------------------------
   // (nb = the updates of this pass: B, fewer in the last of several passes)
   auto run_batch = [&](uint64_t rec, const int nb) {
     const uint32_t lo = (uint32_t)rec, hi = (uint32_t)(rec >> 32);
@@ -300,70 +273,12 @@ __global__ __launch_bounds__(512) void k_tab_wqn(const nact_args G) {
     const uint32_t a = W == 8 ? (hi >> 28) & a_mask : (hi >> 26) & 31u;
     const uint32_t nt = W == 8 ? (hi >> nt_shift) & 1u : hi >> 31;
     const float r = __builtin_bit_cast(float, lo);
-    const uint32_t p = s * WU + a;
-    const bool on = lane < nb;
-    auto td_of = [&](float q) -> float {
-      const float m = W == 8 ? max8(Qs[ns * 2u], Qs[ns * 2u + 1u]) : row_max(ns);
+    cobel_tab_batch<W>(Qu, s * WU + a, ns, lane < nb, nb, lane, [&](float q, float m) -> float {
       const float gnt = nt ? gamma_f : 0.0f;
       float td = r + gnt * m;
       td = td - q;
       return q + alpha_f * td;
-    };
-    // Who is held back is found IN the table (round 6, as in k_tab_pwg / k_tab_wpi; until then two
-    // tables of lane masks beside every Q table): a lane that changes its cell raises it to the TAG
-    // ~lane with ds_max_u32 (bit patterns 0xffffffc0 .. 0xffffffff: above every float, the pad
-    // cells' -inf included, that is not a NaN of exactly that payload) — the cell then holds the
-    // tag of the EARLIEST lane that writes it; every lane reads its row and its cell again and is
-    // held back iff one of them is a tag above its own.  The earliest writer of a cell stores the
-    // new value (committed) or puts the old one back (held back).
-    uint32_t* const Qu = reinterpret_cast<uint32_t*>(Qf);
-    const uint4* const Qs4u = reinterpret_cast<const uint4*>(Qs);
-    const uint32_t tag_mine = ~(uint32_t)lane;
-    // (`lo` = the first lane of the round: committed regardless — only a table that held a tag
-    //  pattern to begin with could hold it back —, so every round ends one lane further)
-    auto tag_round = [&](bool act, bool ch, float q, float qn, int lo) -> int {
-      if (ch) atomicMax(&Qu[p], tag_mine);
-      __builtin_amdgcn_wave_barrier();
-      uint32_t t = 0u, c2 = 0u;
-      if (act) {
-        c2 = Qu[p];
-        t = c2;
-#pragma unroll
-        for (uint32_t j = 0; j < WU / 4u; ++j) {
-          const uint4 v = Qs4u[ns * (WU / 4u) + j];
-          t = max(max(max(v.x, v.y), max(v.z, v.w)), t);
-        }
-      }
-      const unsigned long long blocked = __builtin_amdgcn_ballot_w64(act && t > tag_mine);
-      const int stop = max(blocked ? __ffsll((long long)blocked) - 1 : nb, lo + 1);
-      if (ch && c2 == tag_mine) Qf[p] = lane < stop ? qn : q;
-      __builtin_amdgcn_wave_barrier();
-      return stop;
-    };
-    // (the first round on its own, in front of the loop over the rounds — most batches end with
-    //  it —, as in k_tab_pwg)
-    int first;
-    {
-      float q = 0.0f, qn = 0.0f;
-      if (on) {
-        q = Qf[p];
-        qn = td_of(q);
-      }
-      const bool ch = on && fbits(qn) != fbits(q);
-      if (!__builtin_amdgcn_ballot_w64(ch)) return;
-      first = tag_round(on, ch, q, qn, 0);
-    }
-    while (first < nb) {
-      const bool act = on && lane >= first;
-      float q = 0.0f, qn = 0.0f;
-      if (act) {
-        q = Qf[p];
-        qn = td_of(q);
-      }
-      const bool ch = act && fbits(qn) != fbits(q);
-      if (!__ballot(ch)) return;
-      first = tag_round(act, ch, q, qn, first);
-    }
+    });
   };
 
   // what depends only on the state being entered: lane k < W evaluates successor k
@@ -415,7 +330,7 @@ __global__ __launch_bounds__(512) void k_tab_wqn(const nact_args G) {
     //  ballot and Q[s][a] a readlane, where eight compares, fifteen scalar instructions and seven
     //  selects stood; as in k_tab_pwg / k_tab_wpi)
     const float qc = Qf[(uint32_t)state * WU + (uint32_t)(lane & (W - 1))];
-    smax = W == 8 ? max8(Qs[sn * 2u], Qs[sn * 2u + 1u]) : row_max(sn);
+    smax = cobel_row_max<W>(Q4 + sn * (WU / 4u));
     // ---- select --------------------------------------------------------------------------------------
     const int src_lane = 62 + (int)((cp >> 1) & 1u);
     const uint32_t w0 = rl((cp & 1u) ? blk.z : blk.x, src_lane);
@@ -503,15 +418,14 @@ __global__ __launch_bounds__(512) void k_tab_wqn(const nact_args G) {
       float td = r + gnt * ns_max;
       td = td - q_sa;
       const float qn = q_sa + alpha_f * td;
-      fresh_cur = W == 8 ? log_pack8(r, (uint32_t)state, (uint32_t)a, (uint32_t)ns, nt, nt_shift)
-                         : log_pack32(r, (uint32_t)state, (uint32_t)a, (uint32_t)ns, nt);
+      fresh_cur = cobel_log_pack(r, (uint32_t)state, (uint32_t)a, (uint32_t)ns, nt, A_log);
       appended = loglen < cap;      // (a full log takes no record)
       if (lane == 0) {
         Qf[p_sa] = qn;
         if (appended) rlog[loglen] = fresh_cur;
       }
       if (appended) loglen += 1u;
-      __builtin_amdgcn_wave_barrier();
+      wsync();
     }
     trew += (double)r;
     executed += 1ull;
@@ -579,7 +493,7 @@ __global__ __launch_bounds__(512) void k_tab_wqn(const nact_args G) {
   }
 
   // ---- write back ---------------------------------------------------------------------------------
-  __builtin_amdgcn_wave_barrier();
+  wsync();
   for (int e = lane; e < S * W; e += 64) {
     const int s = e / W, a = e % W;
     if (a < A) Qg[(size_t)s * A + a] = Qf[e];

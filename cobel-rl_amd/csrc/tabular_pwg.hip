@@ -79,24 +79,6 @@ struct pwg_args {
 #define NT_ST(v, p) (*(p) = (v))
 #endif
 
-__device__ __forceinline__ uint32_t rl(uint32_t v, int lane) {
-  return (uint32_t)__builtin_amdgcn_readlane((int)v, lane);
-}
-__device__ __forceinline__ uint32_t rfl(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
-}
-__device__ __forceinline__ float max4(const float4 v) {
-  float m;
-  asm("v_max_f32 %0, %1, %2\n\tv_max3_f32 %0, %0, %3, %4"
-      : "=&v"(m)
-      : "v"(v.x), "v"(v.y), "v"(v.z), "v"(v.w));
-  return m;
-}
-__device__ __forceinline__ uint32_t next_of(uint32_t w0, uint32_t w1, int a) {
-  const uint32_t w = (a & 2) ? w1 : w0;
-  return (a & 1) ? (w >> 16) : (w & 0xffffu);
-}
-__device__ __forceinline__ uint32_t fbits(float x) { return __builtin_bit_cast(uint32_t, x); }
 // this wave's earlier global stores are complete before anything after this point is issued
 __device__ __forceinline__ void stores_done() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
@@ -298,6 +280,9 @@ __device__ __forceinline__ void pwg_instance(const pwg_args& A, const int i, con
     return cnd;
   };
   // ---- one batch, Q in LDS (called under lane < B) -------------------------------------------
+  // (the scheme of cobel_tab_batch.h, kept written out here: inlined from that header, the same
+  //  code changes the register allocation of this step loop — a wait for the step-end prefetch of
+  //  the successor records appears, 10.9 -> 11.25 ms per C3 launch)
   // Which lanes must wait is found IN the table (round 6; until then two tables of lane masks per
   // wave, 1 KiB next to every Q table — the tenth table did not fit the CU's 160 KiB beside them):
   // a lane that changes its cell raises the cell to the TAG ~lane with ds_max_u32 — tags are the

@@ -245,3 +245,38 @@ def test_tables_full_of_tag_patterns_end_the_batch(side, flags_name):
     agent.train(env, 2, 30, 50)
     torch.cuda.synchronize()
     assert 0 < agent.env_steps() <= 96 * 60
+    kernel = agent.describe_launch(env, agent.policy, _lib.F_LEARN, 2, 30, 0, 50)['kernel']
+    if side == 32 and not flags_name:
+        assert kernel == _lib.TAB_KERNEL_PWG
+    else:
+        assert kernel in (_lib.TAB_KERNEL_WPI, _lib.TAB_KERNEL_WPI_FAST, _lib.TAB_KERNEL_WPI_INDEX)
+
+
+def test_tables_full_of_tag_patterns_end_the_replay_batch_of_six_actions():
+    """The same on k_tab_wqn (rows of eight, pad cells -inf): a QAgent's replay batch on a world of
+    six actions, its table full of tag patterns."""
+    from cobel_amd import _lib
+    from cobel_amd.agent import QAgent
+    from cobel_amd.interface import Topology
+    from cobel_amd.policy import EpsilonGreedy
+    r = np.random.default_rng(906)
+    S, A = 31, 6
+    nbr = r.integers(0, S, (S, A))
+    nbr = np.where(r.random((S, A)) < 0.15, np.arange(S)[:, None], nbr)
+    terminal = np.zeros(S, dtype=bool)
+    terminal[[5, 19]] = True
+    reward = np.zeros(S)
+    reward[5], reward[19], reward[12] = 1.0, -0.5, 0.25
+    nodes = {str(i): {'id': str(i), 'pose': np.array([float(i % 6), float(i // 6), 0., 0., 0., 0.]),
+                      'neighbors': [str(int(j)) for j in nbr[i]], 'reward': float(reward[i]),
+                      'terminal': bool(terminal[i])} for i in range(S)}
+    env = Topology(nodes, None, n_envs=96, seed=SEED)
+    agent = QAgent(env.observation_space, env.action_space, EpsilonGreedy(0.1))
+    agent._bind(env)
+    agent._q.view(torch.int32).fill_(-1)
+    agent._q.view(torch.int32)[:, ::3, :] = -64
+    agent.train(env, 2, 30, 50)
+    torch.cuda.synchronize()
+    assert 0 < agent.env_steps() <= 96 * 60
+    assert agent.describe_launch(env, agent.policy, _lib.F_LEARN, 2, 30, 0, 50)['kernel'] == \
+        _lib.TAB_KERNEL_WQN
