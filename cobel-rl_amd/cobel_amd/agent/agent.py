@@ -440,6 +440,9 @@ class FusedAgent(Agent):
 
     def _session(self, interface, trials: int, steps: int, batch: int, learn: bool,
                  extra_flags: int = 0, pol=None) -> None:
+        # (the reference's environments read their world at every step: an edit made since the last
+        #  call — or by a callback between two launches below — reaches the device tables here)
+        interface.sync_world()
         self._bind(interface)
         if pol is None:
             pol = self.policy if learn else self.policy_test
@@ -477,6 +480,7 @@ class FusedAgent(Agent):
                     while int(self.inst[0, _lib.I_TRIAL].item()) < target:
                         logs['step'] = step
                         logs = self.callbacks.on_step_begin(logs)
+                        interface.sync_world()
                         self._launch(interface, pol, flags, target, steps, 1, batch)
                         e = self._last_exp[0].cpu().numpy()
                         r = float(e[4:5].view(np.float32)[0])
@@ -489,6 +493,7 @@ class FusedAgent(Agent):
                         step += 1
                     logs['steps'] = step - 1
                 else:
+                    interface.sync_world()
                     self._launch(interface, pol, flags, target, steps, 0, batch)
                     lat = self.monitors.lat_sum[self.current_trial].item()
                     logs['steps'] = int(lat)

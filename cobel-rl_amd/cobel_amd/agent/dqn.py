@@ -358,6 +358,10 @@ class DQN(Agent):
         keys, trial hooks after every trial, and ``agent.stop`` ends the session at the next trial
         boundary.  Vectorised runs fire the trial hooks once per ``train()`` call with per-trial
         means (a device cannot call Python between steps of thousands of instances)."""
+        # (an edit of the world since the last call reaches the device tables before anything here
+        #  looks at the handle — handle.stochastic decides the loop, _fused_wire takes handle.ptr;
+        #  the Dyna agents hand over a view of the environment)
+        getattr(interface, 'env', interface).sync_world()
         single = interface.n_envs == 1 and not budget
         if single and self.callbacks.has('on_step_begin', 'on_step_end'):
             self._run_hooks(interface, trials, steps, batch_size, learn)

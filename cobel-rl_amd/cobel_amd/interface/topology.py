@@ -42,7 +42,6 @@ class Topology(Interface):
             'only pre-rendered observations (OfflineSimulator) are on the accelerated path'
         self.nodes = nodes
         self.ids = list(nodes.keys())
-        index = {k: i for i, k in enumerate(self.ids)}
         if starting_nodes is None:
             starting_nodes = [k for k, nd in nodes.items() if not nd['terminal']]
         self.starting_nodes = starting_nodes
@@ -54,12 +53,7 @@ class Topology(Interface):
             'every node needs the same number of neighbours (at most %d)' % _lib.MAX_ACTIONS
         S = len(self.ids)
         self.pose = np.array([nodes[k]['pose'] for k in self.ids], dtype=np.float64).reshape(S, 6)
-        world = dict(
-            states=S, next=np.array([[index[m] for m in nodes[k]['neighbors']] for k in self.ids],
-                                    dtype=np.uint16),
-            rewards=np.array([nodes[k]['reward'] for k in self.ids], dtype=np.float64),
-            terminals=np.array([bool(nodes[k]['terminal']) for k in self.ids]),
-            starting_states=np.array([index[k] for k in starting_nodes]), deterministic=True)
+        world = self._tables()
         self.world = world
         self.n_envs = int(n_envs)
         self.rng = rng
@@ -90,6 +84,49 @@ class Topology(Interface):
             self._compile_observations(simulator.observations)
         self._draw()   # the constructor's start-node draw
         self.observation = None
+
+    def _tables(self) -> dict:
+        """The node dictionary and ``starting_nodes`` as the compact tables a gridworld uses."""
+        nodes, index = self.nodes, {k: i for i, k in enumerate(self.ids)}
+        return dict(
+            states=len(self.ids),
+            next=np.array([[index[m] for m in nodes[k]['neighbors']] for k in self.ids],
+                          dtype=np.uint16),
+            rewards=np.array([nodes[k]['reward'] for k in self.ids], dtype=np.float64),
+            terminals=np.array([bool(nodes[k]['terminal']) for k in self.ids]),
+            starting_states=np.array([index[k] for k in self.starting_nodes]), deterministic=True)
+
+    # The reference's step() and reset() read self.nodes / self.starting_nodes themselves
+    # (topology.py:126-172): a node's reward, terminal flag or neighbours, or the start list, may be
+    # edited between two calls.  step(), reset() and every agent session begin with sync_world().
+    live_world = True   # set False to promise that the nodes are never edited: no comparison
+
+    def sync_world(self) -> bool:
+        """Rebuild the tables from ``nodes`` / ``starting_nodes``, compare them with what the
+        device holds and push what differs, in stream order.  Returns whether anything was
+        pushed.  The node set and the neighbour count are fixed (``ValueError``); poses and
+        pre-rendered observations stay as compiled at construction."""
+        # (a handle of several graphs installed from outside is its installer's to update: it does
+        #  not come from this node dictionary)
+        if not self.live_world or self.handle.n_worlds != 1:
+            return False
+        if list(self.nodes.keys()) != self.ids:
+            raise ValueError('the node set of a Topology is fixed at construction (%d nodes): the '
+                             'device tables are sized by it' % len(self.ids))
+        n_act = int(self.action_space.n)
+        if not all(len(nd['neighbors']) == n_act for nd in self.nodes.values()):
+            raise ValueError('every node keeps its %d neighbours: the action count is fixed at '
+                             'construction' % n_act)
+        try:
+            world = self._tables()
+        except KeyError as err:
+            raise ValueError('node %s is not part of this Topology' % err) from None
+        if len(world['starting_states']) == 0:
+            raise ValueError('starting_nodes is empty')
+        pushed = self.handle.update([world], self._stream())
+        if pushed:
+            self.world = world
+        return pushed
 
     def _compile_observations(self, observations: dict) -> None:
         """interface/simulator/offline.py:51-72 + topology.py:174-193: ``observations[pose]`` is an
@@ -132,6 +169,7 @@ class Topology(Interface):
         return _lib.current_stream(self.device)
 
     def _draw(self, mask=None) -> None:
+        self.sync_world()
         m = None
         if mask is not None:
             m = torch.as_tensor(mask, device=self.device).to(torch.uint8).contiguous()
@@ -191,6 +229,7 @@ class Topology(Interface):
             act = torch.full((1,), a, dtype=torch.uint8, device=self.device)
         else:
             act = torch.as_tensor(action, device=self.device).to(torch.uint8).contiguous()
+        self.sync_world()
         _lib.check(_lib.lib().cobel_env_step(
             self.handle.ptr, _lib.ptr(self.state), _lib.ptr(act), _lib.ptr(self._reward),
             _lib.ptr(self._done), self.n_envs, self.instance_base, self._stream()))

@@ -51,6 +51,9 @@ struct cobel_world {
   uint32_t* succ_off;   // [dev] [n_worlds * S * n_actions + 1]
   uint16_t* succ_state; // [dev] [nnz]
   double* succ_cdf;     // [dev] [nnz]
+  int64_t succ_cap;     // entries succ_state / succ_cdf have room for
+  // cobel_world_update*: pinned staging, outgrown buffers (world.hip); NULL until the first update
+  struct cobel_world_live* live;
 };
 
 // the successor Generator.choice(arange(S), p=row) returns for the uniform u (interface/

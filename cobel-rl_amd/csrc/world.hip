@@ -8,6 +8,7 @@
 #include <string.h>
 
 #include <mutex>
+#include <new>
 #include <vector>
 
 #include "cobel_common.h"
@@ -182,6 +183,33 @@ extern "C" int cobel_pairwise_order(int32_t n, const int32_t* pos, int32_t k, ui
 }
 
 // ---------------------------------------------------------------------------------------------
+// Rewarded states of every world and their pairwise combine order (cobel_rw_info; `rw` may be NULL:
+// worlds of other action counts keep none); returns the largest count of rewarded states.
+static int32_t rewarded_info(const float* reward, int32_t n_states, int32_t n_worlds,
+                             cobel_rw_info* rw) {
+  int32_t most = 0;
+  for (int k = 0; k < n_worlds; ++k) {
+    int32_t rewarded = 0;
+    int pos[32];
+    for (int32_t s = 0; s < n_states; ++s)
+      if (reward[(size_t)k * n_states + s] != 0.0f) {
+        if (rewarded < 32) pos[rewarded] = s;
+        rewarded += 1;
+      }
+    if (rewarded > most) most = rewarded;
+    if (!rw) continue;
+    cobel_rw_info& info = rw[(size_t)k];
+    memset(&info, 0, sizeof(info));
+    info.k = rewarded <= 32 ? (uint8_t)rewarded : (uint8_t)255;
+    if (rewarded <= 32) {
+      for (int j = 0; j < rewarded; ++j) info.pos[j] = (uint16_t)pos[j];
+      const int root = cobel_pairwise_schedule(n_states, pos, rewarded, info.dst, info.src);
+      info.root = (uint8_t)(root < 0 ? 0 : root);
+    }
+  }
+  return most;
+}
+
 extern "C" int cobel_world_create(const uint16_t* next, const float* reward,
                                   const uint8_t* terminal, const uint16_t* starts,
                                   const int32_t* start_offsets, int32_t n_states,
@@ -220,24 +248,7 @@ extern "C" int cobel_world_create(const uint16_t* next, const float* reward,
   w->device = device;
   w->n_actions = 4;
   std::vector<cobel_rw_info> rw((size_t)n_worlds);
-  for (int k = 0; k < n_worlds; ++k) {
-    int32_t rewarded = 0;
-    int pos[32];
-    for (int32_t s = 0; s < n_states; ++s)
-      if (reward[(size_t)k * n_states + s] != 0.0f) {
-        if (rewarded < 32) pos[rewarded] = s;
-        rewarded += 1;
-      }
-    if (rewarded > w->max_rewarded_states) w->max_rewarded_states = rewarded;
-    cobel_rw_info& info = rw[(size_t)k];
-    memset(&info, 0, sizeof(info));
-    info.k = rewarded <= 32 ? (uint8_t)rewarded : (uint8_t)255;
-    if (rewarded <= 32) {
-      for (int j = 0; j < rewarded; ++j) info.pos[j] = (uint16_t)pos[j];
-      const int root = cobel_pairwise_schedule(n_states, pos, rewarded, info.dst, info.src);
-      info.root = (uint8_t)(root < 0 ? 0 : root);
-    }
-  }
+  w->max_rewarded_states = rewarded_info(reward, n_states, n_worlds, rw.data());
   w->h_start_off = (int32_t*)malloc(sizeof(int32_t) * (n_worlds + 1));
   memcpy(w->h_start_off, start_offsets, sizeof(int32_t) * (n_worlds + 1));
   hipError_t e = hipMalloc((void**)&w->rec, total * sizeof(cobel_wrec));
@@ -262,6 +273,24 @@ extern "C" int cobel_world_create(const uint16_t* next, const float* reward,
   return COBEL_OK;
 }
 
+// What cobel_world_update / cobel_world_update_transitions keep beside the handle.  Nothing here is
+// freed before cobel_world_destroy: a launch already enqueued may still read a buffer an update
+// outgrew, or a staging area.
+struct cobel_world_live {
+  struct slot {
+    char* host;        // pinned, read by the pack kernel itself
+    size_t bytes;
+    hipEvent_t done;   // recorded behind the kernel that reads `host`
+  };
+  std::vector<slot> slots;
+  std::vector<void*> retired;   // device buffers an update outgrew
+  int32_t starts_cap;           // entries `starts` has room for
+  // distribution rows put aside by cobel_world_update_transitions(NULL), reused by the next lists
+  uint32_t* spare_off;
+  uint16_t* spare_state;
+  double* spare_cdf;
+};
+
 extern "C" int cobel_world_destroy(cobel_world_t* w) {
   if (!w) return COBEL_OK;
   if (w->rec) (void)hipFree(w->rec);
@@ -275,8 +304,46 @@ extern "C" int cobel_world_destroy(cobel_world_t* w) {
   if (w->succ_off) (void)hipFree(w->succ_off);
   if (w->succ_state) (void)hipFree(w->succ_state);
   if (w->succ_cdf) (void)hipFree(w->succ_cdf);
+  if (cobel_world_live* const l = w->live) {
+    for (void* p : l->retired) (void)hipFree(p);
+    if (l->spare_off) (void)hipFree(l->spare_off);
+    if (l->spare_state) (void)hipFree(l->spare_state);
+    if (l->spare_cdf) (void)hipFree(l->spare_cdf);
+    for (const cobel_world_live::slot& sl : l->slots) {
+      (void)hipEventDestroy(sl.done);
+      (void)hipHostFree(sl.host);
+    }
+    delete l;
+  }
   free(w->h_start_off);
   free(w);
+  return COBEL_OK;
+}
+
+// the checks of the list form of distribution rows (cobel_world_set_transitions and its live twin)
+static int check_transitions(const cobel_world* w, const char* who, const uint32_t* succ_off,
+                             const uint16_t* succ_state, const double* succ_cdf, int64_t nnz) {
+  COBEL_REQUIRE(succ_off && succ_state && succ_cdf, COBEL_E_ARG, "%s: NULL table", who);
+  const size_t pairs = (size_t)w->n_worlds * w->n_states * w->n_actions;
+  COBEL_REQUIRE(nnz >= (int64_t)pairs && nnz < ((int64_t)1 << 32), COBEL_E_RANGE,
+                "%s: %lld successors for %zu pairs", who, (long long)nnz, pairs);
+  COBEL_REQUIRE(succ_off[0] == 0 && succ_off[pairs] == (uint32_t)nnz, COBEL_E_ARG,
+                "%s: offsets do not span the lists", who);
+  for (size_t p = 0; p < pairs; ++p) {
+    const uint32_t lo = succ_off[p], hi = succ_off[p + 1];
+    COBEL_REQUIRE(hi > lo && hi <= (uint32_t)nnz, COBEL_E_ARG, "%s: pair %zu has no successor", who,
+                  p);
+    double prev = 0.0;
+    for (uint32_t k = lo; k < hi; ++k) {
+      COBEL_REQUIRE((int)succ_state[k] < w->n_states, COBEL_E_RANGE,
+                    "%s: successor %u outside the world", who, succ_state[k]);
+      COBEL_REQUIRE(succ_cdf[k] > prev && succ_cdf[k] <= 1.0, COBEL_E_ARG,
+                    "%s: pair %zu: cumulative probabilities must increase to 1", who, p);
+      prev = succ_cdf[k];
+    }
+    COBEL_REQUIRE(prev == 1.0, COBEL_E_ARG,
+                  "%s: pair %zu: the last cumulative probability is %g, not 1", who, p, prev);
+  }
   return COBEL_OK;
 }
 
@@ -287,28 +354,10 @@ extern "C" int cobel_world_set_transitions(cobel_world_t* w, const uint32_t* suc
   COBEL_REQUIRE(succ_off && succ_state && succ_cdf, COBEL_E_ARG,
                 "cobel_world_set_transitions: NULL table");
   COBEL_REQUIRE(!w->succ_off, COBEL_E_ARG, "cobel_world_set_transitions: already set");
+  if (int rc = check_transitions(w, "cobel_world_set_transitions", succ_off, succ_state, succ_cdf,
+                                 nnz))
+    return rc;
   const size_t pairs = (size_t)w->n_worlds * w->n_states * w->n_actions;
-  COBEL_REQUIRE(nnz >= (int64_t)pairs && nnz < ((int64_t)1 << 32), COBEL_E_RANGE,
-                "cobel_world_set_transitions: %lld successors for %zu pairs", (long long)nnz, pairs);
-  COBEL_REQUIRE(succ_off[0] == 0 && succ_off[pairs] == (uint32_t)nnz, COBEL_E_ARG,
-                "cobel_world_set_transitions: offsets do not span the lists");
-  for (size_t p = 0; p < pairs; ++p) {
-    const uint32_t lo = succ_off[p], hi = succ_off[p + 1];
-    COBEL_REQUIRE(hi > lo && hi <= (uint32_t)nnz, COBEL_E_ARG,
-                  "cobel_world_set_transitions: pair %zu has no successor", p);
-    double prev = 0.0;
-    for (uint32_t k = lo; k < hi; ++k) {
-      COBEL_REQUIRE((int)succ_state[k] < w->n_states, COBEL_E_RANGE,
-                    "cobel_world_set_transitions: successor %u outside the world", succ_state[k]);
-      COBEL_REQUIRE(succ_cdf[k] > prev && succ_cdf[k] <= 1.0, COBEL_E_ARG,
-                    "cobel_world_set_transitions: pair %zu: cumulative probabilities must increase "
-                    "to 1", p);
-      prev = succ_cdf[k];
-    }
-    COBEL_REQUIRE(prev == 1.0, COBEL_E_ARG,
-                  "cobel_world_set_transitions: pair %zu: the last cumulative probability is %g, not 1",
-                  p, prev);
-  }
   hipError_t e = hipMalloc((void**)&w->succ_off, (pairs + 1) * sizeof(uint32_t));
   if (e == hipSuccess) e = hipMalloc((void**)&w->succ_state, (size_t)nnz * sizeof(uint16_t));
   if (e == hipSuccess) e = hipMalloc((void**)&w->succ_cdf, (size_t)nnz * sizeof(double));
@@ -327,6 +376,7 @@ extern "C" int cobel_world_set_transitions(cobel_world_t* w, const uint32_t* suc
     w->succ_cdf = nullptr;
     return cobel_fail(COBEL_E_HIP, "cobel_world_set_transitions: %s", hipGetErrorString(e));
   }
+  w->succ_cap = nnz;
   return COBEL_OK;
 }
 
@@ -336,6 +386,286 @@ extern "C" int cobel_world_info(const cobel_world_t* w, int32_t* n_states, int32
   if (n_states) *n_states = w->n_states;
   if (n_worlds) *n_worlds = w->n_worlds;
   if (device) *device = w->device;
+  return COBEL_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Live worlds.  The reference reads world['sas'] / ['rewards'] / ['terminals'] /
+// ['starting_states'] on every step and reset (interface/gridworld.py:115-126, :142; interface/
+// topology.py:126-172 reads the node dictionary the same way), so its users edit a world between two
+// training runs: reversal, detour and latent-learning protocols.  Here the tables are resident, and
+// an edit is a rewrite of them IN STREAM ORDER: the new arrays are staged in pinned memory of the
+// handle's own and one small kernel, enqueued like any launch, packs them into the tables every
+// kernel already points at.  Launches enqueued before it read the old world, launches after it the
+// new one, and the host never waits.
+namespace {
+
+struct pack_args {
+  // staged (pinned host memory, every segment 16-byte aligned)
+  const uint16_t* next;      // [total][A]
+  const float* reward;       // [total]
+  const uint8_t* terminal;   // [total] 0 / 1
+  const uint16_t* starts;    // [n_starts]
+  const int32_t* start_off;  // [n_off]
+  const uint4* rw;           // [n_rw16] cobel_rw_info as 16-byte pieces (four-action worlds)
+  // resident
+  uint4* rec;                // cobel_wrec [total], or NULL and the three below
+  uint16_t* next_n;
+  float* reward_s;
+  uint8_t* terminal_s;
+  uint16_t* d_starts;
+  int32_t* d_start_off;
+  uint4* d_rw;
+  int32_t total, A, n_starts, n_off, n_rw16;
+};
+
+// One lane per state: a cobel_wrec leaves as one 16-byte store, so a kernel of another stream that
+// (against the rule of the header) reads meanwhile sees whole records.  The short lists ride along
+// on the first lanes.
+__global__ __launch_bounds__(256) void k_world_pack(const pack_args P) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i < P.total) {
+    if (P.rec) {
+      const uint2 nx = reinterpret_cast<const uint2*>(P.next)[i];   // next[0..3], as cobel_wrec holds them
+      P.rec[i] = make_uint4(nx.x, nx.y, __builtin_bit_cast(uint32_t, P.reward[i]),
+                            (uint32_t)P.terminal[i]);
+    } else {
+      for (int a = 0; a < P.A; ++a) P.next_n[(size_t)i * P.A + a] = P.next[(size_t)i * P.A + a];
+      P.reward_s[i] = P.reward[i];
+      P.terminal_s[i] = P.terminal[i];
+    }
+  }
+  if (i < P.n_starts) P.d_starts[i] = P.starts[i];
+  if (i < P.n_off) P.d_start_off[i] = P.start_off[i];
+  if (i < P.n_rw16) P.d_rw[i] = P.rw[i];
+}
+
+__global__ __launch_bounds__(256) void k_world_lists(const uint32_t* __restrict__ off,
+                                                     const uint16_t* __restrict__ state,
+                                                     const double* __restrict__ cdf,
+                                                     uint32_t* __restrict__ d_off,
+                                                     uint16_t* __restrict__ d_state,
+                                                     double* __restrict__ d_cdf, size_t n_off,
+                                                     size_t nnz) {
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_off || i < nnz; i += stride) {
+    if (i < n_off) d_off[i] = off[i];
+    if (i < nnz) {
+      d_state[i] = state[i];
+      d_cdf[i] = cdf[i];
+    }
+  }
+}
+
+size_t align16(size_t b) { return (b + 15u) & ~(size_t)15u; }
+
+int world_live(cobel_world* w) {
+  if (w->live) return COBEL_OK;
+  cobel_world_live* const l = new (std::nothrow) cobel_world_live();
+  COBEL_REQUIRE(l, COBEL_E_ARG, "cobel_world_update: out of host memory");
+  l->starts_cap = w->h_start_off[w->n_worlds];
+  w->live = l;
+  return COBEL_OK;
+}
+
+// A staging area nobody reads any more: one whose kernel has finished (asked without waiting), else
+// a new one.  The caller records `done` behind the kernel it launches.
+int stage_slot(cobel_world_live* l, size_t bytes, cobel_world_live::slot** out) {
+  for (cobel_world_live::slot& sl : l->slots)
+    if (sl.bytes >= bytes && hipEventQuery(sl.done) == hipSuccess) {
+      *out = &sl;
+      return COBEL_OK;
+    }
+  (void)hipGetLastError();   // (hipErrorNotReady of a query is no failure)
+  cobel_world_live::slot sl{nullptr, bytes, nullptr};
+  COBEL_HIP_TRY(hipHostMalloc((void**)&sl.host, bytes, hipHostMallocDefault));
+  const hipError_t e = hipEventCreateWithFlags(&sl.done, hipEventDisableTiming);
+  if (e != hipSuccess) {
+    (void)hipHostFree(sl.host);
+    return cobel_fail(COBEL_E_HIP, "cobel_world_update: %s", hipGetErrorString(e));
+  }
+  l->slots.push_back(sl);
+  *out = &l->slots.back();
+  return COBEL_OK;
+}
+
+}  // namespace
+
+extern "C" int cobel_world_update(cobel_world_t* w, const uint16_t* next, const float* reward,
+                                  const uint8_t* terminal, const uint16_t* starts,
+                                  const int32_t* start_offsets, void* stream) {
+  if (int rc = cobel_world_check(w, "cobel_world_update")) return rc;
+  // every check of cobel_world_create / cobel_world_create_n, before the handle is touched
+  COBEL_REQUIRE(next && reward && terminal && starts && start_offsets, COBEL_E_ARG,
+                "cobel_world_update: NULL argument");
+  const int32_t S = w->n_states, W = w->n_worlds, A = w->n_actions;
+  COBEL_REQUIRE(start_offsets[0] == 0, COBEL_E_ARG, "cobel_world_update: start_offsets[0] != 0");
+  for (int k = 0; k < W; ++k)
+    COBEL_REQUIRE(start_offsets[k + 1] > start_offsets[k], COBEL_E_ARG,
+                  "cobel_world_update: world %d has no starting state", k);
+  const size_t total = (size_t)W * (size_t)S;
+  for (size_t k = 0; k < total * (size_t)A; ++k)
+    COBEL_REQUIRE(next[k] < S, COBEL_E_RANGE, "cobel_world_update: next[%zu][%zu] = %u >= n_states",
+                  k / A, k % A, (unsigned)next[k]);
+  const int32_t n_starts = start_offsets[W];
+  for (int32_t k = 0; k < n_starts; ++k)
+    COBEL_REQUIRE(starts[k] < S, COBEL_E_RANGE, "cobel_world_update: start %u >= n_states",
+                  (unsigned)starts[k]);
+
+  if (int rc = world_live(w)) return rc;
+  cobel_world_live* const l = w->live;
+  const size_t o_next = 0, o_reward = o_next + align16(total * A * sizeof(uint16_t)),
+               o_terminal = o_reward + align16(total * sizeof(float)),
+               o_starts = o_terminal + align16(total),
+               o_off = o_starts + align16((size_t)n_starts * sizeof(uint16_t)),
+               o_rw = o_off + align16((size_t)(W + 1) * sizeof(int32_t)),
+               bytes = o_rw + (w->rw ? (size_t)W * sizeof(cobel_rw_info) : 0);
+  cobel_world_live::slot* sl = nullptr;
+  if (int rc = stage_slot(l, bytes, &sl)) return rc;
+  // the start list may have grown: a larger buffer, the old one stays for launches in flight
+  uint16_t* d_starts = w->starts;
+  int32_t cap = l->starts_cap;
+  if (n_starts > cap) {
+    cap = n_starts > 2 * cap ? n_starts : 2 * cap;
+    l->retired.reserve(l->retired.size() + 1);
+    COBEL_HIP_TRY(hipMalloc((void**)&d_starts, sizeof(uint16_t) * (size_t)cap));
+  }
+
+  memcpy(sl->host + o_next, next, total * A * sizeof(uint16_t));
+  memcpy(sl->host + o_reward, reward, total * sizeof(float));
+  for (size_t k = 0; k < total; ++k) sl->host[o_terminal + k] = terminal[k] ? 1 : 0;
+  memcpy(sl->host + o_starts, starts, (size_t)n_starts * sizeof(uint16_t));
+  memcpy(sl->host + o_off, start_offsets, (size_t)(W + 1) * sizeof(int32_t));
+  const int32_t most = rewarded_info(
+      reward, S, W, w->rw ? reinterpret_cast<cobel_rw_info*>(sl->host + o_rw) : nullptr);
+
+  pack_args P;
+  P.next = reinterpret_cast<const uint16_t*>(sl->host + o_next);
+  P.reward = reinterpret_cast<const float*>(sl->host + o_reward);
+  P.terminal = reinterpret_cast<const uint8_t*>(sl->host + o_terminal);
+  P.starts = reinterpret_cast<const uint16_t*>(sl->host + o_starts);
+  P.start_off = reinterpret_cast<const int32_t*>(sl->host + o_off);
+  P.rw = reinterpret_cast<const uint4*>(sl->host + o_rw);
+  P.rec = reinterpret_cast<uint4*>(w->rec);
+  P.next_n = w->next_n;
+  P.reward_s = w->reward_s;
+  P.terminal_s = w->terminal_s;
+  P.d_starts = d_starts;
+  P.d_start_off = w->start_off;
+  P.d_rw = reinterpret_cast<uint4*>(w->rw);
+  P.total = (int32_t)total;
+  P.A = A;
+  P.n_starts = n_starts;
+  P.n_off = W + 1;
+  P.n_rw16 = w->rw ? W * (int32_t)(sizeof(cobel_rw_info) / 16) : 0;
+  int32_t lanes = P.total;
+  if (P.n_starts > lanes) lanes = P.n_starts;
+  if (P.n_off > lanes) lanes = P.n_off;
+  if (P.n_rw16 > lanes) lanes = P.n_rw16;
+  hipLaunchKernelGGL(k_world_pack, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0,
+                     (hipStream_t)stream, P);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipEventRecord(sl->done, (hipStream_t)stream);
+  if (e != hipSuccess) {
+    if (d_starts != w->starts) l->retired.push_back(d_starts);
+    return cobel_fail(COBEL_E_HIP, "cobel_world_update: %s", hipGetErrorString(e));
+  }
+  // host-side fields: from this call on
+  if (d_starts != w->starts) {
+    l->retired.push_back(w->starts);
+    w->starts = d_starts;
+    l->starts_cap = cap;
+  }
+  memcpy(w->h_start_off, start_offsets, sizeof(int32_t) * (size_t)(W + 1));
+  w->max_rewarded_states = most;
+  return COBEL_OK;
+}
+
+extern "C" int cobel_world_update_transitions(cobel_world_t* w, const uint32_t* succ_off,
+                                              const uint16_t* succ_state, const double* succ_cdf,
+                                              int64_t nnz, void* stream) {
+  const char* const who = "cobel_world_update_transitions";
+  if (int rc = cobel_world_check(w, who)) return rc;
+  if (!succ_off) {   // back to plain table rows; the lists wait for the next distributions
+    if (!w->succ_off) return COBEL_OK;
+    if (int rc = world_live(w)) return rc;
+    cobel_world_live* const l = w->live;
+    l->retired.reserve(l->retired.size() + 3);
+    if (l->spare_off) {
+      l->retired.push_back(l->spare_off);
+      l->retired.push_back(l->spare_state);
+      l->retired.push_back(l->spare_cdf);
+    }
+    l->spare_off = w->succ_off;
+    l->spare_state = w->succ_state;
+    l->spare_cdf = w->succ_cdf;
+    w->succ_off = nullptr;
+    w->succ_state = nullptr;
+    w->succ_cdf = nullptr;
+    return COBEL_OK;
+  }
+  if (int rc = check_transitions(w, who, succ_off, succ_state, succ_cdf, nnz)) return rc;
+  if (int rc = world_live(w)) return rc;
+  cobel_world_live* const l = w->live;
+  const size_t pairs = (size_t)w->n_worlds * w->n_states * w->n_actions;
+  const size_t o_cdf = 0, o_off = o_cdf + align16((size_t)nnz * sizeof(double)),
+               o_state = o_off + align16((pairs + 1) * sizeof(uint32_t)),
+               bytes = o_state + align16((size_t)nnz * sizeof(uint16_t));
+  cobel_world_live::slot* sl = nullptr;
+  if (int rc = stage_slot(l, bytes, &sl)) return rc;
+  // resident lists: the handle's, else the ones put aside; larger ones where these are too short
+  const bool from_spare = !w->succ_off && l->spare_off;
+  uint32_t* d_off = w->succ_off ? w->succ_off : l->spare_off;
+  uint16_t* d_state = w->succ_off ? w->succ_state : l->spare_state;
+  double* d_cdf = w->succ_off ? w->succ_cdf : l->spare_cdf;
+  int64_t cap = d_off ? w->succ_cap : 0;
+  uint32_t* new_off = nullptr;
+  uint16_t* new_state = nullptr;
+  double* new_cdf = nullptr;
+  l->retired.reserve(l->retired.size() + 3);
+  if (nnz > cap) {
+    cap = d_off ? nnz + nnz / 2 : nnz;
+    hipError_t e = hipSuccess;
+    if (!d_off) e = hipMalloc((void**)&new_off, (pairs + 1) * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc((void**)&new_state, (size_t)cap * sizeof(uint16_t));
+    if (e == hipSuccess) e = hipMalloc((void**)&new_cdf, (size_t)cap * sizeof(double));
+    if (e != hipSuccess) {
+      if (new_off) l->retired.push_back(new_off);
+      if (new_state) l->retired.push_back(new_state);
+      return cobel_fail(COBEL_E_HIP, "%s: %s", who, hipGetErrorString(e));
+    }
+  }
+  memcpy(sl->host + o_cdf, succ_cdf, (size_t)nnz * sizeof(double));
+  memcpy(sl->host + o_off, succ_off, (pairs + 1) * sizeof(uint32_t));
+  memcpy(sl->host + o_state, succ_state, (size_t)nnz * sizeof(uint16_t));
+  const size_t most = (size_t)nnz > pairs + 1 ? (size_t)nnz : pairs + 1;
+  const unsigned blocks = (unsigned)((most + 255) / 256 < 4096 ? (most + 255) / 256 : 4096);
+  hipLaunchKernelGGL(k_world_lists, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
+                     reinterpret_cast<const uint32_t*>(sl->host + o_off),
+                     reinterpret_cast<const uint16_t*>(sl->host + o_state),
+                     reinterpret_cast<const double*>(sl->host + o_cdf), new_off ? new_off : d_off,
+                     new_state ? new_state : d_state, new_cdf ? new_cdf : d_cdf, pairs + 1,
+                     (size_t)nnz);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipEventRecord(sl->done, (hipStream_t)stream);
+  if (e != hipSuccess) {
+    if (new_off) l->retired.push_back(new_off);
+    if (new_state) l->retired.push_back(new_state);
+    if (new_cdf) l->retired.push_back(new_cdf);
+    return cobel_fail(COBEL_E_HIP, "%s: %s", who, hipGetErrorString(e));
+  }
+  if (new_state) {   // outgrown lists stay for launches in flight
+    if (d_state) l->retired.push_back(d_state);
+    if (d_cdf) l->retired.push_back(d_cdf);
+    d_state = new_state;
+    d_cdf = new_cdf;
+  }
+  if (new_off) d_off = new_off;
+  if (from_spare) l->spare_off = nullptr, l->spare_state = nullptr, l->spare_cdf = nullptr;
+  w->succ_off = d_off;
+  w->succ_state = d_state;
+  w->succ_cdf = d_cdf;
+  w->succ_cap = cap;
   return COBEL_OK;
 }
 

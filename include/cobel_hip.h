@@ -16,9 +16,9 @@
  *   - kernels are enqueued on `stream` (a hipStream_t passed as void*; NULL = the
  *     default stream) and calls return without synchronising;
  *   - the library keeps no global mutable state besides the last-error string; a
- *     world handle is immutable after creation (cobel_world_create*, then at most one
- *     cobel_world_set_transitions before its first use) and may be shared by any number
- *     of runs on its device.
+ *     world handle changes only through cobel_world_set_transitions (once, before its first
+ *     use) and cobel_world_update / cobel_world_update_transitions (in stream order, see
+ *     there) and may be shared by any number of runs on its device.
  */
 #ifndef COBEL_HIP_H
 #define COBEL_HIP_H
@@ -140,6 +140,44 @@ COBEL_API int cobel_world_set_transitions(cobel_world_t* world,
                        const uint32_t* succ_off /* [host] [n_worlds * S * n_actions + 1] */,
                        const uint16_t* succ_state /* [host] [nnz] */,
                        const double* succ_cdf /* [host] [nnz] */, int64_t nnz);
+
+/* Live worlds.  The reference reads world['sas'] / ['rewards'] / ['terminals'] /
+ * ['starting_states'] anew on every step and reset (interface/gridworld.py:115-126, :142;
+ * interface/topology.py:126-172 reads the node dictionary), so a caller may move a reward, a
+ * start box or a wall between two runs.  cobel_world_update rewrites the tables of a handle IN
+ * STREAM ORDER: arrays as cobel_world_create_n takes them, for the handle's own n_states /
+ * n_worlds / n_actions (those never change).  Everything cobel_world_create* checks is checked
+ * first; a refused update (COBEL_E_ARG, COBEL_E_RANGE) leaves the handle exactly as it was.  Every
+ * derived field follows: the packed records (or next / reward / terminal tables), the start lists
+ * (which may change length), the rewarded states and their pairwise order, and their largest
+ * count, by which cobel_sr_run picks its kernel form.
+ *   - launches enqueued on `stream` BEFORE the call see the old world, launches enqueued AFTER it
+ *     the new one; the call enqueues one small kernel and returns, it never waits for the device;
+ *   - the caller's arrays are free again on return (they are staged in pinned memory of the
+ *     handle's own); buffers an update outgrows are kept until cobel_world_destroy.  A staging
+ *     area is reused once the kernel that reads it has finished (asked, never waited for); an
+ *     update made while every area is still in flight allocates another one (the size of the
+ *     tables, about 1 MB for 64 worlds of 1 024 states), all held until cobel_world_destroy: a
+ *     caller that issues many updates without letting the stream progress pays that memory.  The
+ *     first update of a handle also pays the allocation of its staging area and one event;
+ *   - the host-side fields (start-list length, rewarded-state count, whether rows are
+ *     distributions) take effect at call time: while an update is made the handle must not be in
+ *     use on ANOTHER stream, and launches on other streams must be ordered behind `stream` by the
+ *     caller to see the new world.
+ * cobel_world_update_transitions replaces the distribution rows the same way, with the checks of
+ * cobel_world_set_transitions; succ_off == NULL returns to plain table rows (the table of
+ * cobel_world_create / cobel_world_update: update it as well when the most likely successors
+ * changed).  cobel_world_set_transitions keeps its meaning, refusal of a second call included. */
+COBEL_API int cobel_world_update(cobel_world_t* world,
+                       const uint16_t* next /* [host] [n_worlds][S][n_actions] */,
+                       const float* reward /* [host] [n_worlds][S] */,
+                       const uint8_t* terminal /* [host] [n_worlds][S] */,
+                       const uint16_t* starts /* [host] concatenated start lists */,
+                       const int32_t* start_offsets /* [host] [n_worlds + 1] */, void* stream);
+COBEL_API int cobel_world_update_transitions(cobel_world_t* world,
+                       const uint32_t* succ_off /* [host] [n_worlds * S * n_actions + 1], or NULL */,
+                       const uint16_t* succ_state /* [host] [nnz] */,
+                       const double* succ_cdf /* [host] [nnz] */, int64_t nnz, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Stand-alone vectorised environment.  Replaces Gridworld.step / Gridworld.reset
