@@ -4,8 +4,8 @@ Same constructor, ``train(interface, trials, steps, batch_size=32, no_replay=Fal
 ``test``, ``predict_on_batch`` and attributes (``Q``, ``M``, ``learning_rate``, ``gamma``,
 ``action_mask``, ``mask_actions``, ``episodic_replay``, ``current_trial``, ``stop``).  Tables are
 float32; see include/cobel_hip.h for the exact arithmetic (bit-exact against the reference run
-with float32 tables).  Up to 62 planning updates per step one wavefront plans a batch; larger
-``batch_size`` values (the reference has no limit) run on the general kernel of ``cobel_tab_run``.
+with float32 tables).  Up to 62 planning updates per step one wavefront plans a batch in one pass;
+larger ``batch_size`` values (the reference has no limit) run as several passes of the same kernels.
 """
 from __future__ import annotations
 

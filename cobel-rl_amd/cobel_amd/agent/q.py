@@ -103,7 +103,7 @@ class QAgent(TabularAgent):
         run.log_cap = self._log_cap if keep else 0
 
     def train(self, interface, trials: int, steps: int = 32, batch_size: int = 32) -> None:
-        assert batch_size >= 0     # (above _lib.MAX_BATCH: the general kernel, any size)
+        assert batch_size >= 0     # (above _lib.MAX_BATCH: passes of the wavefront kernels, any size)
         self._bind(interface)
         used = int(self.inst[:, _lib.I_LOG_LEN].max().item())
         need = (used + trials * steps) * 8 * self._log_words() * self.n_envs

@@ -68,21 +68,51 @@ __device__ __forceinline__ int cobel_draw_successor(const uint32_t* __restrict__
   return (int)succ[k];
 }
 
+// What the routing of a tabular run decides (tab_plan, tabular.hip): which kernel serves it, the
+// three numbers cobel_tab_describe reports beside it, and the choices the launchers would otherwise
+// work out again.  Filled once per call; the launchers take it as it is.
+struct cobel_tab_plan {
+  int32_t kind;          // COBEL_TAB_KERNEL_*; 0 with inst_per_wg == 0: nothing to launch (n == 0)
+  size_t lds;            // dynamic LDS per workgroup, lds_pad included
+  int32_t wg_per_cu;     // workgroups per CU by LDS (lds_workgroups_per_cu; 1 for PWG, 0 for general)
+  int32_t inst_per_wg;   // instances per workgroup
+  bool replay;           // the run replays: learning, batch > 0, a model or an experience log
+  bool occ, wlds;        // wavefront forms: visit counters / the world's records in LDS
+  bool fast, midx;       // ... plain Dyna-Q training / with the model digest in HBM
+  size_t lds_pad;        // ... COBEL_DEBUG_LDS_PAD (occupancy experiments)
+  int lpw;               // lane per instance: instances per wave (64, 32 or 16)
+  int nl, ng;            // PWG: waves with Q in LDS / in global memory
+  int wpg;               // WQN: waves (= instances) per workgroup
+  int lpb;               // general: lanes per workgroup
+};
+
+// LDS is handed out in blocks of 1 280 bytes, 128 per CU — not in KiB (measured on MI355X with
+// scripts/experiments/exp_occupancy.py: the launch time of k_tab_wpi steps down at 15 360 and at 14 080 bytes
+// per workgroup and is flat in between; 16 384 B, a 32 x 32 world, are 13 blocks: nine per CU —
+// k_tab_pwg's ONE workgroup per CU takes all 128 blocks for ten).
+inline int lds_workgroups_per_cu(size_t bytes) {
+  const size_t blocks = (bytes + 1279) / 1280;
+  return blocks ? (int)(128 / blocks) : 128;
+}
+
+// The kernel files of the tabular agents.  Each `..._plan` knows the limits of its own kernel: it
+// returns false where the kernel does not serve the run, else fills its part of the plan.  The
+// arguments have passed tab_plan's checks.  Each `..._launch` takes the plan and launches.
 // general.hip: any action count / batch size / state count (one lane per instance)
 int cobel_env_step_general(const cobel_world* world, int32_t* state, const uint8_t* action,
                            float* reward_out, uint8_t* done_out, uint32_t* env_ctr, uint64_t seed,
                            int32_t n, uint32_t instance_base, hipStream_t st);
-int cobel_tab_general_launch(const cobel_world* world, const cobel_tab_run_t& r, hipStream_t st);
-
-// tabular_pwg.hip: plain Dyna-Q training as one persistent workgroup per CU (Q in LDS + Q in L2)
-bool cobel_tab_pwg_plan(const cobel_world* world, const cobel_tab_run_t& r, int* nl, int* ng,
-                        size_t* lds_bytes);
-int cobel_tab_pwg_launch(const cobel_world* world, const cobel_tab_run_t& r, hipStream_t st);
-
+void cobel_tab_general_plan(const cobel_tab_run_t& r, cobel_tab_plan& plan);   // (takes every run)
+int cobel_tab_general_launch(const cobel_world* world, const cobel_tab_run_t& r,
+                             const cobel_tab_plan& plan, hipStream_t st);
+// tabular_pwg.hip: plain Dyna-Q training as one persistent workgroup per CU
+bool cobel_tab_pwg_plan(const cobel_world* world, const cobel_tab_run_t& r, cobel_tab_plan& plan);
+int cobel_tab_pwg_launch(const cobel_world* world, const cobel_tab_run_t& r,
+                         const cobel_tab_plan& plan, hipStream_t st);
 // tabular_nact.hip: Q-learning on worlds of 1..32 (not four) actions, one wavefront per instance
-bool cobel_tab_nact_covers(const cobel_world* world, const cobel_tab_run_t& r, size_t* lds_bytes,
-                           int* instances_per_workgroup);
-int cobel_tab_nact_launch(const cobel_world* world, const cobel_tab_run_t& r, hipStream_t st);
+bool cobel_tab_nact_plan(const cobel_world* world, const cobel_tab_run_t& r, cobel_tab_plan& plan);
+int cobel_tab_nact_launch(const cobel_world* world, const cobel_tab_run_t& r,
+                          const cobel_tab_plan& plan, hipStream_t st);
 
 // world.hip: the additions NumPy's pairwise sum performs on k non-zero elements at `pos` (ascending)
 // of a vector of n elements; returns the slot holding the result (-1: k == 0)
@@ -119,6 +149,19 @@ int cobel_world_check4(const cobel_world* w, const char* who);  // ... and a fou
   do {                                 \
     if (!(cond)) return cobel_fail(code, __VA_ARGS__); \
   } while (0)
+
+// Launches `kernel`; more than 64 KiB of dynamic LDS have to be allowed to the kernel first.
+template <typename ARGS>
+hipError_t cobel_launch(void (*kernel)(ARGS), dim3 grid, dim3 block, size_t lds, hipStream_t st,
+                        const ARGS& args) {
+  if (lds > 64 * 1024) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(kernel, grid, block, lds, st, args);
+  return hipGetLastError();
+}
 
 // Packed 8-byte records.
 //   model entry  : lo = f32 reward estimate, hi = next_state | nonterminal << 16

@@ -570,10 +570,31 @@ __global__ __launch_bounds__(64) void k_tab_general(const gen_args G) {
   if (G.r.batches_done && batches) atomicAdd(G.r.batches_done, batches);
 }
 
+// (an if chain: it names the instantiations in the order the code object has always held them in)
+template <int AGENT>
+auto general_variant(int A) -> void (*)(const gen_args) {
+  if (A <= 8) return &k_tab_general<AGENT, 8>;
+  if (A <= 16) return &k_tab_general<AGENT, 16>;
+  return &k_tab_general<AGENT, 32>;
+}
+
 }  // namespace
 
-// Arguments already checked by cobel_tab_run.
-int cobel_tab_general_launch(const cobel_world* world, const cobel_tab_run_t& r, hipStream_t st) {
+// Lanes per workgroup.  The lanes share nothing, and a lane spends its time waiting for its own
+// dependent table reads: 65 536 instances as 1 024 full waves are ONE wave per SIMD, with nobody to
+// run while it waits.  Narrower workgroups (a wave each, partly filled) put up to eight waves on
+// a SIMD: six-action hexagonal QAgent, 65 536 instances: 3.73 (64 lanes) / 4.08 (32) / 4.11 (16) /
+// 4.23e8 env-steps/s (8).  Full waves again once there are enough instances to fill the chip.
+// (cobel_tab_describe reports the kernel as 64 instances per workgroup, no LDS, whatever lpb.)
+void cobel_tab_general_plan(const cobel_tab_run_t& r, cobel_tab_plan& plan) {
+  plan.kind = r.n ? COBEL_TAB_KERNEL_GENERAL : 0;
+  plan.inst_per_wg = r.n ? 64 : 0;
+  plan.lpb = 64;
+  while (plan.lpb > 8 && (long long)r.n < 8192ll * plan.lpb) plan.lpb >>= 1;
+}
+
+int cobel_tab_general_launch(const cobel_world* world, const cobel_tab_run_t& r,
+                             const cobel_tab_plan& plan, hipStream_t st) {
   gen_args G;
   G.rec = world->rec;
   G.next_n = world->next_n;
@@ -591,26 +612,9 @@ int cobel_tab_general_launch(const cobel_world* world, const cobel_tab_run_t& r,
   G.alpha_f = (float)r.alpha;
   G.gamma_f = (float)r.gamma;
   G.model_lr_f = (float)r.model_lr;
-  // Lanes per workgroup.  The lanes share nothing, and a lane spends its time waiting for its own
-  // dependent table reads: 65 536 instances as 1 024 full waves are ONE wave per SIMD, with nobody to
-  // run while it waits.  Narrower workgroups (a wave each, partly filled) put up to eight waves on
-  // a SIMD: six-action hexagonal QAgent, 65 536 instances: 3.73 (64 lanes) / 4.08 (32) / 4.11 (16) /
-  // 4.23e8 env-steps/s (8).  Full waves again once there are enough instances to fill the chip.
-  int lpb = 64;
-  while (lpb > 8 && (long long)r.n < 8192ll * lpb) lpb >>= 1;
-  const dim3 grid((unsigned)((r.n + lpb - 1) / lpb));
-  COBEL_REQUIRE(G.A <= 8 || !(r.flags & COBEL_F_MASK_ACTIONS) || ((uintptr_t)r.action_mask & 3u) == 0,
-                COBEL_E_ARG, "cobel_tab_run: the action masks of a %d-action world are 32-bit words, "
-                "4-byte aligned", G.A);
-#define COBEL_GENERAL(AGENT)                                                                     \
-  do {                                                                                           \
-    if (G.A <= 8) hipLaunchKernelGGL((k_tab_general<AGENT, 8>), grid, dim3(lpb), 0, st, G);      \
-    else if (G.A <= 16) hipLaunchKernelGGL((k_tab_general<AGENT, 16>), grid, dim3(lpb), 0, st, G); \
-    else hipLaunchKernelGGL((k_tab_general<AGENT, 32>), grid, dim3(lpb), 0, st, G);              \
-  } while (0)
-  if (r.agent == COBEL_AGENT_DYNAQ) COBEL_GENERAL(COBEL_AGENT_DYNAQ);
-  else COBEL_GENERAL(COBEL_AGENT_Q);
-#undef COBEL_GENERAL
-  COBEL_HIP_TRY(hipGetLastError());
+  const auto kernel = r.agent == COBEL_AGENT_DYNAQ ? general_variant<COBEL_AGENT_DYNAQ>(G.A)
+                                                   : general_variant<COBEL_AGENT_Q>(G.A);
+  COBEL_HIP_TRY(cobel_launch(kernel, dim3((unsigned)((r.n + plan.lpb - 1) / plan.lpb)),
+                             dim3(plan.lpb), 0, st, G));
   return COBEL_OK;
 }

@@ -64,15 +64,6 @@ struct tab_lds {
 constexpr int kThrBytes = 16 * 3 * 8;
 constexpr int kPassLanes = COBEL_MAX_BATCH;   // planning updates one wavefront takes per pass
 
-// LDS is handed out in blocks of 1 280 bytes, 128 per CU — not in KiB (measured on MI355X with
-// scripts/experiments/exp_occupancy.py: the launch time of k_tab_wpi steps down at 15 360 and at 14 080 bytes
-// per workgroup and is flat in between; 16 384 B, a 32 x 32 world, are 13 blocks: nine per CU —
-// k_tab_pwg's ONE workgroup per CU takes all 128 blocks for ten).
-inline int lds_workgroups_per_cu(size_t bytes) {
-  const size_t blocks = (bytes + 1279) / 1280;
-  return blocks ? (int)(128 / blocks) : 128;
-}
-
 __host__ __device__ __forceinline__ size_t tab_lds_bytes(int S, int agent, bool replay, bool wlds,
                                                          bool occ, bool midx = false) {
   size_t b = (size_t)S * 16;
@@ -1070,54 +1061,88 @@ __global__ __launch_bounds__(256) void k_model_index(const uint64_t* __restrict_
   index[t] = (uint16_t)((hi & 0x3fffu) | (((hi >> 16) & 1u) << 14) | (lo ? 0x8000u : 0u));
 }
 
-template <int AGENT, bool OCC, bool WLDS, bool FAST, bool MIDX, bool PSETS, bool STOCH = false,
-          bool MULTI = false>
-int launch_wpi(const tab_args& A, size_t lds, hipStream_t st) {
-  if (lds > 64 * 1024) {
-    COBEL_HIP_TRY(hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&k_tab_wpi<AGENT, OCC, WLDS, FAST, MIDX, PSETS, STOCH, MULTI>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  }
-  hipLaunchKernelGGL((k_tab_wpi<AGENT, OCC, WLDS, FAST, MIDX, PSETS, STOCH, MULTI>), dim3(A.r.n),
-                     dim3(64), lds, st, A);
-  COBEL_HIP_TRY(hipGetLastError());
+tab_args make_tab_args(const cobel_world* world, const cobel_tab_run_t& r, const cobel_tab_plan& P) {
+  tab_args A;
+  A.rec = world->rec;
+  A.starts = world->starts;
+  A.start_off = world->start_off;
+  A.S = world->n_states;
+  A.n_worlds = world->n_worlds;
+  A.r = r;
+  A.eps = cobel_make_eps_consts(r.epsilon);
+  A.alpha_f = (float)r.alpha;
+  A.gamma_f = (float)r.gamma;
+  A.model_lr_f = (float)r.model_lr;
+  A.lpw = P.lpw;
+  A.succ_off = world->succ_off;
+  A.succ_state = world->succ_state;
+  A.succ_cdf = world->succ_cdf;
+  return A;
+}
+
+// The instantiations, chosen as kernel pointers.  (They are named in the order the code object has
+// always held them in — k_tab_lpi first — so that the device code stays byte for byte what it was.)
+using tab_kernel_t = void (*)(const tab_args);
+
+template <bool ONE, bool MON>
+tab_kernel_t lpi_variant(bool logs, bool extra) {
+  if (logs) return extra ? &k_tab_lpi<ONE, MON, true, true> : &k_tab_lpi<ONE, MON, true, false>;
+  return extra ? &k_tab_lpi<ONE, MON, false, true> : &k_tab_lpi<ONE, MON, false, false>;
+}
+
+int lpi_launch(const cobel_world* world, const cobel_tab_run_t& r, const cobel_tab_plan& P,
+               hipStream_t st) {
+  const bool learn = (r.flags & COBEL_F_LEARN) != 0;
+  const bool one = world->n_worlds == 1;
+  const bool mon = r.lat_sum || r.lat_cnt || r.reward_sum || r.resp_cnt;
+  // (QAgent with a log but no replay in this call still appends its experiences)
+  const bool logs = r.agent == COBEL_AGENT_Q && learn && r.replay_log != nullptr && r.log_cap > 0;
+  // (k_tab_lpi's EXTRA: anything but plain training without masks, traces and last experience)
+  const bool extra = !learn || ((r.flags & COBEL_F_MASK_ACTIONS) && r.action_mask) || r.last_exp ||
+                     r.lat_trace;
+  const tab_kernel_t kernel =
+      one ? (mon ? lpi_variant<true, true>(logs, extra) : lpi_variant<true, false>(logs, extra))
+          : (mon ? lpi_variant<false, true>(logs, extra) : lpi_variant<false, false>(logs, extra));
+  COBEL_HIP_TRY(cobel_launch(kernel, dim3((unsigned)((r.n + P.lpw - 1) / P.lpw)), dim3(64), P.lds,
+                             st, make_tab_args(world, r, P)));
   return COBEL_OK;
 }
 
-template <int AGENT, bool FAST, bool MIDX, bool PSETS>
-int dispatch_wpi2(const tab_args& A, bool occ, bool wlds, size_t lds, hipStream_t st) {
-  if (!FAST && A.succ_off) {   // (drawn successors: generic form only, see cobel_tab_run)
-    if (occ) return wlds ? launch_wpi<AGENT, true, true, false, false, PSETS, true>(A, lds, st)
-                         : launch_wpi<AGENT, true, false, false, false, PSETS, true>(A, lds, st);
-    return wlds ? launch_wpi<AGENT, false, true, false, false, PSETS, true>(A, lds, st)
-                : launch_wpi<AGENT, false, false, false, false, PSETS, true>(A, lds, st);
-  }
-  if (FAST && MIDX && A.r.batch > kPassLanes) {   // (several passes per step: see MULTI)
-    if (occ) return wlds ? launch_wpi<AGENT, true, true, FAST, MIDX, PSETS, false, FAST && MIDX>(A, lds, st)
-                         : launch_wpi<AGENT, true, false, FAST, MIDX, PSETS, false, FAST && MIDX>(A, lds, st);
-    return wlds ? launch_wpi<AGENT, false, true, FAST, MIDX, PSETS, false, FAST && MIDX>(A, lds, st)
-                : launch_wpi<AGENT, false, false, FAST, MIDX, PSETS, false, FAST && MIDX>(A, lds, st);
-  }
-  if (occ) return wlds ? launch_wpi<AGENT, true, true, FAST, MIDX, PSETS>(A, lds, st)
-                       : launch_wpi<AGENT, true, false, FAST, MIDX, PSETS>(A, lds, st);
-  return wlds ? launch_wpi<AGENT, false, true, FAST, MIDX, PSETS>(A, lds, st)
-              : launch_wpi<AGENT, false, false, FAST, MIDX, PSETS>(A, lds, st);
+template <int AGENT, bool FAST, bool MIDX, bool PSETS, bool STOCH = false, bool MULTI = false>
+tab_kernel_t wpi_variant(const cobel_tab_plan& P) {
+  if (P.occ) return P.wlds ? &k_tab_wpi<AGENT, true, true, FAST, MIDX, PSETS, STOCH, MULTI>
+                           : &k_tab_wpi<AGENT, true, false, FAST, MIDX, PSETS, STOCH, MULTI>;
+  return P.wlds ? &k_tab_wpi<AGENT, false, true, FAST, MIDX, PSETS, STOCH, MULTI>
+                : &k_tab_wpi<AGENT, false, false, FAST, MIDX, PSETS, STOCH, MULTI>;
 }
 
 // The plain-training kernels exist with and without parameter sets; the generic ones (masks,
-// episodic replay, test runs, QAgent replay) always read them through the same code.
-template <int AGENT>
-int dispatch_wpi(const tab_args& A, bool occ, bool wlds, bool fast, bool midx, size_t lds,
-                 hipStream_t st) {
-  const bool psets = A.r.param_index != nullptr;
-  if (AGENT == COBEL_AGENT_DYNAQ && fast && midx)
-    return psets ? dispatch_wpi2<COBEL_AGENT_DYNAQ, true, true, true>(A, occ, wlds, lds, st)
-                 : dispatch_wpi2<COBEL_AGENT_DYNAQ, true, true, false>(A, occ, wlds, lds, st);
-  if (AGENT == COBEL_AGENT_DYNAQ && fast)
-    return psets ? dispatch_wpi2<COBEL_AGENT_DYNAQ, true, false, true>(A, occ, wlds, lds, st)
-                 : dispatch_wpi2<COBEL_AGENT_DYNAQ, true, false, false>(A, occ, wlds, lds, st);
-  return psets ? dispatch_wpi2<AGENT, false, false, true>(A, occ, wlds, lds, st)
-               : dispatch_wpi2<AGENT, false, false, false>(A, occ, wlds, lds, st);
+// episodic replay, test runs, QAgent replay) always read them through the same code.  Drawn
+// successors: generic form only (STOCH).  Several passes per step: digest form only (MULTI).
+int wpi_launch(const cobel_world* world, const cobel_tab_run_t& r, const cobel_tab_plan& P,
+               hipStream_t st) {
+  constexpr int D = COBEL_AGENT_DYNAQ, Q = COBEL_AGENT_Q;
+  const bool dyna = r.agent == D, psets = r.param_index != nullptr;
+  const bool draws = world->succ_off != nullptr, multi = r.batch > kPassLanes;
+  tab_kernel_t kernel;
+  if (dyna && (draws || P.midx)) {
+    if (psets) kernel = draws   ? wpi_variant<D, false, false, true, true>(P)
+                        : multi ? wpi_variant<D, true, true, true, false, true>(P)
+                                : wpi_variant<D, true, true, true>(P);
+    else kernel = draws   ? wpi_variant<D, false, false, false, true>(P)
+                  : multi ? wpi_variant<D, true, true, false, false, true>(P)
+                          : wpi_variant<D, true, true, false>(P);
+  } else if (dyna && P.fast) {
+    kernel = psets ? wpi_variant<D, true, false, true>(P) : wpi_variant<D, true, false, false>(P);
+  } else if (dyna) {
+    kernel = psets ? wpi_variant<D, false, false, true>(P) : wpi_variant<D, false, false, false>(P);
+  } else if (psets) {
+    kernel = draws ? wpi_variant<Q, false, false, true, true>(P) : wpi_variant<Q, false, false, true>(P);
+  } else {
+    kernel = draws ? wpi_variant<Q, false, false, false, true>(P) : wpi_variant<Q, false, false, false>(P);
+  }
+  COBEL_HIP_TRY(cobel_launch(kernel, dim3(r.n), dim3(64), P.lds, st, make_tab_args(world, r, P)));
+  return COBEL_OK;
 }
 
 }  // namespace
@@ -1165,9 +1190,41 @@ extern "C" int cobel_model_index_build(const uint64_t* model, uint16_t* index, i
   return COBEL_OK;
 }
 
-// describe != NULL: report which kernel the run would take instead of launching it
-static int tab_run_impl(const cobel_world_t* world, const cobel_tab_run_t* run, void* stream,
-                        int32_t* describe) {
+// Lane per instance (k_tab_lpi): no planning in this call and nothing but Q to keep per instance.
+// Instances per wave: 64 unless the Q columns of a full wave do not fit in LDS.  (Narrower waves
+// to give each SIMD more than one resident wave were measured on C2 — 65 536 instances are one
+// wave per SIMD — and lose: 1.25 ms per launch at 64, 1.45 ms at 32, 2.57 ms at 16 instances per
+// wave; the step is as much issue- as latency-bound.  COBEL_DEBUG_LPW overrides.)
+static bool lpi_plan(const cobel_world* world, const cobel_tab_run_t& r, cobel_tab_plan& P) {
+  // (per launch: scripts/experiments/exp_occupancy.py; validated against the limit below)
+  static const char* const lpw_env = cobel_debug_env("COBEL_DEBUG_LPW");
+  const size_t S = (size_t)world->n_states;
+  int lpw = 64;
+  if (lpw_env) {
+    const int v = atoi(lpw_env);
+    if (v == 16 || v == 32 || v == 64) lpw = v;
+  }
+  while (lpw > 16 && S * lpw * 16 + kThrBytes + S * 18 + 16 + kMonBytes > (size_t)kLdsLimit)
+    lpw >>= 1;   // larger worlds: fewer columns per wave so that the Q tables still fit
+  P.lpw = lpw;   // (every wavefront form passes it on to its kernel)
+  const size_t lds = S * lpw * 16 + kThrBytes + S * 16 + ((S * 2 + 15) & ~(size_t)15);
+  const bool learn = (r.flags & COBEL_F_LEARN) != 0;
+  const bool mon = r.lat_sum || r.lat_cnt || r.reward_sum || r.resp_cnt;
+  // (per-instance parameter sets: the lane-per-instance kernel keeps ONE threshold table per wave)
+  if (world->succ_off || P.replay || P.occ || r.param_index || (learn && r.agent != COBEL_AGENT_Q) ||
+      lds + kMonBytes > (size_t)kLdsLimit || r.n < 64 || (r.flags & COBEL_F_FORCE_WAVE))
+    return false;
+  P.kind = COBEL_TAB_KERNEL_LPI;
+  P.lds = lds + (mon ? (size_t)kMonBytes : 0);
+  P.wg_per_cu = lds_workgroups_per_cu(P.lds);
+  P.inst_per_wg = lpw;
+  return true;
+}
+
+// The routing of a run, top to bottom: the argument checks, then the first kernel that takes it.
+static int tab_plan(const cobel_world_t* world, const cobel_tab_run_t* run, cobel_tab_plan& P) {
+  P = cobel_tab_plan{};
+  // 1. arguments
   COBEL_REQUIRE(world && run, COBEL_E_ARG, "cobel_tab_run: NULL world/run");
   if (int rc = cobel_world_check(world, "cobel_tab_run")) return rc;
   const cobel_tab_run_t& r = *run;
@@ -1190,201 +1247,101 @@ static int tab_run_impl(const cobel_world_t* world, const cobel_tab_run_t* run, 
                 "cobel_tab_run: epsilon %g outside [0, 1]", r.epsilon);
   COBEL_REQUIRE(!(r.flags & COBEL_F_MASK_ACTIONS) || r.action_mask, COBEL_E_ARG,
                 "cobel_tab_run: mask_actions set without an action mask");
+  COBEL_REQUIRE(world->n_actions <= 8 || !(r.flags & COBEL_F_MASK_ACTIONS) ||
+                    ((uintptr_t)r.action_mask & 3u) == 0,
+                COBEL_E_ARG, "cobel_tab_run: the action masks of a %d-action world are 32-bit words, "
+                "4-byte aligned", world->n_actions);
   COBEL_REQUIRE(r.trial_cap >= 0 && r.log_cap >= 0, COBEL_E_RANGE, "cobel_tab_run: negative cap");
   COBEL_REQUIRE(!r.param_index || (r.param_sets && r.n_param_sets > 0), COBEL_E_ARG,
                 "cobel_tab_run: param_index given without parameter sets");
-  // Runs outside what the wavefront kernels are built for — an action count other than four
-  // (hexagonal topologies), transition rows that are distributions (the successor is drawn),
-  // more than COBEL_MAX_BATCH updates per step, tables beyond LDS — take
-  // the general kernel (general.hip: one lane per instance, every update in sequence).
-  int32_t lds_max = 0;
-  // (batches above COBEL_MAX_BATCH run as several passes of the wavefront kernels: Dyna-Q's pairs
-  //  and — round 6 — QAgent's log records beyond the first pass are drawn and gathered in the step)
-  const int32_t pass = r.batch > COBEL_MAX_BATCH ? COBEL_MAX_BATCH : r.batch;
-  // (worlds whose transition rows are distributions: the generic wavefront kernels draw the
-  //  successor in the step — no fast / digest / lane-per-instance / persistent form for them)
-  const bool draws = world->succ_off != nullptr;
-  const bool replays = (r.flags & COBEL_F_LEARN) && !(r.flags & COBEL_F_NO_REPLAY) && r.batch > 0 &&
-                       (r.agent == COBEL_AGENT_DYNAQ || r.replay_log != nullptr);
-  // (without replayed updates a lane per instance is the better shape — what k_tab_lpi is for
+  P.replay = (r.flags & COBEL_F_LEARN) && !(r.flags & COBEL_F_NO_REPLAY) && r.batch > 0 &&
+             (r.agent == COBEL_AGENT_DYNAQ || r.replay_log != nullptr);
+
+  // 2. Q-learning on worlds of other action counts whose tables fit the LDS: one wavefront per instance
+  if (cobel_tab_nact_plan(world, r, P)) return COBEL_OK;
+
+  // 3. Runs outside what the four-action wavefront kernels are built for take the general kernel
+  // (general.hip: one lane per instance, every update in sequence): an action count other than
+  // four (hexagonal topologies), tables beyond LDS, and drawn successors without replayed updates.
+  // (Worlds whose transition rows are distributions: the generic wavefront kernels draw the
+  //  successor in the step — no fast / digest / lane-per-instance / persistent form for them; but
+  //  without replayed updates a lane per instance is the better shape — what k_tab_lpi is for
   //  one-hot rows; measured on slippery 10 x 10 / 32 x 32 worlds, 65 536 instances x 512 steps:
   //  Q-learning 6.0 / 6.3 ms on k_tab_general against 11.4 / 20.8 on the wavefront kernel, Dyna-Q
   //  B 32 44 / 72 ms against 14.6 / 34.9: scripts/experiments/exp_tab_slippery.py)
-  const bool general = world->n_actions != 4 || (draws && !replays) ||
-                       (r.batch > COBEL_MAX_BATCH && r.agent != COBEL_AGENT_DYNAQ &&
-                        (r.flags & COBEL_F_EPISODIC)) ||
-                       (r.flags & COBEL_F_TAB_GENERAL) ||
-                       cobel_tab_query(world->n_states, r.agent, pass, &lds_max, nullptr) != COBEL_OK;
-  // Q-learning on worlds of other action counts whose tables fit the LDS: one wavefront per instance
-  {
-    size_t nact_lds = 0;
-    int nact_ipw = 0;
-    if (cobel_tab_nact_covers(world, r, &nact_lds, &nact_ipw)) {
-      if (describe) {
-        describe[0] = COBEL_TAB_KERNEL_WQN;
-        describe[1] = (int32_t)nact_lds;
-        describe[2] = lds_workgroups_per_cu(nact_lds);
-        describe[3] = nact_ipw;
-        return COBEL_OK;
-      }
-      return cobel_tab_nact_launch(world, r, (hipStream_t)stream);
-    }
-  }
-  if (general) {
+  // Batches above COBEL_MAX_BATCH run as several passes of the wavefront kernels: Dyna-Q's pairs
+  // and QAgent's log records beyond the first pass are drawn and gathered in the step.  The
+  // clause on COBEL_F_EPISODIC keeps QAgent runs that carry the flag (which every kernel ignores for
+  // QAgent: only Dyna-Q replays per trial) where they ran before QAgent's batches above
+  // COBEL_MAX_BATCH moved to the wavefront kernels; it is a leftover of that move, kept as found.
+  const int32_t pass = r.batch > COBEL_MAX_BATCH ? COBEL_MAX_BATCH : r.batch;
+  if (world->n_actions != 4 || (world->succ_off && !P.replay) ||
+      (r.batch > COBEL_MAX_BATCH && r.agent != COBEL_AGENT_DYNAQ && (r.flags & COBEL_F_EPISODIC)) ||
+      (r.flags & COBEL_F_TAB_GENERAL) ||
+      cobel_tab_query(world->n_states, r.agent, pass, nullptr, nullptr) != COBEL_OK) {
     COBEL_REQUIRE(world->n_actions == 4 || !r.model_index, COBEL_E_ARG,
                   "cobel_tab_run: the model digest exists for four-action worlds only");
-    if (describe) {
-      describe[0] = r.n ? COBEL_TAB_KERNEL_GENERAL : 0;
-      describe[1] = 0;
-      describe[2] = 0;
-      describe[3] = r.n ? 64 : 0;
-      return COBEL_OK;
-    }
-    if (r.n == 0) return COBEL_OK;
-    return cobel_tab_general_launch(world, r, (hipStream_t)stream);
+    cobel_tab_general_plan(r, P);
+    return COBEL_OK;
   }
-  if (r.n == 0) return COBEL_OK;
+  if (r.n == 0) return COBEL_OK;   // (nothing to launch: kind and numbers stay 0)
 
-  tab_args A;
-  A.rec = world->rec;
-  A.starts = world->starts;
-  A.start_off = world->start_off;
-  A.S = world->n_states;
-  A.n_worlds = world->n_worlds;
-  A.r = r;
-  A.eps = cobel_make_eps_consts(r.epsilon);
-  A.alpha_f = (float)r.alpha;
-  A.gamma_f = (float)r.gamma;
-  A.model_lr_f = (float)r.model_lr;
-  A.succ_off = world->succ_off;
-  A.succ_state = world->succ_state;
-  A.succ_cdf = world->succ_cdf;
-  const bool occ = r.occupancy != nullptr;
-  const bool wlds = world->n_states <= kWorldLdsStates;
-  const bool replay = (r.flags & COBEL_F_LEARN) && !(r.flags & COBEL_F_NO_REPLAY) && r.batch > 0 &&
-                      (r.agent == COBEL_AGENT_DYNAQ || r.replay_log != nullptr);
-  // (more than COBEL_MAX_BATCH updates per step: plain training takes them in passes only with the
-  //  digest in HBM — the MULTI instantiations)
+  // The four-action wavefront forms share these choices.  Plain Dyna-Q training has its own
+  // instantiations (fast), with the model digest in HBM where the caller brings one (midx); more
+  // than COBEL_MAX_BATCH updates per step it takes in passes only with the digest.
   const bool digest = r.model_index != nullptr && !(r.flags & COBEL_F_FORCE_LDS_MODEL);
-  const bool fast = !draws && r.agent == COBEL_AGENT_DYNAQ && replay && !(r.flags & COBEL_F_EPISODIC) &&
-                    (r.batch <= COBEL_MAX_BATCH || digest) &&
-                    !(r.flags & (COBEL_F_MASK_ACTIONS | COBEL_F_TEST_STREAM)) && !r.last_exp;
-  const bool midx = fast && r.model_index != nullptr && !(r.flags & COBEL_F_FORCE_LDS_MODEL);
-  // (per launch: scripts/experiments/exp_occupancy.py; validated against the limit below)
-  static const char* const lpw_env = cobel_debug_env("COBEL_DEBUG_LPW");
-  size_t lds = tab_lds_bytes(world->n_states, r.agent, replay, wlds, occ, midx);
-  const size_t lds_pad = cobel_debug_lds_pad(lds, (size_t)kLdsLimit);   // occupancy experiments
-  lds += lds_pad;
+  P.occ = r.occupancy != nullptr;
+  P.wlds = world->n_states <= kWorldLdsStates;
+  P.fast = !world->succ_off && r.agent == COBEL_AGENT_DYNAQ && P.replay &&
+           !(r.flags & COBEL_F_EPISODIC) && (r.batch <= COBEL_MAX_BATCH || digest) &&
+           !(r.flags & (COBEL_F_MASK_ACTIONS | COBEL_F_TEST_STREAM)) && !r.last_exp;
+  P.midx = P.fast && digest;
+  P.lds = tab_lds_bytes(world->n_states, r.agent, P.replay, P.wlds, P.occ, P.midx);
+  P.lds_pad = cobel_debug_lds_pad(P.lds, (size_t)kLdsLimit);   // occupancy experiments
+  P.lds += P.lds_pad;
+
+  // 4. a lane per instance: no planning in this call
+  if (lpi_plan(world, r, P)) return COBEL_OK;
+  // 5. plain training with the digest on worlds whose Q table lets LDS hold fewer instances than
+  // the register file: one persistent workgroup per CU
+  if (cobel_tab_pwg_plan(world, r, P)) return COBEL_OK;
+  // 6. one wavefront per instance
+  P.kind = P.midx ? COBEL_TAB_KERNEL_WPI_INDEX
+                  : (P.fast ? COBEL_TAB_KERNEL_WPI_FAST : COBEL_TAB_KERNEL_WPI);
+  P.wg_per_cu = lds_workgroups_per_cu(P.lds);
+  P.inst_per_wg = 1;
+  return COBEL_OK;
+}
+
+static int tab_run(const cobel_world_t* world, const cobel_tab_run_t* run, void* stream) {
+  cobel_tab_plan P;
+  if (int rc = tab_plan(world, run, P)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  // No planning in this call and nothing but Q to keep per instance: 64 instances per wave.
-  const bool learn = (r.flags & COBEL_F_LEARN) != 0;
-  // instances per wave: 64 unless the Q columns of a full wave do not fit in LDS.  (Narrower waves
-  // to give each SIMD more than one resident wave were measured on C2 — 65 536 instances are one
-  // wave per SIMD — and lose: 1.25 ms per launch at 64, 1.45 ms at 32, 2.57 ms at 16 instances per
-  // wave; the step is as much issue- as latency-bound.  COBEL_DEBUG_LPW overrides.)
-  int lpw = 64;
-  if (lpw_env) {
-    const int v = atoi(lpw_env);
-    if (v == 16 || v == 32 || v == 64) lpw = v;
+  if (!P.inst_per_wg) return COBEL_OK;   // n == 0
+  switch (P.kind) {
+    case COBEL_TAB_KERNEL_LPI: return lpi_launch(world, *run, P, st);
+    case COBEL_TAB_KERNEL_GENERAL: return cobel_tab_general_launch(world, *run, P, st);
+    case COBEL_TAB_KERNEL_PWG: return cobel_tab_pwg_launch(world, *run, P, st);
+    case COBEL_TAB_KERNEL_WQN: return cobel_tab_nact_launch(world, *run, P, st);
+    default: return wpi_launch(world, *run, P, st);
   }
-  while (lpw > 16 && (size_t)world->n_states * lpw * 16 + kThrBytes + (size_t)world->n_states * 18 +
-                              16 + kMonBytes > (size_t)kLdsLimit)
-    lpw >>= 1;   // larger worlds: fewer columns per wave so that the Q tables still fit
-  A.lpw = lpw;
-  const size_t lds_lpi = (size_t)world->n_states * lpw * 16 + kThrBytes +
-                         (size_t)world->n_states * 16 + (((size_t)world->n_states * 2 + 15) & ~(size_t)15);
-  // (per-instance parameter sets: the lane-per-instance kernel keeps ONE threshold table per wave)
-  if (!draws && !replay && !occ && !r.param_index && (!learn || r.agent == COBEL_AGENT_Q) &&
-      lds_lpi + kMonBytes <= (size_t)kLdsLimit &&
-      r.n >= 64 && !(r.flags & COBEL_F_FORCE_WAVE)) {
-    const bool one = world->n_worlds == 1;
-    const bool mon = r.lat_sum || r.lat_cnt || r.reward_sum || r.resp_cnt;
-    const size_t bytes = lds_lpi + (mon ? (size_t)kMonBytes : 0);
-    const dim3 grid((unsigned)((r.n + lpw - 1) / lpw));
-    if (describe) {
-      describe[0] = COBEL_TAB_KERNEL_LPI;
-      describe[1] = (int32_t)bytes;
-      describe[2] = lds_workgroups_per_cu(bytes);
-      describe[3] = lpw;
-      return COBEL_OK;
-    }
-#define COBEL_LPI_X(ONE, MON, LOG, EXTRA)                                                      \
-  do {                                                                                         \
-    if (bytes > 64 * 1024)                                                                     \
-      COBEL_HIP_TRY(hipFuncSetAttribute(                                                       \
-          reinterpret_cast<const void*>(&k_tab_lpi<ONE, MON, LOG, EXTRA>),                     \
-          hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));                            \
-    hipLaunchKernelGGL((k_tab_lpi<ONE, MON, LOG, EXTRA>), grid, dim3(64), bytes, st, A);       \
-  } while (0)
-#define COBEL_LPI(ONE, MON, LOG)                                                               \
-  do {                                                                                         \
-    if (extra) COBEL_LPI_X(ONE, MON, LOG, true);                                               \
-    else COBEL_LPI_X(ONE, MON, LOG, false);                                                    \
-  } while (0)
-#define COBEL_LPI2(ONE, MON)                                                                   \
-  do {                                                                                         \
-    if (logs) COBEL_LPI(ONE, MON, true);                                                       \
-    else COBEL_LPI(ONE, MON, false);                                                           \
-  } while (0)
-    // (QAgent with a log but no replay in this call still appends its experiences)
-    const bool logs = r.agent == COBEL_AGENT_Q && learn && r.replay_log != nullptr && r.log_cap > 0;
-    // (k_tab_lpi's EXTRA: anything but plain training without masks, traces and last experience)
-    const bool extra = !learn || ((r.flags & COBEL_F_MASK_ACTIONS) && r.action_mask) || r.last_exp ||
-                       r.lat_trace;
-    if (one && mon) COBEL_LPI2(true, true);
-    else if (one) COBEL_LPI2(true, false);
-    else if (mon) COBEL_LPI2(false, true);
-    else COBEL_LPI2(false, false);
-#undef COBEL_LPI2
-#undef COBEL_LPI
-#undef COBEL_LPI_X
-    COBEL_HIP_TRY(hipGetLastError());
-    return COBEL_OK;
-  }
-  // plain training with the digest in HBM on worlds whose Q table lets LDS hold fewer instances
-  // than the register file: one persistent workgroup per CU, part of its waves with Q in L2
-  if (midx && !occ && !lds_pad && !(r.flags & (COBEL_F_NO_PWG | COBEL_F_FORCE_WAVE))) {
-    int nl = 0, ng = 0;
-    size_t wg_lds = 0;
-    if (cobel_tab_pwg_plan(world, r, &nl, &ng, &wg_lds)) {
-      if (describe) {
-        describe[0] = COBEL_TAB_KERNEL_PWG;
-        describe[1] = (int32_t)wg_lds;
-        describe[2] = 1;
-        describe[3] = nl + ng;
-        return COBEL_OK;
-      }
-      return cobel_tab_pwg_launch(world, r, st);
-    }
-  }
-  if (describe) {
-    describe[0] = midx ? COBEL_TAB_KERNEL_WPI_INDEX
-                       : (fast ? COBEL_TAB_KERNEL_WPI_FAST : COBEL_TAB_KERNEL_WPI);
-    describe[1] = (int32_t)lds;
-    describe[2] = lds_workgroups_per_cu(lds);
-    describe[3] = 1;
-    return COBEL_OK;
-  }
-  if (r.agent == COBEL_AGENT_DYNAQ)
-    return dispatch_wpi<COBEL_AGENT_DYNAQ>(A, occ, wlds, fast, midx, lds, st);
-  return dispatch_wpi<COBEL_AGENT_Q>(A, occ, wlds, false, false, lds, st);
 }
 
 extern "C" int cobel_tab_run(const cobel_world_t* world, const cobel_tab_run_t* run,
                              void* stream) {
-  return tab_run_impl(world, run, stream, nullptr);
+  return tab_run(world, run, stream);
 }
 
 extern "C" int cobel_dynaq_run(const cobel_world_t* world, const cobel_tab_run_t* run, void* stream) {
   COBEL_REQUIRE(run && run->agent == COBEL_AGENT_DYNAQ, COBEL_E_ARG,
                 "cobel_dynaq_run: run->agent is not COBEL_AGENT_DYNAQ");
-  return tab_run_impl(world, run, stream, nullptr);
+  return tab_run(world, run, stream);
 }
 
 extern "C" int cobel_q_run(const cobel_world_t* world, const cobel_tab_run_t* run, void* stream) {
   COBEL_REQUIRE(run && run->agent == COBEL_AGENT_Q, COBEL_E_ARG,
                 "cobel_q_run: run->agent is not COBEL_AGENT_Q");
-  return tab_run_impl(world, run, stream, nullptr);
+  return tab_run(world, run, stream);
 }
 
 extern "C" int cobel_tab_scratch_check(const void* scratch, int64_t scratch_bytes, void* stream) {
@@ -1405,5 +1362,11 @@ extern "C" int cobel_tab_describe(const cobel_world_t* world, const cobel_tab_ru
   COBEL_REQUIRE(out, COBEL_E_ARG, "cobel_tab_describe: NULL out");
   out[0] = out[1] = out[2] = out[3] = 0;
   if (world && run && run->n == 0) return COBEL_OK;
-  return tab_run_impl(world, run, nullptr, out);
+  cobel_tab_plan P;
+  if (int rc = tab_plan(world, run, P)) return rc;
+  out[0] = P.kind;
+  out[1] = (int32_t)P.lds;
+  out[2] = P.wg_per_cu;
+  out[3] = P.inst_per_wg;
+  return COBEL_OK;
 }

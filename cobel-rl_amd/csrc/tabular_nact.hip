@@ -514,17 +514,17 @@ __global__ __launch_bounds__(512) void k_tab_wqn(const nact_args G) {
   }
 }
 
-// waves per workgroup and the LDS they take; false: the run is not covered
-bool nact_plan(const cobel_world* world, const cobel_tab_run_t& r, int* wpg_out, size_t* lds_out) {
+}  // namespace
+
+// Waves per workgroup and the LDS they take; false: the run is not for this kernel.
+bool cobel_tab_nact_plan(const cobel_world* world, const cobel_tab_run_t& r, cobel_tab_plan& plan) {
   const int S = world->n_states, A = world->n_actions;
   const int W = nact_width(A);
   const bool masked = (r.flags & COBEL_F_MASK_ACTIONS) != 0;
   // (the packed log record holds 14-bit states on rows of 8, 13-bit states beyond; the table sizes
   //  below are the tested ones)
   if (r.agent != COBEL_AGENT_Q || A == 4 || A < 1 || A > 32 || !world->next_n || world->succ_off ||
-      r.last_exp || (r.param_index && !r.param_sets) ||
-      (masked && (!r.action_mask || (W > 8 && ((uintptr_t)r.action_mask & 3u)))) ||
-      (r.flags & (COBEL_F_TAB_GENERAL | COBEL_F_EPISODIC)) ||
+      r.last_exp || (r.flags & (COBEL_F_TAB_GENERAL | COBEL_F_EPISODIC)) ||
       S > 1024 || (size_t)S * W > (W == 8 ? 8192u : 16384u) || r.n < 1)
     return false;
   const bool shared = world->n_worlds == 1;
@@ -553,28 +553,15 @@ bool nact_plan(const cobel_world* world, const cobel_tab_run_t& r, int* wpg_out,
   while (wpg > 1 && (r.n + wpg - 1) / wpg < n_cu) wpg >>= 1;
   const size_t lds = nact_lds_bytes(S, A, wpg, shared, masked || r.param_index != nullptr);
   if (lds > lds_cu) return false;
-  *wpg_out = wpg;
-  *lds_out = lds;
+  plan.kind = COBEL_TAB_KERNEL_WQN;
+  plan.lds = lds;
+  plan.wg_per_cu = lds_workgroups_per_cu(lds);
+  plan.inst_per_wg = plan.wpg = wpg;
   return true;
 }
 
-}  // namespace
-
-bool cobel_tab_nact_covers(const cobel_world* world, const cobel_tab_run_t& r, size_t* lds_bytes,
-                           int* instances_per_workgroup) {
-  int wpg = 0;
-  size_t lds = 0;
-  if (!nact_plan(world, r, &wpg, &lds)) return false;
-  if (lds_bytes) *lds_bytes = lds;
-  if (instances_per_workgroup) *instances_per_workgroup = wpg;
-  return true;
-}
-
-int cobel_tab_nact_launch(const cobel_world* world, const cobel_tab_run_t& r, hipStream_t st) {
-  int wpg = 0;
-  size_t lds = 0;
-  if (!nact_plan(world, r, &wpg, &lds))
-    return cobel_fail(COBEL_E_UNSUPPORTED, "cobel_tab_nact_launch: run not covered");
+int cobel_tab_nact_launch(const cobel_world* world, const cobel_tab_run_t& r,
+                          const cobel_tab_plan& plan, hipStream_t st) {
   nact_args G;
   G.next_n = world->next_n;
   G.reward_s = world->reward_s;
@@ -584,37 +571,21 @@ int cobel_tab_nact_launch(const cobel_world* world, const cobel_tab_run_t& r, hi
   G.S = world->n_states;
   G.n_worlds = world->n_worlds;
   G.A = world->n_actions;
-  G.wpg = wpg;
+  G.wpg = plan.wpg;
   G.shared_world = world->n_worlds == 1 ? 1 : 0;
   G.r = r;
   G.alpha_f = (float)r.alpha;
   G.gamma_f = (float)r.gamma;
-  const bool plain = (r.flags & COBEL_F_LEARN) && !(r.flags & COBEL_F_NO_REPLAY) && r.replay_log &&
-                     r.batch > 0 && G.A > 1 && !r.occupancy;
+  const bool plain = plan.replay && G.A > 1 && !r.occupancy;
   const int W = nact_width(G.A);
-  const dim3 grid((unsigned)((r.n + wpg - 1) / wpg)), block(64 * wpg);
-#define COBEL_WQN(PLAIN, W, CDF)                                                                  \
-  do {                                                                                            \
-    if (lds > 64 * 1024)                                                                          \
-      COBEL_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tab_wqn<PLAIN, W, CDF>), \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));   \
-    hipLaunchKernelGGL((k_tab_wqn<PLAIN, W, CDF>), grid, block, lds, st, G);                      \
-  } while (0)
-  const bool masked = (r.flags & COBEL_F_MASK_ACTIONS) != 0;
-  if (W == 8 && (masked || r.param_index)) {
-    if (plain) COBEL_WQN(true, 8, true);
-    else COBEL_WQN(false, 8, true);
-  } else if (W == 8) {
-    if (plain) COBEL_WQN(true, 8, false);
-    else COBEL_WQN(false, 8, false);
-  } else if (W == 16) {
-    if (plain) COBEL_WQN(true, 16, true);
-    else COBEL_WQN(false, 16, true);
-  } else {
-    if (plain) COBEL_WQN(true, 32, true);
-    else COBEL_WQN(false, 32, true);
-  }
-#undef COBEL_WQN
-  COBEL_HIP_TRY(hipGetLastError());
+  // (rows of eight choose by the threshold table unless masks or parameter sets need the CDF)
+  const bool cdf8 = (r.flags & COBEL_F_MASK_ACTIONS) || r.param_index;
+  void (*const kernel)(const nact_args) =
+      W == 8 && cdf8 ? (plain ? &k_tab_wqn<true, 8, true> : &k_tab_wqn<false, 8, true>)
+      : W == 8       ? (plain ? &k_tab_wqn<true, 8, false> : &k_tab_wqn<false, 8, false>)
+      : W == 16      ? (plain ? &k_tab_wqn<true, 16, true> : &k_tab_wqn<false, 16, true>)
+                     : (plain ? &k_tab_wqn<true, 32, true> : &k_tab_wqn<false, 32, true>);
+  COBEL_HIP_TRY(cobel_launch(kernel, dim3((unsigned)((r.n + plan.wpg - 1) / plan.wpg)),
+                             dim3(64 * plan.wpg), plan.lds, st, G));
   return COBEL_OK;
 }

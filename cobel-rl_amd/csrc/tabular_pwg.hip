@@ -6,12 +6,15 @@
 // instances fit on a CU (17 408 B each).  The step is a chain of dependent work, not a stream:
 // measured on trained agents, the same kernel on 24 x 24 mazes padded to 9 / 10 / 11 / 12 / 14 / 16
 // instances per CU takes 16.75 / 15.45 / 14.37 / 13.43 / 12.05 / 11.03 ms per launch
-// (scripts/experiments/exp_occ_trained.py) — every further resident wave is throughput.  LDS is full at nine;
-// registers allow sixteen.  So here ONE workgroup of sixteen wavefronts owns a CU for the whole
-// launch: `nl` of its waves keep their instance's Q table in LDS exactly as k_tab_wpi does, the
-// other `ng` waves work on the caller's Q table where it lies, in global memory (L2 resident while
-// the instance is in flight: 16 KiB).  All waves take instances from one atomic counter until it
-// runs out, so the two kinds may run at different speeds.
+// (scripts/experiments/exp_occ_trained.py) — every further resident wave is throughput.  LDS is
+// handed out in blocks of 1 280 B, so nine workgroups of k_tab_wpi fill it; ONE workgroup that owns
+// a CU for the whole launch takes all of it, and ten tables of 16 KiB fit.  That is the production
+// form: `nl` = ten waves at 32 x 32 (as many as tables fit, sixteen at most), each keeping its
+// instance's Q table in LDS exactly as k_tab_wpi does.  Waves that work on the caller's Q table
+// where it lies, in global memory (L2 resident while the instance is in flight: 16 KiB) — `ng` of
+// them — exist only for COBEL_F_PWG_GLOBAL and forced mixes (tests, experiments): next to ten LDS
+// waves they cost more than they add (cobel_tab_pwg_plan).  All waves take instances from one
+// atomic counter until it runs out, so the two kinds may run at different speeds.
 //
 // Q in global memory (QG) without a memory round trip per planning round:
 //   * everything a step reads from Q is requested at the top of the step, after the previous
@@ -902,14 +905,14 @@ __global__ __launch_bounds__(1024) void k_tab_pwg(const pwg_args A) {
 
 }  // namespace
 
-// Does this run qualify, and with how many waves of each kind?  (plain Dyna-Q training with the
-// digest in HBM, exact dependency lookup, no visit counters, no parameter sets)
-bool cobel_tab_pwg_plan(const cobel_world* world, const cobel_tab_run_t& r, int* nl_out, int* ng_out,
-                        size_t* lds_out) {
+// Does this run qualify, and with how many waves of each kind?  Plain Dyna-Q training with the
+// digest in HBM (plan.midx), one pass per step, no visit counters, no parameter sets, on worlds
+// whose Q table lets LDS hold fewer instances than the register file.
+bool cobel_tab_pwg_plan(const cobel_world* world, const cobel_tab_run_t& r, cobel_tab_plan& plan) {
   static const char* const force = cobel_debug_env("COBEL_DEBUG_PWG");   // "nl,ng" (experiments)
   const int S = world->n_states;
-  if (r.agent != COBEL_AGENT_DYNAQ || !r.model_index || r.occupancy || r.param_index ||
-      r.last_exp || S * 4 > 4096 || S <= 256 || r.batch < 1 || r.batch > COBEL_MAX_BATCH)
+  if (!plan.midx || plan.lds_pad || (r.flags & (COBEL_F_NO_PWG | COBEL_F_FORCE_WAVE)) ||
+      r.occupancy || r.param_index || S * 4 > 4096 || S <= 256 || r.batch > COBEL_MAX_BATCH)
     return false;
   const bool scratch = r.scratch && r.scratch_bytes >= COBEL_TAB_SCRATCH_BYTES(r.n);
   if (!scratch && !world->queue) return false;
@@ -939,13 +942,15 @@ bool cobel_tab_pwg_plan(const cobel_world* world, const cobel_tab_run_t& r, int*
   } else if (r.flags & COBEL_F_PWG_GLOBAL) {
     nl = 0;
     ng = 16;
-  } else if (128 / ((slice_l + 1279) / 1280) >= 16) {
-    // (LDS comes in blocks of 1 280 B, 128 per CU: tabular.hip lds_workgroups_per_cu)
+  } else if (lds_workgroups_per_cu(slice_l) >= 16) {
     return false;   // LDS is not what limits the resident instances: k_tab_wpi as it is
   }
-  *nl_out = nl;
-  *ng_out = ng;
-  *lds_out = (size_t)nl * slice_l + (size_t)ng * kHashBytes;
+  plan.kind = COBEL_TAB_KERNEL_PWG;
+  plan.lds = (size_t)nl * slice_l + (size_t)ng * kHashBytes;
+  plan.wg_per_cu = 1;
+  plan.inst_per_wg = nl + ng;
+  plan.nl = nl;
+  plan.ng = ng;
   return true;
 }
 
@@ -1028,11 +1033,10 @@ static int plan_slices(const cobel_tab_run_t& r, int grid, int n_cu, int nl, int
   return 3;
 }
 
-int cobel_tab_pwg_launch(const cobel_world* world, const cobel_tab_run_t& r, hipStream_t st) {
-  int nl = 0, ng = 0;
-  size_t lds = 0;
-  if (!cobel_tab_pwg_plan(world, r, &nl, &ng, &lds))
-    return cobel_fail(COBEL_E_UNSUPPORTED, "cobel_tab_pwg_launch: run not covered");
+int cobel_tab_pwg_launch(const cobel_world* world, const cobel_tab_run_t& r,
+                         const cobel_tab_plan& plan, hipStream_t st) {
+  const int nl = plan.nl, ng = plan.ng;
+  size_t lds = plan.lds;
   pwg_args A;
   A.rec = world->rec;
   A.starts = world->starts;
@@ -1093,10 +1097,6 @@ int cobel_tab_pwg_launch(const cobel_world* world, const cobel_tab_run_t& r, hip
   void (*const kernel)(const pwg_args) =
       A.n_slices > 1 ? (pow2 ? &k_tab_pwg<true, true> : &k_tab_pwg<true, false>)
                      : (pow2 ? &k_tab_pwg<false, true> : &k_tab_pwg<false, false>);
-  if (lds > 64 * 1024)
-    COBEL_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * waves), lds, st, A);
-  COBEL_HIP_TRY(hipGetLastError());
+  COBEL_HIP_TRY(cobel_launch(kernel, dim3(grid), dim3(64 * waves), lds, st, A));
   return COBEL_OK;
 }

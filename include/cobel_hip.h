@@ -450,12 +450,14 @@ enum {
   COBEL_TAB_KERNEL_WPI = 1,       /* one wavefront per instance, every run-time switch          */
   COBEL_TAB_KERNEL_WPI_FAST = 2,  /* ... plain Dyna-Q training, model digest in LDS             */
   COBEL_TAB_KERNEL_WPI_INDEX = 3, /* ... plain Dyna-Q training, model digest in HBM (model_index) */
-  COBEL_TAB_KERNEL_PWG = 5,       /* plain Dyna-Q training, one persistent workgroup of 16 wavefronts
-                                     per CU: some keep Q in LDS, the others work on it in L2; out[1]
-                                     = LDS of the workgroup, out[2] = 1, out[3] = its wavefronts    */
-  COBEL_TAB_KERNEL_WQN = 6,       /* Q-learning on worlds of 1..8 (not four) actions whose tables fit
-                                     the LDS: one wavefront per instance, Q rows padded to eight
-                                     values; out[3] = instances per workgroup                      */
+  COBEL_TAB_KERNEL_PWG = 5,       /* plain Dyna-Q training on worlds of 257 .. 1 024 states, one
+                                     persistent workgroup per CU: as many wavefronts as Q tables fit
+                                     its LDS (ten at 32 x 32); wavefronts that work on Q in global
+                                     memory only with COBEL_F_PWG_GLOBAL and forced mixes; out[1] =
+                                     LDS of the workgroup, out[2] = 1, out[3] = its wavefronts      */
+  COBEL_TAB_KERNEL_WQN = 6,       /* Q-learning on worlds of 1..32 (not four) actions whose tables fit
+                                     the LDS: one wavefront per instance, Q rows padded to 8, 16 or
+                                     32 values; out[3] = instances per workgroup                   */
   COBEL_TAB_KERNEL_GENERAL = 4    /* one lane per instance, tables in HBM: any action count, batch
                                      size and state count                                        */
 };
