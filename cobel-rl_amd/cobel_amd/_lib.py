@@ -21,6 +21,7 @@ AGENT_Q, AGENT_DYNAQ = 0, 1
 F_LEARN, F_NO_REPLAY, F_EPISODIC, F_MASK_ACTIONS, F_TEST_STREAM, F_FORCE_WAVE = 1, 2, 4, 8, 16, 32
 F_FORCE_LDS_MODEL, F_NO_PREFETCH, F_SR_STREAM_ROWS, F_TAB_GENERAL, F_NO_PWG = 64, 128, 256, 512, 1024
 F_PWG_GLOBAL = 2048
+F_SFMA_STREAM = 4096
 TAB_KERNEL_LPI, TAB_KERNEL_WPI, TAB_KERNEL_WPI_FAST, TAB_KERNEL_WPI_INDEX, TAB_KERNEL_GENERAL = range(5)
 TAB_KERNEL_PWG = 5
 TAB_KERNEL_WQN = 6
@@ -276,6 +277,7 @@ _SIGNATURES = {
     'cobel_sr_run': (C.c_int, [_P, C.POINTER(SRRun), _P]),
     'cobel_sr_retrieve_q': (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P]),
     'cobel_sfma_query': (C.c_int, [C.c_int32, C.POINTER(C.c_int32)]),
+    'cobel_sfma_plan': (C.c_int, [C.c_int32, C.c_uint32, C.POINTER(C.c_int32 * 4)]),
     'cobel_sfma_exp_check': (C.c_int, [C.c_void_p] * 6 + [C.c_int32, C.c_void_p]),
     'cobel_sfma_run': (C.c_int, [_P, C.POINTER(SFMARun), _P]),
     'cobel_adam_step': (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int32,

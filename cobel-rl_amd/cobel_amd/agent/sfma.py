@@ -53,6 +53,7 @@ class SFMA(TabularAgent):
         self.keep_replay_trace = False     # collect replayed experiences in `replay_events`
         self.force_general_kernel = False  # testing: skip the specialised kernels
         self.force_one_wave = False        # testing: general kernel with one wave per instance
+        self.force_stream_kernel = False   # testing: the streaming form, also where the LDS form fits
         self.replay_events = []
         self._fired = 0
         self._trace = self._trace_len = self._cdf = self._cdf_key = None
@@ -60,13 +61,18 @@ class SFMA(TabularAgent):
 
     # -- tables ---------------------------------------------------------------------------------
     def _alloc_tables(self) -> None:
-        lds = C.c_int32()
-        _lib.check(_lib.lib().cobel_sfma_query(self.n_states, C.byref(lds)))
+        self._plan(_lib.F_SFMA_STREAM if self.force_stream_kernel else 0)   # refuses > 16 383 states
         self._q = torch.zeros((self.n_envs, self.n_states, 4), dtype=torch.float32,
                               device=self.device)
         self._q.copy_(torch.as_tensor(self._q_host, device=self.device).expand_as(self._q))
         self.M._bind(self.n_envs, self.device)
         self.replays_done = torch.zeros(1, dtype=torch.int64, device=self.device)
+
+    def _plan(self, flags: int) -> None:
+        """``launch_plan``: (form, LDS bytes, threads per instance, scratch bytes — none) of the
+        launch under ``flags``, as ``cobel_sfma_run`` decides it; refreshed by every launch."""
+        self.launch_plan = (C.c_int32 * 4)()
+        _lib.check(_lib.lib().cobel_sfma_plan(self.n_states, flags, C.byref(self.launch_plan)))
 
     @property
     def td(self):
@@ -152,6 +158,7 @@ class SFMA(TabularAgent):
         run.interp_fwd, run.interp_rev = M.interpolation_fwd, M.interpolation_rev
         run.seed = interface.seed
         M._sync_mode()
+        self._plan(flags)
         self.inst[:, _lib.I_CTR_MEMORY] = M.counter
         _lib.check(_lib.lib().cobel_sfma_run(interface.handle.ptr, C.byref(run),
                                              _lib.current_stream(self.device)))
@@ -211,9 +218,11 @@ class SFMA(TabularAgent):
               no_replay: bool = False) -> None:
         extra = (_lib.F_NO_REPLAY if no_replay else 0) | \
                 (_lib.F_FORCE_WAVE if self.force_general_kernel else 0) | \
-                ((_lib.F_FORCE_WAVE | _lib.F_NO_PREFETCH) if self.force_one_wave else 0)
+                ((_lib.F_FORCE_WAVE | _lib.F_NO_PREFETCH) if self.force_one_wave else 0) | \
+                (_lib.F_SFMA_STREAM if self.force_stream_kernel else 0)
         self._session(interface, trials, steps, batch_size, True, extra)
 
     def test(self, interface, trials: int, steps: int) -> None:
         # agent/sfma.py:369: the test loop selects with self.policy
-        self._session(interface, trials, steps, 0, False, pol=self.policy)
+        self._session(interface, trials, steps, 0, False, pol=self.policy,
+                      extra_flags=_lib.F_SFMA_STREAM if self.force_stream_kernel else 0)

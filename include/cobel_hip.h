@@ -304,6 +304,7 @@ enum { COBEL_AGENT_Q = 0, COBEL_AGENT_DYNAQ = 1 };
 #define COBEL_F_NO_PWG 1024u       /* Dyna-Q: never take the persistent-workgroup kernel (testing,
                                       A/B measurements): k_tab_wpi, one workgroup per instance      */
 #define COBEL_F_PWG_GLOBAL 2048u   /* ... its wavefronts ALL work on Q in global memory (testing)          */
+#define COBEL_F_SFMA_STREAM 4096u   /* cobel_sfma_run: always take the streaming form (testing)           */
 #define COBEL_F_SR_STREAM_ROWS 256u /* SR: always take the row-streaming kernel, also where the
                                       sparse-reward kernel applies (testing, A/B measurements)    */
 
@@ -645,8 +646,15 @@ typedef struct {
   uint64_t seed;
 } cobel_sfma_run_t;
 
-/* 0 = supported; fills *lds_bytes with the LDS one instance needs. */
+/* The LDS-resident form: 0 = it serves n_states; fills *lds_bytes with the LDS one instance needs. */
 COBEL_API int cobel_sfma_query(int32_t n_states, int32_t* lds_bytes);
+/* What cobel_sfma_run launches for a world of n_states under `flags` (COBEL_F_*; the ones that
+ * matter are COBEL_F_SFMA_STREAM and COBEL_F_NO_PREFETCH): out = {form (0 LDS-resident, up to
+ * 1 274 states; 1 streaming, tables read where the caller keeps them), LDS bytes per workgroup,
+ * threads per instance, bytes of caller-owned scratch (0: neither form takes any)}.
+ * COBEL_E_RANGE for n_states < 1; COBEL_E_UNSUPPORTED beyond 16 383 states, the largest index the
+ * 15-bit successor field of an experience (NS | flag << 15) holds. */
+COBEL_API int cobel_sfma_plan(int32_t n_states, uint32_t flags, int32_t out[4]);
 COBEL_API int cobel_sfma_run(const cobel_world_t* world, const cobel_sfma_run_t* run, void* stream);
 /* For tests: exp(x[i]) by the routine the plain-training SFMA kernel uses for its softmax weights
  * (arguments in [0, 700], memory/sfma.py:349-372) and by the device library's exp, which every
