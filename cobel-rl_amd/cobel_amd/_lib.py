@@ -207,6 +207,36 @@ class SFMARun(C.Structure):
     ]
 
 
+SFM_ERROR_MOD_LOCAL, SFM_ERROR_MOD, SFM_STRIDED = 1, 2, 4
+
+
+class SFMAExp(C.Structure):
+    """``cobel_sfma_exp_t`` (32 bytes)."""
+    _fields_ = [
+        ('state', C.c_int32), ('action', C.c_int32), ('next_state', C.c_int32),
+        ('nonterminal', C.c_int32), ('reward', C.c_double), ('td', C.c_double),
+    ]
+
+
+class SFMAMem(C.Structure):
+    """``cobel_sfma_mem_t``."""
+    _fields_ = [
+        ('model', C.c_void_p), ('strength', C.c_void_p), ('stamp', C.c_void_p),
+        ('sfma_inst', C.c_void_p), ('metric', C.c_void_p), ('recency_tab', C.c_void_p),
+        ('counter', C.c_void_p),
+        ('n', C.c_int32), ('n_states', C.c_int32), ('n_worlds', C.c_int32),
+        ('recency_len', C.c_int32), ('instance_base', C.c_uint32),
+        ('flags', C.c_uint32), ('sfma_flags', C.c_uint32), ('mem_flags', C.c_uint32),
+        ('model_lr', C.c_double),
+        ('decay_inhibition', C.c_double), ('decay_strength', C.c_double),
+        ('c_step', C.c_double), ('i_step', C.c_double), ('r_threshold', C.c_double),
+        ('beta', C.c_double),
+        ('reward_modulation', C.c_double), ('blend', C.c_double), ('interp_fwd', C.c_double),
+        ('interp_rev', C.c_double),
+        ('seed', C.c_uint64),
+    ]
+
+
 class SRRun(C.Structure):
     """``cobel_sr_run_t``."""
     _fields_ = [
@@ -280,6 +310,11 @@ _SIGNATURES = {
     'cobel_sfma_plan': (C.c_int, [C.c_int32, C.c_uint32, C.POINTER(C.c_int32 * 4)]),
     'cobel_sfma_exp_check': (C.c_int, [C.c_void_p] * 6 + [C.c_int32, C.c_void_p]),
     'cobel_sfma_run': (C.c_int, [_P, C.POINTER(SFMARun), _P]),
+    'cobel_sfma_mem_plan': (C.c_int, [C.c_int32, C.c_uint32, C.POINTER(C.c_int32 * 4)]),
+    'cobel_sfma_store': (C.c_int, [C.POINTER(SFMAMem), _P, _P]),
+    'cobel_sfma_replay': (C.c_int, [C.POINTER(SFMAMem), C.c_int32, C.c_int32, _P, _P, _P, _P, _P,
+                                    _P]),
+    'cobel_sfma_random_batch': (C.c_int, [C.POINTER(SFMAMem), C.c_int32, _P, _P, _P]),
     'cobel_adam_step': (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int32,
                                   C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _P,
                                   C.c_double, _P]),

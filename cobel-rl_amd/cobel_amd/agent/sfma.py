@@ -157,6 +157,8 @@ class SFMA(TabularAgent):
         run.reward_modulation, run.blend = M.reward_modulation, M.blend
         run.interp_fwd, run.interp_rev = M.interpolation_fwd, M.interpolation_rev
         run.seed = interface.seed
+        # (the memory's own methods, called between sessions, go on in this stream)
+        M._session(interface.seed, interface.instance_base, interface.handle.n_worlds)
         M._sync_mode()
         self._plan(flags)
         self.inst[:, _lib.I_CTR_MEMORY] = M.counter
@@ -221,6 +223,17 @@ class SFMA(TabularAgent):
                 ((_lib.F_FORCE_WAVE | _lib.F_NO_PREFETCH) if self.force_one_wave else 0) | \
                 (_lib.F_SFMA_STREAM if self.force_stream_kernel else 0)
         self._session(interface, trials, steps, batch_size, True, extra)
+
+    def replay(self, batch_size: int, state=None) -> list:
+        """agent/sfma.py:392-421 between sessions: a replay of the memory followed by the TD updates
+        of the replayed experiences.  The replay is ``M.replay(batch_size, state)`` — a device call
+        of its own.  The TD updates exist inside the fused kernel only, which picks its replays
+        itself (end of a trial, start of a trial): no combination of its flags applies a given
+        batch, and a second TD kernel is not kept for this."""
+        raise NotImplementedError(
+            'SFMA.replay between sessions: the replay itself is M.replay(batch_size, state) (or '
+            'M.replay_batch); Q is updated from replays inside train() only — call train() for '
+            'replays with TD updates')
 
     def test(self, interface, trials: int, steps: int) -> None:
         # agent/sfma.py:369: the test loop selects with self.policy

@@ -1,8 +1,15 @@
 """Memory module of the SFMA agent — ``cobel.memory.SFMAMemory`` (memory/sfma.py:19-416).
 
-Same constructor and attributes as the reference.  ``store`` / ``replay`` /
-``retrieve_random_batch`` are folded into the fused kernel (``cobel_sfma_run``); this class owns
-the parameters and the device tables:
+Same constructor, attributes and methods as the reference.  Inside ``SFMA.train`` the store and
+the replay are folded into the fused kernel (``cobel_sfma_run``); called on the memory itself,
+``store`` / ``replay`` / ``retrieve_random_batch`` are device calls on the same tables
+(``cobel_sfma_store`` / ``cobel_sfma_replay`` / ``cobel_sfma_random_batch``, csrc/sfma_mem.hip:
+the kernel code of the fused kernel), and ``replay_batch`` runs K independent replays of every
+instance side by side.  A memory is bound to a device by the agent's first session or, without an
+agent, by ``bind``.  The methods draw from the memory stream of the session (seed, instance base)
+at ``counter``, where ``train`` left it and where ``train`` goes on afterwards.
+
+This class owns the parameters and the device tables:
 
   ``table``     packed model records [N, S, 4] (float32 reward estimate, next state, nonterminal),
                 decoded by ``rewards`` / ``states`` / ``terminals``
@@ -11,14 +18,21 @@ the parameters and the device tables:
                 whole recency vector on every store: T[j] = decay_recency ** age, by repeated
                 multiplication, 0 after the end-of-trial reset)
   ``state``     per-instance words: clock, epoch, replay mode, |TD| sum, agent-stream counter
-``I`` (inhibition) only lives inside a replay and is not kept.
+``I`` (inhibition) only lives inside a replay; the one a host-called ``replay`` leaves is kept.
 """
 from __future__ import annotations
+
+import ctypes as C
 
 import numpy as np
 import torch
 
 from .. import _lib
+
+EXPERIENCE = np.dtype([('state', '<i4'), ('action', '<i4'), ('next_state', '<i4'),
+                       ('nonterminal', '<i4'), ('reward', '<f8'), ('td', '<f8')])
+EVENT = np.dtype([('sa', '<u4'), ('next', '<u4'), ('reward', '<f4'), ('trial', '<i4'),
+                  ('td', '<f8')])
 
 
 class SFMAMemory:
@@ -48,8 +62,25 @@ class SFMAMemory:
         self.table = self.strength = self.stamp = self.state = self.counter = None
         self._metric_dev = self._metric_src = None
         self._recency = None
+        # the session the host-called methods draw in: seed, instance base, worlds of the metric
+        self.seed, self.instance_base, self._n_worlds = 0, 0, 1
+        self.launch_flags = 0      # testing: _lib.F_SFMA_STREAM / F_FORCE_WAVE / F_NO_PREFETCH
+        self._inhibition = None
 
     # -- device state ---------------------------------------------------------------------------
+    def bind(self, n_envs: int = 1, device=None, seed: int = 0, instance_base: int = 0) -> None:
+        """Put the tables of ``n_envs`` instances on ``device`` (default: the current GPU) for a
+        memory that is used without an agent; instance i draws from the memory stream of
+        (``seed``, ``instance_base + i``)."""
+        assert self.table is None, 'the memory is bound already'
+        if device is None:
+            device = torch.device('cuda', torch.cuda.current_device())
+        self._bind(n_envs, torch.device(device))
+        self._session(seed, instance_base, 1)
+
+    def _session(self, seed: int, instance_base: int, n_worlds: int) -> None:
+        self.seed, self.instance_base, self._n_worlds = int(seed), int(instance_base), int(n_worlds)
+
     def _bind(self, n_envs: int, device) -> None:
         if self.table is not None:
             return
@@ -150,7 +181,12 @@ class SFMAMemory:
 
     @property
     def I(self):  # noqa: E743
-        return np.zeros(self.nb_states)
+        """The inhibition the last host-called ``replay`` left (of replay 0 for ``replay_batch``);
+        zeros before the first one."""
+        if self._inhibition is None:
+            n = 1 if self.table is None else self.table.shape[0]
+            return self._squeeze(np.zeros((n, self.nb_states)))
+        return self._squeeze(self._inhibition)
 
     @property
     def modes(self):
@@ -161,3 +197,147 @@ class SFMAMemory:
         r, s, t = self._decode()
         return {'state': state, 'action': action, 'reward': r[0, state, action],
                 'next_state': s[0, state, action], 'terminal': t[0, state, action]}
+
+    # -- the reference's methods as device calls (csrc/sfma_mem.hip) ------------------------------
+    def _mem(self, mem_flags: int = 0):
+        assert self.table is not None, \
+            'the memory has no device tables yet: train an agent with it, or call bind()'
+        dev = self.table.device
+        m = _lib.SFMAMem()
+        m.model, m.strength, m.stamp = _lib.ptr(self.table), _lib.ptr(self.strength), _lib.ptr(self.stamp)
+        m.sfma_inst, m.counter = _lib.ptr(self.state), _lib.ptr(self.counter)
+        m.metric = _lib.ptr(self._metric_on(dev, self._n_worlds))
+        sf = 0
+        for flag, on in ((_lib.SF_DETERMINISTIC, self.deterministic), (_lib.SF_RECENCY, self.recency),
+                         (_lib.SF_C_NORMALIZE, self.C_normalize),
+                         (_lib.SF_D_NORMALIZE, self.D_normalize),
+                         (_lib.SF_R_NORMALIZE, self.R_normalize),
+                         (_lib.SF_REWARD_MOD_LOCAL, self.reward_mod_local),
+                         (_lib.SF_REWARD_MOD, self.reward_mod), (_lib.SF_STATE_MOD, self.state_mod)):
+            sf |= flag if on else 0
+        if self.recency:
+            tab = self._recency_table(dev)
+            m.recency_tab, m.recency_len = _lib.ptr(tab), tab.numel()
+        m.n, m.n_states, m.n_worlds = self.table.shape[0], self.nb_states, self._n_worlds
+        m.instance_base = self.instance_base
+        m.flags, m.sfma_flags, m.mem_flags = self.launch_flags, sf, mem_flags
+        m.model_lr = self.learning_rate
+        m.decay_inhibition, m.decay_strength = self.decay_inhibition, self.decay_strength
+        m.c_step, m.i_step = self.C_step, self.I_step
+        m.r_threshold, m.beta = self.R_threshold, self.beta
+        m.reward_modulation, m.blend = self.reward_modulation, self.blend
+        m.interp_fwd, m.interp_rev = self.interpolation_fwd, self.interpolation_rev
+        m.seed = self.seed
+        self._sync_mode()
+        return m, dev
+
+    def launch_plan(self):
+        """(form, LDS bytes, threads per workgroup, streaming tier) of the memory's launches."""
+        out = (C.c_int32 * 4)()
+        _lib.check(_lib.lib().cobel_sfma_mem_plan(self.nb_states, self.launch_flags, C.byref(out)))
+        return list(out)
+
+    def _per_instance(self, value, name: str, limit: int):
+        """None / scalar / [N] -> int32 [N] with -1 for None, range-checked."""
+        n = self.table.shape[0]
+        if value is None:
+            return None
+        a = np.broadcast_to(np.asarray(value, dtype=np.int64), (n,))
+        if ((a < 0) | (a >= limit)).any():
+            raise IndexError('%s outside [0, %d)' % (name, limit))
+        return np.ascontiguousarray(a, dtype=np.int32)
+
+    def store(self, experience: dict) -> None:
+        """memory/sfma.py:195-236.  One experience per instance: with several instances the values
+        of ``experience`` are scalars (the same for all) or [N] arrays.  ``'terminal'`` holds what
+        the reference's agent puts there, 1 - end_trial.  ``'td'`` is read under ``error_mod`` /
+        ``error_mod_local`` only (KeyError without it, as in the reference)."""
+        flags = (_lib.SFM_ERROR_MOD_LOCAL if self.error_mod_local else 0) | \
+                (_lib.SFM_ERROR_MOD if self.error_mod else 0)
+        m, dev = self._mem(flags)
+        n, S = m.n, self.nb_states
+        rec = np.zeros(n, dtype=EXPERIENCE)
+        rec['state'] = self._per_instance(experience['state'], 'state', S)
+        rec['action'] = self._per_instance(experience['action'], 'action', self.nb_actions)
+        rec['next_state'] = self._per_instance(experience['next_state'], 'next_state', S)
+        rec['nonterminal'] = np.broadcast_to(np.asarray(experience['terminal']), (n,)) != 0
+        rec['reward'] = np.broadcast_to(np.asarray(experience['reward'], dtype=np.float64), (n,))
+        if flags:
+            rec['td'] = np.broadcast_to(np.asarray(experience['td'], dtype=np.float64), (n,))
+        exps = torch.as_tensor(rec.view(np.uint8), device=dev)
+        _lib.check(_lib.lib().cobel_sfma_store(C.byref(m), _lib.ptr(exps), _lib.current_stream(dev)))
+
+    def _replay(self, n_replays: int, length: int, state, action, strided: bool):
+        m, dev = self._mem(_lib.SFM_STRIDED if strided else 0)
+        n, S = m.n, self.nb_states
+        assert n_replays >= 1 and length >= 0
+        st = self._per_instance(state, 'current_state', S)
+        ac = self._per_instance(action, 'current_action', self.nb_actions)
+        if st is None and bool((self.strength.clamp(min=0).sum(dim=1) == 0).any()):
+            # P = clip(C) / sum(clip(C)) is 0 / 0: Generator.choice refuses NaN probabilities
+            raise ValueError('probabilities contain NaN')
+        st_d = None if st is None else torch.as_tensor(st, device=dev)
+        ac_d = None if ac is None else torch.as_tensor(ac, device=dev)
+        events = torch.zeros((n, n_replays, max(length, 1) * _lib.SFMA_EVENT_BYTES),
+                             dtype=torch.uint8, device=dev)
+        lengths = torch.zeros((n, n_replays), dtype=torch.int32, device=dev)
+        inhibition = torch.zeros((n, S), dtype=torch.float64, device=dev)
+        _lib.check(_lib.lib().cobel_sfma_replay(
+            C.byref(m), n_replays, length, _lib.ptr(st_d), _lib.ptr(ac_d), _lib.ptr(events),
+            _lib.ptr(lengths), _lib.ptr(inhibition), _lib.current_stream(dev)))
+        self._inhibition = inhibition.cpu().numpy()
+        ev = events.cpu().numpy().view(EVENT).reshape(n, n_replays, max(length, 1))[:, :, :length]
+        return ev, lengths.cpu().numpy()
+
+    @staticmethod
+    def _experiences(ev) -> list:
+        """Event records -> the reference's experience dicts (reward: the float32 table entry)."""
+        sa = ev['sa'].astype(np.int64)
+        return [{'state': int(s & 0xFFFF), 'action': int((s >> 16) & 0xFF), 'reward': r,
+                 'next_state': int(ns), 'terminal': int((s >> 24) & 1)}
+                for s, r, ns in zip(sa, ev['reward'], ev['next'])]
+
+    def replay(self, replay_length: int, current_state=None, current_action=None) -> list:
+        """memory/sfma.py:238-347: one replay per instance, drawing what the reference draws.  A
+        list of experience dicts; one such list per instance when there are several (``current_*``
+        are then scalars or [N] arrays)."""
+        ev, lens = self._replay(1, replay_length, current_state, current_action, False)
+        out = [self._experiences(ev[i, 0, :lens[i, 0]]) for i in range(ev.shape[0])]
+        return out[0] if len(out) == 1 else out
+
+    def replay_batch(self, n_replays: int, replay_length: int, current_state=None,
+                     current_action=None) -> dict:
+        """``n_replays`` independent replays of every instance from the memory as it stands, side by
+        side on the device.  Replay k draws from index ``counter + k * (replay_length + 2)`` of the
+        memory stream; the counter advances by ``n_replays * (replay_length + 2)``.  Arrays
+        ``state`` / ``action`` / ``reward`` / ``next_state`` / ``terminal`` [N, K, L] (valid up to
+        ``length`` [N, K]; -1 / NaN behind it)."""
+        ev, lens = self._replay(n_replays, replay_length, current_state, current_action, True)
+        sa = ev['sa'].astype(np.int64)
+        live = np.arange(replay_length)[None, None, :] < lens[:, :, None]
+        fill = lambda a, v: np.where(live, a, v)      # noqa: E731
+        return {'state': fill(sa & 0xFFFF, -1), 'action': fill((sa >> 16) & 0xFF, -1),
+                'reward': fill(ev['reward'], np.float32(np.nan)),
+                'next_state': fill(ev['next'].astype(np.int64), -1),
+                'terminal': fill((sa >> 24) & 1, -1), 'length': lens.astype(np.int64)}
+
+    def retrieve_random_batch(self, number_of_experiences: int, mask) -> list:
+        """memory/sfma.py:375-416: uniform draws over the unmasked experiences (one vector draw of
+        the memory stream)."""
+        m, dev = self._mem()
+        n4 = self.nb_states * self.nb_actions
+        probs = np.ones(n4) * np.asarray(mask).astype(int)
+        assert probs.shape == (n4,), 'mask: one entry per experience, index a * S + s'
+        probs /= np.sum(probs)
+        if np.isnan(probs).any():
+            raise ValueError('probabilities contain NaN')
+        cdf = np.cumsum(probs)
+        cdf /= cdf[-1]
+        cdf_d = torch.as_tensor(cdf, device=dev)
+        k = int(number_of_experiences)
+        events = torch.zeros((m.n, max(k, 1) * _lib.SFMA_EVENT_BYTES), dtype=torch.uint8, device=dev)
+        _lib.check(_lib.lib().cobel_sfma_random_batch(C.byref(m), k, _lib.ptr(cdf_d),
+                                                      _lib.ptr(events), _lib.current_stream(dev)))
+        ev = events.cpu().numpy().view(EVENT).reshape(m.n, max(k, 1))[:, :k]
+        out = [self._experiences(ev[i]) for i in range(m.n)]
+        return out[0] if len(out) == 1 else out

@@ -26,6 +26,20 @@ struct sfma_args {
   uint32_t big_lds;   // kBigNsInLds | kBigRowsInLds
 };
 
+// The memory's own calls (sfma_mem.hip: cobel_sfma_store, cobel_sfma_replay) run the same body
+// with MEM = 1 (one store per instance) or MEM = 2 (one replay per workgroup, n_replays workgroups
+// per instance); `r` then carries the memory's tables and parameters only.
+struct sfma_mem_args {
+  const cobel_sfma_exp_t* exps;   // MEM 1: [N] the experience to store
+  uint32_t* counter;              // [N] next index on the memory stream
+  const int32_t* start_state;     // MEM 2: [N] or NULL; < 0: drawn from the clipped strengths
+  const int32_t* start_action;    // MEM 2: [N] or NULL; < 0: drawn
+  int32_t* lengths;               // MEM 2: [N][n_replays] reactivations of each replay
+  double* inhibition;             // MEM 2: [N][S] or NULL, I as replay 0 leaves it
+  int32_t n_replays;
+  uint32_t mem_flags;             // COBEL_SFM_*
+};
+
 constexpr uint32_t kBigNsInLds = 1u;     // NS, the model's successor of every experience
 constexpr uint32_t kBigRowsInLds = 2u;   // Dc, Dn, the two similarity rows of a reactivation
 
@@ -251,10 +265,17 @@ __device__ __forceinline__ double exp_in_range(double x) {
 // workgroup share one vector L1, and every hand-over between threads already has its barrier);
 // the priority vector P has no home, so the passes after the first rate their experiences again
 // — the same operations in the same order, hence the same float64 values.
-template <int CH, int NW, bool FAST = false, bool BIG = false>
-__device__ __forceinline__ void sfma_body(const sfma_args A) {
+// MEM (with CH = 0): SFMAMemory's methods as calls of their own, on the store and the replay of the
+// agent's kernel: 1 stores M.exps[i] in instance i and ends; 2 runs one replay of A.r.batch
+// reactivations in workgroup (instance, replay) without writing any table of the memory — the
+// strengths and the model are read (LDS copy, or in place in the streaming form), inhibition and
+// priorities are the workgroup's own — and reports its events, its length and, for replay 0, I.
+template <int CH, int NW, bool FAST = false, bool BIG = false, int MEM = 0>
+__device__ __forceinline__ void sfma_body(const sfma_args A,
+                                          const sfma_mem_args M = sfma_mem_args{}) {
   static_assert(CH == 0 || NW == 1, "the register path is one wave per instance");
   static_assert(!BIG || (CH == 0 && !FAST), "the streaming form is the general path");
+  static_assert(MEM == 0 || (CH == 0 && !FAST), "the memory's calls take the general path");
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   constexpr int NT = 64 * NW;
   constexpr int RS = NW > 8 ? NW : 8;   // entries per slot of the cross-wave scratch
@@ -266,7 +287,9 @@ __device__ __forceinline__ void sfma_body(const sfma_args A) {
   const sfma_lds L = BIG ? carve_big(lds_raw, S, A.big_lds)
                          : (FAST ? carve(lds_raw, kFastStates) : carve(lds_raw, S));
   const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int i = (int)blockIdx.x;
+  // (MEM 2: workgroup b serves replay b % n_replays of instance b / n_replays)
+  const int i = MEM == 2 ? (int)blockIdx.x / M.n_replays : (int)blockIdx.x;
+  const int rk = MEM == 2 ? (int)blockIdx.x - i * M.n_replays : 0;
   int slot = 0;   // rotating scratch slot: one barrier per cross-wave reduction
   auto bsync = [&]() {
     if (NW == 1) wsync();
@@ -468,7 +491,7 @@ __device__ __forceinline__ void sfma_body(const sfma_args A) {
   };
 
   for (int e = t; e < S; e += NT) {
-    if (!BIG) L.Q[e] = reinterpret_cast<const float4*>(Qg)[e];
+    if (!BIG && !MEM) L.Q[e] = reinterpret_cast<const float4*>(Qg)[e];
     L.I[e] = 0.0;
   }
   if (t < 48) L.thr[t] = A.eps_thr[t / 3][t % 3];
@@ -493,17 +516,21 @@ __device__ __forceinline__ void sfma_body(const sfma_args A) {
     }
   bsync();
 
-  int32_t* const inst = A.r.inst + (size_t)i * COBEL_I_WORDS;
+  // (MEM: there is no agent; the memory stream continues at M.counter[i], replay rk of a strided
+  //  call at its own place (L + 2) * rk behind it — the most one replay can consume)
+  int32_t* const inst = MEM ? nullptr : A.r.inst + (size_t)i * COBEL_I_WORDS;
   int32_t* const sinst = A.r.sfma_inst + (size_t)i * COBEL_SI_WORDS;
-  int state = inst[COBEL_I_STATE];
-  int step = inst[COBEL_I_STEP];
-  int trial = inst[COBEL_I_TRIAL];
-  uint32_t ce = (uint32_t)inst[COBEL_I_CTR_ENV];
-  uint32_t cp = (uint32_t)inst[COBEL_I_CTR_POLICY];
-  uint32_t cm = (uint32_t)inst[COBEL_I_CTR_MEMORY];
-  uint32_t iflags = (uint32_t)inst[COBEL_I_FLAGS];
-  double trew = *reinterpret_cast<const double*>(inst + COBEL_I_REWARD_LO);
-  unsigned long long nsteps = *reinterpret_cast<const unsigned long long*>(inst + COBEL_I_STEPS_LO);
+  int state = MEM ? 0 : inst[COBEL_I_STATE];
+  int step = MEM ? 0 : inst[COBEL_I_STEP];
+  int trial = MEM ? 0 : inst[COBEL_I_TRIAL];
+  uint32_t ce = MEM ? 0u : (uint32_t)inst[COBEL_I_CTR_ENV];
+  uint32_t cp = MEM ? 0u : (uint32_t)inst[COBEL_I_CTR_POLICY];
+  uint32_t cm = MEM ? M.counter[i] + (uint32_t)rk * (uint32_t)(A.r.batch + 2)
+                    : (uint32_t)inst[COBEL_I_CTR_MEMORY];
+  uint32_t iflags = MEM ? 0u : (uint32_t)inst[COBEL_I_FLAGS];
+  double trew = MEM ? 0.0 : *reinterpret_cast<const double*>(inst + COBEL_I_REWARD_LO);
+  unsigned long long nsteps =
+      MEM ? 0ull : *reinterpret_cast<const unsigned long long*>(inst + COBEL_I_STEPS_LO);
   uint32_t clock = (uint32_t)sinst[COBEL_SI_CLOCK];
   uint32_t epoch = (uint32_t)sinst[COBEL_SI_EPOCH];
   int mode = sinst[COBEL_SI_MODE];
@@ -518,8 +545,8 @@ __device__ __forceinline__ void sfma_body(const sfma_args A) {
       (flags & COBEL_F_TEST_STREAM) ? COBEL_STREAM_POLICY_TEST : COBEL_STREAM_POLICY;
   const uint8_t* const amask = (flags & COBEL_F_MASK_ACTIONS) ? A.r.action_mask : nullptr;
   const uint64_t seed = A.r.seed;
-  const int start_lo = A.start_off[world];
-  const uint32_t start_cnt = (uint32_t)(A.start_off[world + 1] - start_lo);
+  const int start_lo = MEM ? 0 : A.start_off[world];
+  const uint32_t start_cnt = MEM ? 1u : (uint32_t)(A.start_off[world + 1] - start_lo);
   // Everything in this kernel is wave-uniform, so the compiler wants it all in scalar registers
   // and then spills (1 300 of 3 000 vector instructions were v_readlane / v_writelane).  Constants
   // that only feed vector arithmetic are pinned to vector registers instead.
@@ -605,18 +632,75 @@ __device__ __forceinline__ void sfma_body(const sfma_args A) {
       ev.reward = R;
       ev.trial = tr;
       ev.td = td;
-      A.r.replay_trace[(size_t)i * A.r.trace_cap + tpos] = ev;
+      // (MEM 2: one row of the trace per replay)
+      A.r.replay_trace[(size_t)(MEM == 2 ? (int)blockIdx.x : i) * A.r.trace_cap + tpos] = ev;
     }
     tpos += 1;
+  };
+
+  // M.store (memory/sfma.py:204-236) of the experience (state, a, r, ns, nt); rd: the reward as the
+  // strength modulation takes it, td: the error the error modulation takes (MEM 1 only)
+  auto mem_store = [&](int state, int a, int ns, uint32_t nt, float r, double rd, double td) {
+    const int sa = state * 4 + a, j = a * S + state;
+    const float Rold = ld_r(j);
+    const float d = r - Rold;
+    const float Rnew = Rold + mlr_f * d;
+    if (t == 0) {
+      Mg[sa] = cobel_model_pack(Rnew, (uint32_t)ns, nt);   // written through
+      if (!BIG) L.R[j] = Rnew;
+      if (ns_lds) L.NS[j] = (uint16_t)((uint32_t)ns | (nt << 15));
+    }
+    if (!FAST && A.r.decay_strength != 1.0) {
+      for (int e = t; e < n4; e += NT) st_c(e, ld_c(e) * A.r.decay_strength);
+      bsync();
+    }
+    clock += 1u;
+    if (t == 0) {
+      double c = ld_c(j) + A.r.c_step;
+      if (!FAST && (sf & COBEL_SF_REWARD_MOD_LOCAL)) c = c + rd * A.r.reward_modulation;
+      st_c(j, c);
+      stamp[j] = clock;
+    }
+    if (!FAST && (sf & COBEL_SF_REWARD_MOD)) {
+      bsync();
+      const double* const row = Dm + (size_t)state * S;
+      for (int e = t; e < n4; e += NT) {
+        const int s2 = e % S;
+        st_c(e, ld_c(e) + (rd * row[s2]) * A.r.reward_modulation);
+      }
+    }
+    if constexpr (MEM == 1) {
+      // error modulation (:225-233): this experience, then every experience by its similarity to
+      // the successor
+      if (M.mem_flags & COBEL_SFM_ERROR_MOD_LOCAL) {
+        bsync();
+        if (t == 0) st_c(j, ld_c(j) + fabs(td));
+      }
+      if (M.mem_flags & COBEL_SFM_ERROR_MOD) {
+        bsync();
+        const double* const row = Dm + (size_t)ns * S;
+        for (int e = t; e < n4; e += NT) st_c(e, ld_c(e) + fabs(td) * row[e % S]);
+      }
+    }
+    if (!FAST && (sf & COBEL_SF_STATE_MOD)) {
+      bsync();
+      if (t < 4) st_c(t * S + state, ld_c(t * S + state) + 1.0);
+    }
   };
 
   // SFMAMemory.replay (memory/sfma.py:238-347) [+ the TD updates of SFMA.replay when `update`]
   // (the kernels with experiences in registers are launched without the normalisation switches)
   const bool c_norm = CH == 0 && (sf & COBEL_SF_C_NORMALIZE);
   const bool d_norm = CH == 0 && (sf & COBEL_SF_D_NORMALIZE);
+  const int mem_action = (MEM == 2 && M.start_action) ? M.start_action[i] : -1;
   auto sfma_replay = [&](int start_state, bool update, int kind, int tr) {
-    int action = (int)cobel_draw_bounded(cm, 0u, g, COBEL_STREAM_MEMORY, seed, 4u);
-    cm += 1u;
+    int action;
+    if (MEM == 2 && mem_action >= 0) {
+      action = mem_action;   // current_action given: no integer is drawn (:261-264)
+    } else {
+      action = (int)cobel_draw_bounded(cm, 0u, g, COBEL_STREAM_MEMORY, seed, 4u);
+      cm += 1u;
+    }
     int cur = start_state;
     const int j0 = t * chunk;
     if (cur < 0) {
@@ -959,8 +1043,28 @@ __device__ __forceinline__ void sfma_body(const sfma_args A) {
   //  with `continue`s every scalar of either phase was live across every iteration: the online step
   //  reloaded ~140 spilled scalars — v_readlane, a vector instruction on a kernel bound by vector
   //  issue.)
+  if constexpr (MEM == 1) {
+    // (an experience outside the tables is refused by the callers; here it is left out)
+    const cobel_sfma_exp_t x = M.exps[i];
+    if ((uint32_t)x.state < (uint32_t)S && (uint32_t)x.action < 4u &&
+        (uint32_t)x.next_state < (uint32_t)S)
+      mem_store(x.state, x.action, x.next_state, x.nonterminal ? 1u : 0u, (float)x.reward,
+                x.reward, x.td);
+  }
+  if constexpr (MEM == 2) {
+    const int s0 = M.start_state ? M.start_state[i] : -1;
+    if (s0 < S && mem_action < 4) sfma_replay(s0, false, 0, 0);
+    if (t == 0) {
+      M.lengths[blockIdx.x] = tpos;
+      // a single replay advances the stream by what it drew (a strided call by its whole stride,
+      // once every replay has read the counter: cobel_sfma_replay)
+      if (!(M.mem_flags & COBEL_SFM_STRIDED)) M.counter[i] = cm;
+    }
+    if (M.inhibition && rk == 0)
+      for (int e = t; e < S; e += NT) M.inhibition[(size_t)i * S + e] = L.I[e];
+  }
   int req_count = 0, req_start = -1, req_kind = 0, req_trial = 0;
-  while (true) {
+  while (MEM == 0) {
     while (req_count > 0) {
       req_count -= 1;
       if (!FAST && req_kind == 0 && (sf & COBEL_SF_RANDOM)) random_replay(req_trial);
@@ -1027,39 +1131,8 @@ __device__ __forceinline__ void sfma_body(const sfma_args A) {
     float td_online = 0.0f;
 
     if (learn) {
-      const int sa = state * 4 + a, j = a * S + state;
-      // M.store (memory/sfma.py:204-236)
-      const float Rold = ld_r(j);
-      const float d = r - Rold;
-      const float Rnew = Rold + mlr_f * d;
-      if (t == 0) {
-        Mg[sa] = cobel_model_pack(Rnew, (uint32_t)ns, nt);   // written through
-        if (!BIG) L.R[j] = Rnew;
-        if (ns_lds) L.NS[j] = (uint16_t)((uint32_t)ns | (nt << 15));
-      }
-      if (!FAST && A.r.decay_strength != 1.0) {
-        for (int e = t; e < n4; e += NT) st_c(e, ld_c(e) * A.r.decay_strength);
-        bsync();
-      }
-      clock += 1u;
-      if (t == 0) {
-        double c = ld_c(j) + A.r.c_step;
-        if (!FAST && (sf & COBEL_SF_REWARD_MOD_LOCAL)) c = c + (double)r * A.r.reward_modulation;
-        st_c(j, c);
-        stamp[j] = clock;
-      }
-      if (!FAST && (sf & COBEL_SF_REWARD_MOD)) {
-        bsync();
-        const double* const row = Dm + (size_t)state * S;
-        for (int e = t; e < n4; e += NT) {
-          const int s2 = e % S;
-          st_c(e, ld_c(e) + ((double)r * row[s2]) * A.r.reward_modulation);
-        }
-      }
-      if (!FAST && (sf & COBEL_SF_STATE_MOD)) {
-        bsync();
-        if (t < 4) st_c(t * S + state, ld_c(t * S + state) + 1.0);
-      }
+      const int sa = state * 4 + a;
+      mem_store(state, a, ns, nt, r, (double)r, 0.0);
       // agent.update_q online (agent/sfma.py:437-455), float32
       const float4 nrow = ld_q4(ns);
       const float m = max4_masked(nrow, amask ? (uint32_t)amask[ns] & 15u : 15u);
@@ -1138,10 +1211,13 @@ __device__ __forceinline__ void sfma_body(const sfma_args A) {
 
   bsync();
   if (!BIG) {
-    for (int e = t; e < S; e += NT) reinterpret_cast<float4*>(Qg)[e] = L.Q[e];
-    for (int e = t; e < n4; e += NT) Cg[e] = L.C[e];
+    if (!MEM)
+      for (int e = t; e < S; e += NT) reinterpret_cast<float4*>(Qg)[e] = L.Q[e];
+    if (MEM != 2)
+      for (int e = t; e < n4; e += NT) Cg[e] = L.C[e];
   }
-  if (t == 0) {
+  if (MEM == 1 && t == 0) sinst[COBEL_SI_CLOCK] = (int32_t)clock;
+  if (!MEM && t == 0) {
     inst[COBEL_I_STATE] = state;
     inst[COBEL_I_STEP] = step;
     inst[COBEL_I_TRIAL] = trial;

@@ -666,6 +666,85 @@ COBEL_API int cobel_sfma_exp_check(const double* x, double* in_range, double* li
                                    double* quotient, int32_t n, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * SFMAMemory on its own: store / replay / retrieve_random_batch (memory/sfma.py:195-416) as calls
+ * on the tables cobel_sfma_run keeps, for N instances, without an agent.  The kernels are the
+ * store and the replay of cobel_sfma_run (the same code, in its general form), so a store writes
+ * the bits the agent's kernel writes and a replay reactivates what the agent's replay would.
+ *
+ * Draws.  The memory stream is the one cobel_sfma_run uses: COBEL_STREAM_MEMORY of instance
+ * instance_base + i at index counter[i], integers on sub-stream 0, doubles on sub-stream 1 (a
+ * NumPy Generator stand-in TapeRNG(seed, g, STREAM_MEMORY, start = counter, double_sub = 1)).
+ *   - a single replay (n_replays = 1, no COBEL_SFM_STRIDED) consumes what the reference consumes —
+ *     one integer unless the action is given, one double if the state is drawn, one double per
+ *     reactivation unless deterministic — and advances counter[i] by that many;
+ *   - COBEL_SFM_STRIDED: replay k starts at counter[i] + k * (replay_length + 2), the most one replay
+ *     can consume, and the call advances counter[i] by n_replays * (replay_length + 2): replay k is
+ *     what a reference memory in the same state produces with its generator positioned there;
+ *   - a random batch of any size is one vector draw: doubles at index counter[i], sub-streams
+ *     1, 2, ...; counter[i] advances by one.
+ * ------------------------------------------------------------------------------------------ */
+#define COBEL_SFM_ERROR_MOD_LOCAL 1u  /* M.error_mod_local: C[j] += |td|                             */
+#define COBEL_SFM_ERROR_MOD 2u        /* M.error_mod: C += |td| * tile(D[next_state])                */
+#define COBEL_SFM_STRIDED 4u          /* cobel_sfma_replay: one stride of the stream per replay      */
+
+/* One experience handed to cobel_sfma_store, 32 bytes. */
+typedef struct {
+  int32_t state, action, next_state;
+  int32_t nonterminal;    /* experience['terminal'] (the reference stores 1 - end_trial there)  */
+  double reward;          /* rounded to float32 for the model's estimate, as given for C        */
+  double td;              /* read under COBEL_SFM_ERROR_MOD_LOCAL / COBEL_SFM_ERROR_MOD only    */
+} cobel_sfma_exp_t;
+
+typedef struct {
+  /* tables, caller-owned device memory, as in cobel_sfma_run_t */
+  uint64_t* model;        /* [N][S][4]                                                        */
+  double* strength;       /* [N][4S]                                                          */
+  uint32_t* stamp;        /* [N][4S]                                                          */
+  int32_t* sfma_inst;     /* [N][COBEL_SI_WORDS]: clock, epoch and mode are used              */
+  const double* metric;   /* [n_worlds][S][S]; instance g uses world g % n_worlds             */
+  const double* recency_tab; /* [recency_len], needed under COBEL_SF_RECENCY                  */
+  uint32_t* counter;      /* [N] next index on the memory stream, in/out                      */
+  int32_t n, n_states, n_worlds, recency_len;
+  uint32_t instance_base;
+  uint32_t flags;         /* COBEL_F_SFMA_STREAM | COBEL_F_FORCE_WAVE | COBEL_F_NO_PREFETCH, as
+                             cobel_sfma_plan reads them                                        */
+  uint32_t sfma_flags;    /* COBEL_SF_*: the switches of the memory                            */
+  uint32_t mem_flags;     /* COBEL_SFM_*                                                       */
+  double model_lr;        /* M.learning_rate                                                   */
+  double decay_inhibition, decay_strength;
+  double c_step, i_step, r_threshold, beta;
+  double reward_modulation, blend, interp_fwd, interp_rev;
+  uint64_t seed;
+} cobel_sfma_mem_t;
+
+/* What the memory's calls launch for n_states under `flags`: out = {form (0 LDS-resident, 1
+ * streaming), LDS bytes per workgroup, threads per workgroup, what the streaming form keeps in
+ * LDS besides I (bit 0 the successor table, bit 1 the two similarity rows)}.  The form, the LDS
+ * and its tiers are cobel_sfma_plan's; a workgroup is one instance (store) or one replay. */
+COBEL_API int cobel_sfma_mem_plan(int32_t n_states, uint32_t flags, int32_t out[4]);
+/* M.store(experiences[i]) in every instance i: model record, C *= decay_strength, C[j] += C_step,
+ * stamp and clock, reward / error / state modulation.  experiences: [dev] [N]. */
+COBEL_API int cobel_sfma_store(const cobel_sfma_mem_t* mem, const cobel_sfma_exp_t* experiences,
+                               void* stream);
+/* n_replays independent replays of replay_length reactivations in every instance, side by side.
+ * Reads the memory only (strengths, stamps, model records); writes counter (see above) and
+ *   events     [dev] [N][n_replays][replay_length], td = NaN, trial = 0, kind = 0
+ *   lengths    [dev] [N][n_replays] reactivations before the ratings ran out
+ *   inhibition [dev] [N][S] or NULL: M.I as replay 0 of each instance leaves it
+ * start_state / start_action: [dev] [N] or NULL; an entry < 0 (or NULL) means None: the start is
+ * drawn from the clipped strengths, the action is drawn. */
+COBEL_API int cobel_sfma_replay(const cobel_sfma_mem_t* mem, int32_t n_replays,
+                                int32_t replay_length, const int32_t* start_state,
+                                const int32_t* start_action, cobel_sfma_event_t* events,
+                                int32_t* lengths, double* inhibition, void* stream);
+/* M.retrieve_random_batch: n_experiences draws per instance through random_cdf ([dev] [4S],
+ * cumsum(p) / cumsum(p)[-1] of the masked uniform p as in cobel_sfma_run_t); events [dev]
+ * [N][n_experiences] as above. */
+COBEL_API int cobel_sfma_random_batch(const cobel_sfma_mem_t* mem, int32_t n_experiences,
+                                      const double* random_cdf, cobel_sfma_event_t* events,
+                                      void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Fused Adam step for network parameters stacked over instances (the DQN path keeps one network
  * per agent-env instance, parameters [N][...] per tensor).  Replaces optimizer.step() behind
  * TorchNetwork.train_on_batch (network/network_torch.py:160-167) for torch.optim.Adam without
