@@ -22,6 +22,9 @@ F_LEARN, F_NO_REPLAY, F_EPISODIC, F_MASK_ACTIONS, F_TEST_STREAM, F_FORCE_WAVE = 
 F_FORCE_LDS_MODEL, F_NO_PREFETCH, F_SR_STREAM_ROWS, F_TAB_GENERAL, F_NO_PWG = 64, 128, 256, 512, 1024
 F_PWG_GLOBAL = 2048
 F_SFMA_STREAM = 4096
+F_REPLAY_LANE = 8192
+REPLAY_WAVE, REPLAY_LANE = 0, 1
+UPDATE_ONLINE, UPDATE_PLANNING = 0, 1
 TAB_KERNEL_LPI, TAB_KERNEL_WPI, TAB_KERNEL_WPI_FAST, TAB_KERNEL_WPI_INDEX, TAB_KERNEL_GENERAL = range(5)
 TAB_KERNEL_PWG = 5
 TAB_KERNEL_WQN = 6
@@ -166,6 +169,14 @@ class TabRun(C.Structure):
     ]
 
 
+class TabExp(C.Structure):
+    """``cobel_tab_exp_t`` (24 bytes)."""
+    _fields_ = [
+        ('state', C.c_int32), ('action', C.c_int32), ('next_state', C.c_int32),
+        ('nonterminal', C.c_int32), ('reward', C.c_float), ('reserved_', C.c_int32),
+    ]
+
+
 def tab_scratch_bytes(n: int) -> int:
     """``COBEL_TAB_SCRATCH_BYTES(n)``."""
     return (256 + 7 * (int(n) + 8)) * 4
@@ -297,6 +308,11 @@ _SIGNATURES = {
     'cobel_q_run': (C.c_int, [_P, C.POINTER(TabRun), _P]),
     'cobel_tab_describe': (C.c_int, [_P, C.POINTER(TabRun), C.POINTER(C.c_int32)]),
     'cobel_tab_scratch_check': (C.c_int, [_P, C.c_int64, _P]),
+    'cobel_dynaq_replay': (C.c_int, [_P, C.POINTER(TabRun), C.c_int32, _P]),
+    'cobel_dynaq_replay_plan': (C.c_int, [_P, C.POINTER(TabRun), C.c_int32,
+                                          C.POINTER(C.c_int32 * 4)]),
+    'cobel_dynaq_update': (C.c_int, [_P, C.POINTER(TabRun), _P, C.c_uint32, _P, _P]),
+    'cobel_model_store': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_double, _P]),
     'cobel_pack_model': (C.c_uint64, [C.c_float, C.c_uint16, C.c_uint8]),
     'cobel_unpack_model': (None, [C.c_uint64, C.POINTER(C.c_float), C.POINTER(C.c_uint16),
                                   C.POINTER(C.c_uint8)]),

@@ -7,7 +7,8 @@ On device the model is one packed 8-byte record per (state, action):
 (cobel_tab_run); the methods here serve single host-side calls (memory/dyna_q.py:77-157) on one
 instance and go through the same device table, the same float32 arithmetic and the same memory
 stream (counter ``counter[instance]``, one vector draw per batch) as the kernel, so host calls and
-launches can be interleaved freely.
+launches can be interleaved freely.  ``store_batch`` is ``store`` for all instances in one launch
+(cobel_model_store).
 """
 from __future__ import annotations
 
@@ -15,6 +16,47 @@ import numpy as np
 import torch
 
 from .. import _lib
+
+
+def _is_array(v) -> bool:
+    return (torch.is_tensor(v) and v.dim() > 0) or (not torch.is_tensor(v) and np.ndim(v) > 0)
+
+
+def pack_experiences(experience: dict, n: int, n_states: int, device):
+    """``cobel_tab_exp_t [n]`` on ``device`` (int32 ``[n, 6]``) from an experience dictionary whose
+    values are scalars (every instance gets the same) or ``[n]`` arrays / tensors.  ``state < 0``
+    marks an instance without an experience; any other pair outside the tables is an
+    ``IndexError`` (values given as device tensors are not read back: the kernels skip such
+    entries).  The reward is rounded to float32, the type of the tables."""
+    keys = ('state', 'action', 'next_state', 'terminal', 'reward')
+    vals = [experience[k] for k in keys]
+    if any(torch.is_tensor(v) for v in vals):
+        out = torch.zeros((n, 6), dtype=torch.int32, device=device)
+        for col, v in enumerate(vals):
+            v = torch.as_tensor(v, device=device)
+            if col == 4:
+                out[:, col] = v.to(torch.float32).expand(n).contiguous().view(torch.int32)
+            elif col == 3:
+                out[:, col] = (v != 0).to(torch.int32).expand(n)
+            else:
+                out[:, col] = v.to(torch.int32).expand(n)
+        return out
+    host = np.zeros((n, 6), dtype=np.int32)
+    for col, v in enumerate(vals):
+        v = np.asarray(v)
+        assert v.ndim == 0 or v.shape == (n,), \
+            'experience values are scalars or one entry per instance (%d)' % n
+        if col == 4:
+            host[:, col] = np.broadcast_to(v.astype(np.float32), (n,)).view(np.int32)
+        elif col == 3:
+            host[:, col] = np.broadcast_to(v != 0, (n,))
+        else:
+            host[:, col] = np.broadcast_to(v.astype(np.int64), (n,))
+    on = host[:, 0] >= 0
+    if (host[on, 0] >= n_states).any() or (host[on, 2] < 0).any() or \
+            (host[on, 2] >= n_states).any() or (host[on, 1] < 0).any() or (host[on, 1] >= 4).any():
+        raise IndexError('experience outside the tables (%d states, 4 actions)' % n_states)
+    return torch.as_tensor(host, device=device)
 
 
 class DynaQMemory:
@@ -98,6 +140,18 @@ class DynaQMemory:
         digest = (int(experience['next_state']) & 0x3FFF) | (int(bool(experience['terminal'])) << 14) \
             | (0x8000 if np.float32(new).view(np.uint32) != 0 else 0)
         self.index[instance, s, a] = digest - (1 << 16) if digest >= (1 << 15) else digest
+
+    def store_batch(self, experience: dict) -> None:
+        """``store`` in every instance at once (memory/dyna_q.py:77-96, one launch of
+        cobel_model_store, no synchronisation): the values of ``experience`` are scalars or ``[N]``
+        arrays / device tensors, ``state < 0`` leaves an instance as it is.  Same float32
+        arithmetic and digest as ``store`` and as the fused kernel's step."""
+        self._bind()
+        n = self.table.shape[0]
+        exps = pack_experiences(experience, n, self.number_of_states, self.table.device)
+        _lib.check(_lib.lib().cobel_model_store(
+            _lib.ptr(self.table), _lib.ptr(self.index), n, self.number_of_states, _lib.ptr(exps),
+            float(self.learning_rate), _lib.current_stream(self.table.device)))
 
     def retrieve(self, state: int, action: int, instance: int = 0) -> dict:
         self._bind()

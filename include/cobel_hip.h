@@ -305,6 +305,7 @@ enum { COBEL_AGENT_Q = 0, COBEL_AGENT_DYNAQ = 1 };
                                       A/B measurements): k_tab_wpi, one workgroup per instance      */
 #define COBEL_F_PWG_GLOBAL 2048u   /* ... its wavefronts ALL work on Q in global memory (testing)          */
 #define COBEL_F_SFMA_STREAM 4096u   /* cobel_sfma_run: always take the streaming form (testing)           */
+#define COBEL_F_REPLAY_LANE 8192u   /* cobel_dynaq_replay: always take the lane form (testing)           */
 #define COBEL_F_SR_STREAM_ROWS 256u /* SR: always take the row-streaming kernel, also where the
                                       sparse-reward kernel applies (testing, A/B measurements)    */
 
@@ -495,6 +496,59 @@ COBEL_API int cobel_model_init(uint64_t* model /* [dev] [N][S][4] */, int32_t n,
 COBEL_API int cobel_model_index_build(const uint64_t* model /* [dev] [N][S][4] */,
                                       uint16_t* index /* [dev] [N][S][4] */, int32_t n,
                                       int32_t n_states, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Dyna-Q between sessions.  The reference's DynaQ is a loop over three public calls —
+ * M.store(experience), update_q(experience), replay(batch_size) (agent/dyna_q.py:193-211) — which
+ * users also call themselves, to plan between trials or between sessions.  These are those calls
+ * for N instances on the tables cobel_tab_run keeps (same run struct), in stream order with it.
+ * ------------------------------------------------------------------------------------------ */
+/* One experience per instance, 24 bytes.  state < 0: the instance has none (left untouched). */
+typedef struct {
+  int32_t state, action, next_state;
+  int32_t nonterminal;    /* experience['terminal'] (the reference stores 1 - end_trial there)  */
+  float reward;           /* float32, as the tables are                                         */
+  int32_t reserved_;
+} cobel_tab_exp_t;
+
+enum { COBEL_REPLAY_WAVE = 0, COBEL_REPLAY_LANE = 1 };
+enum { COBEL_UPDATE_ONLINE = 0, COBEL_UPDATE_PLANNING = 1 };
+
+/* DynaQ.replay (agent/dyna_q.py:319-330) with DynaQMemory.retrieve_batch (memory/dyna_q.py:
+ * 122-157), n_batches times in one launch: per batch, run->batch pairs in one vector draw of
+ * COBEL_STREAM_MEMORY at the instance's counter inst[COBEL_I_CTR_MEMORY] (element j from
+ * sub-stream j, what a planning step of cobel_tab_run consumes), their model records, the updates
+ * in the reference's order in the planning arithmetic (float64 TD, one rounding into the float32
+ * Q), the counter advanced by one.  n_batches calls of one batch and one call of n_batches leave
+ * the same bits.  Uses q, model, inst, batch (>= 1, no upper limit), alpha / gamma or the parameter
+ * sets, seed, instance_base, n and flags (COBEL_F_REPLAY_LANE) of the run; monitors, scratch and
+ * model_index are ignored (planning never writes the model).  Two forms, same results:
+ * COBEL_REPLAY_WAVE — one wavefront per instance, Q in LDS — while a Q table fits the LDS,
+ * COBEL_REPLAY_LANE — one lane per instance, Q in place — beyond, and under the flag.
+ * COBEL_E_RANGE for n_batches < 0 or batch < 1, COBEL_E_ARG for a misaligned or missing table or an
+ * agent other than COBEL_AGENT_DYNAQ, COBEL_E_UNSUPPORTED for worlds of other than four actions. */
+COBEL_API int cobel_dynaq_replay(const cobel_world_t* world, const cobel_tab_run_t* run,
+                                 int32_t n_batches, void* stream);
+/* What cobel_dynaq_replay would launch, without launching (same checks): out = {COBEL_REPLAY_*,
+ * LDS bytes per workgroup, threads per workgroup, instances per workgroup}. */
+COBEL_API int cobel_dynaq_replay_plan(const cobel_world_t* world, const cobel_tab_run_t* run,
+                                      int32_t n_batches, int32_t out[4]);
+/* DynaQ.update_q (agent/dyna_q.py:275-301): one given experience per instance, td [dev] [N]
+ * float64 (0 for an instance without one).  form COBEL_UPDATE_ONLINE: float32, gamma * nt first,
+ * one rounding per operation — the step of cobel_tab_run, what the reference computes on float32
+ * tables from Python scalars; COBEL_UPDATE_PLANNING: the arithmetic of cobel_dynaq_replay, what it
+ * computes from the NumPy scalars its memory hands out.  Uses q, alpha / gamma or the parameter
+ * sets and n of the run.  An experience that names a pair outside the tables is skipped. */
+COBEL_API int cobel_dynaq_update(const cobel_world_t* world, const cobel_tab_run_t* run,
+                                 const cobel_tab_exp_t* exps /* [dev] [N] */, uint32_t form,
+                                 double* td /* [dev] [N] */, void* stream);
+/* DynaQMemory.store (memory/dyna_q.py:77-96) in every instance: R += lr * (r - R) in float32
+ * (d = r - R; R + lr * d, as the step of cobel_tab_run), next state and flag replaced; the digest
+ * entry follows when model_index is given (NULL: none is kept). */
+COBEL_API int cobel_model_store(uint64_t* model /* [dev] [N][S][4] */,
+                                uint16_t* model_index /* [dev] [N][S][4] or NULL */, int32_t n,
+                                int32_t n_states, const cobel_tab_exp_t* exps /* [dev] [N] */,
+                                double model_lr, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Successor-representation agent.  Replaces SR.train / SR.update / SR.retrieve_q
