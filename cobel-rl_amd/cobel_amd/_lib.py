@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get('COBEL_LIB') or os.path.join(os.path.dirname(_HERE), '
 
 OK, E_ARG, E_RANGE, E_HIP, E_UNSUPPORTED = 0, -1, -2, -3, -4
 STREAM_ENV, STREAM_POLICY, STREAM_MEMORY, STREAM_POLICY_TEST, STREAM_AGENT = 0, 1, 2, 3, 4
+STREAM_PMA_MEMORY, STREAM_PMA_POLICY = 5, 6
 SUB_DOUBLE = 1
 AGENT_Q, AGENT_DYNAQ = 0, 1
 F_LEARN, F_NO_REPLAY, F_EPISODIC, F_MASK_ACTIONS, F_TEST_STREAM, F_FORCE_WAVE = 1, 2, 4, 8, 16, 32
@@ -248,6 +249,44 @@ class SFMAMem(C.Structure):
     ]
 
 
+PMA_MAX_STATES, PMA_MAX_ACTIONS = 128, 8
+(PMA_EQUAL_NEED, PMA_EQUAL_GAIN, PMA_IGNORE_BARRIERS, PMA_ALLOW_LOOPS, PMA_GAIN_ORIGINAL,
+ PMA_SHARED_POLICY) = (1 << k for k in range(6))
+
+
+class PMAMem(C.Structure):
+    """``cobel_pma_mem_t``."""
+    _fields_ = [
+        ('q', C.c_void_p), ('rewards', C.c_void_p), ('states', C.c_void_p),
+        ('terminals', C.c_void_p), ('T', C.c_void_p), ('SR', C.c_void_p),
+        ('update_mask', C.c_void_p), ('action_mask', C.c_void_p),
+        ('mem_ctr', C.c_void_p), ('pol_ctr', C.c_void_p),
+        ('gamma_pow', C.c_void_p), ('gamma_q_pow', C.c_void_p),
+        ('n', C.c_int32), ('n_states', C.c_int32), ('n_actions', C.c_int32),
+        ('pow_len', C.c_int32),
+        ('instance_base', C.c_uint32), ('flags', C.c_uint32), ('pol_stream', C.c_uint32),
+        ('reserved_', C.c_uint32),
+        ('learning_rate', C.c_double), ('learning_rate_q', C.c_double),
+        ('learning_rate_T', C.c_double), ('gamma', C.c_double), ('gamma_q', C.c_double),
+        ('min_gain', C.c_double), ('epsilon', C.c_double),
+        ('seed', C.c_uint64),
+    ]
+
+
+class PMARun(C.Structure):
+    """``cobel_pma_run_t``."""
+    _fields_ = [
+        ('inst', C.c_void_p),
+        ('lat_sum', C.c_void_p), ('lat_cnt', C.c_void_p), ('reward_sum', C.c_void_p),
+        ('resp_cnt', C.c_void_p), ('lat_trace', C.c_void_p), ('occupancy', C.c_void_p),
+        ('steps_done', C.c_void_p), ('last', C.c_void_p), ('replay_out', C.c_void_p),
+        ('trial_cap', C.c_int32), ('mon_stripes', C.c_int32), ('steps_per_trial', C.c_int32),
+        ('batch', C.c_int32),
+        ('flags', C.c_uint32), ('reserved_', C.c_uint32),
+        ('alpha', C.c_double), ('gamma_pow1', C.c_double), ('epsilon', C.c_double),
+    ]
+
+
 class SRRun(C.Structure):
     """``cobel_sr_run_t``."""
     _fields_ = [
@@ -331,6 +370,11 @@ _SIGNATURES = {
     'cobel_sfma_replay': (C.c_int, [C.POINTER(SFMAMem), C.c_int32, C.c_int32, _P, _P, _P, _P, _P,
                                     _P]),
     'cobel_sfma_random_batch': (C.c_int, [C.POINTER(SFMAMem), C.c_int32, _P, _P, _P]),
+    'cobel_pma_plan': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32 * 4)]),
+    'cobel_pma_replay': (C.c_int, [C.POINTER(PMAMem), C.c_int32, _P, _P, _P, _P, _P]),
+    'cobel_pma_trial': (C.c_int, [_P, C.POINTER(PMAMem), C.POINTER(PMARun), _P]),
+    'cobel_pma_store': (C.c_int, [C.POINTER(PMAMem), _P, _P]),
+    'cobel_pma_update_sr': (C.c_int, [C.POINTER(PMAMem), _P]),
     'cobel_adam_step': (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int32,
                                   C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _P,
                                   C.c_double, _P]),

@@ -1,0 +1,198 @@
+"""PMA agent — ``cobel.agent.PMA`` (agent/pma.py:16-369): Dyna-Q with Prioritized Memory Access
+(Mattar & Daw 2018) on the kernels of csrc/pma.hip.
+
+Same constructor, ``train(interface, trials, steps, batch_size=32, no_replay=False)``, ``test``,
+``update_q``, ``predict_on_batch`` and attributes (``Q``, ``M``, ``learning_rate``, ``gamma``,
+``action_mask``, ``mask_actions``), plus the ``on_replay_end`` callback with ``logs['replay']``.
+``Q`` is float64, as the reference's.  As in the reference, ``test()`` draws its actions from
+``policy`` (``policy_test`` is stored and not consulted, agent/pma.py:291).
+
+``train`` runs trial by trial over all instances: ``cobel_pma_trial`` (reset, the start-of-trial
+replay, the steps with the 1-step update and the store), then ``M.update_sr()`` through the public
+method, then the end-of-trial replay with need from ``SR[last]``.  Instances whose trial timed out
+have no last state: their need is ``M.compute_need(None)`` on the host, so ``last`` [N] is read
+back once per trial.  Host callbacks fire at these boundaries: ``on_replay_end`` of the start
+replay after the trial's kernel, step callbacks not at all.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+
+from .. import _lib
+from ..spaces import Discrete
+from .agent import Callbacks, FusedAgent
+
+
+class CallbacksPMA(Callbacks):
+    def on_replay_end(self, logs: dict) -> dict:
+        return self._fire('on_replay_end', logs)
+
+
+class PMA(FusedAgent):
+    CallbacksPMA = CallbacksPMA
+    general_actions = True
+
+    def __init__(self, observation_space, action_space, policy, memory, policy_test=None,
+                 learning_rate: float = 0.9, gamma: float = 0.99, custom_callbacks=None) -> None:
+        assert type(observation_space) is Discrete, 'PMA requires a discrete observation space!'
+        assert type(action_space) is Discrete, 'PMA requires a discrete action space!'
+        super().__init__(observation_space, action_space, policy, policy_test, custom_callbacks)
+        if self.n_states > _lib.PMA_MAX_STATES or self.n_actions > _lib.PMA_MAX_ACTIONS:
+            raise NotImplementedError(
+                'PMA: %d states and %d actions — this version serves worlds of up to %d states '
+                'and %d actions' % (self.n_states, self.n_actions, _lib.PMA_MAX_STATES,
+                                    _lib.PMA_MAX_ACTIONS))
+        self.callbacks = CallbacksPMA(self, custom_callbacks)
+        self.learning_rate = learning_rate
+        self.gamma = gamma
+        self.M = memory
+        assert (memory.nb_states, memory.nb_actions) == (self.n_states, self.n_actions), \
+            'the memory was built for another world'
+        self._q = None
+        self._q_host = np.zeros((self.n_states, self.n_actions))
+        self._last = None
+
+    # -- tables ---------------------------------------------------------------------------------
+    def _alloc_tables(self) -> None:
+        self._q = torch.zeros((self.n_envs, self.n_states, self.n_actions), dtype=torch.float64,
+                              device=self.device)
+        self._q.copy_(torch.as_tensor(self._q_host, device=self.device).expand_as(self._q))
+        self._last = torch.full((self.n_envs,), -1, dtype=torch.int32, device=self.device)
+        self.M._bind(self.n_envs, self.device)
+
+    @property
+    def Q(self):
+        """``(S, A)`` float64 NumPy snapshot for one instance, the device tensor ``[N, S, A]``
+        when vectorised.  Assigning broadcasts to all instances."""
+        if self._q is None:
+            return self._q_host
+        return self._q[0].cpu().numpy() if self.n_envs == 1 else self._q
+
+    @Q.setter
+    def Q(self, value) -> None:
+        if self._q is None:
+            self._q_host = np.array(value, dtype=np.float64).reshape(self.n_states, self.n_actions)
+        else:
+            v = value if torch.is_tensor(value) else torch.as_tensor(
+                np.asarray(value, dtype=np.float64))
+            v = v.to(device=self.device, dtype=torch.float64)
+            self._q.copy_(v.expand_as(self._q) if v.dim() == 2 else v)
+
+    def predict_on_batch(self, batch):
+        idx = np.array(batch).astype(int)
+        if self._q is None:
+            return self._q_host[idx]
+        if self.n_envs == 1:
+            return self._q[0][torch.as_tensor(idx, device=self.device)].cpu().numpy()
+        return self._q[:, torch.as_tensor(idx, device=self.device)]
+
+    def update_q(self, update: list) -> None:
+        """agent/pma.py:319-353 for a given n-step list of experiences, applied to every instance:
+        a host call for use between sessions (inside ``train`` the 1-step update is part of the
+        trial kernel)."""
+        q = np.array(self.Q.cpu().numpy() if torch.is_tensor(self.Q) else self.Q)
+        for Q in q.reshape(-1, self.n_states, self.n_actions):
+            future_value = np.amax(Q[update[-1]['next_state']]) * update[-1]['terminal']
+            for s, step in enumerate(update):
+                r, ok = 0.0, True
+                for k in range(len(update) - s):
+                    if update[s + k]['terminal'] == 0 and s != len(update) - 1:
+                        ok = False
+                        break
+                    r += update[s + k]['reward'] * (self.gamma ** k)
+                if not ok:
+                    break
+                td = r + future_value * (self.gamma ** (k + 1))
+                td -= Q[step['state']][step['action']]
+                Q[step['state']][step['action']] += self.learning_rate * td
+        self.Q = q.reshape(-1, self.n_states, self.n_actions) if self.n_envs not in (None, 1) else \
+            q.reshape(self.n_states, self.n_actions)
+
+    # -- launch ---------------------------------------------------------------------------------
+    def _launch(self, interface, pol, flags, trials_target, steps, budget, batch) -> None:
+        M, mon = self.M, self.monitors
+        shared = M.policy is pol
+        mem = M._mem(self._q, self._mask_dev, batch)
+        run = _lib.PMARun()
+        run.inst = _lib.ptr(self.inst)
+        run.lat_sum, run.lat_cnt = _lib.ptr(mon.raw('lat_sum')), _lib.ptr(mon.raw('lat_cnt'))
+        run.reward_sum, run.resp_cnt = _lib.ptr(mon.raw('reward_sum')), _lib.ptr(mon.raw('resp_cnt'))
+        run.lat_trace, run.occupancy = _lib.ptr(mon.lat_trace), _lib.ptr(mon.occupancy)
+        run.steps_done = _lib.ptr(mon.steps_done)
+        run.last = _lib.ptr(self._last)
+        run.replay_out = _lib.ptr(self._start_records)
+        run.trial_cap, run.mon_stripes = mon.cap, mon.stripes
+        run.steps_per_trial, run.batch = steps, batch
+        run.flags = flags | ((_lib.PMA_SHARED_POLICY << 16) if shared else 0)
+        run.alpha, run.gamma_pow1 = self.learning_rate, self.gamma ** 1
+        run.epsilon = float(pol.epsilon)
+        _lib.check(_lib.lib().cobel_pma_trial(interface.handle.ptr, C.byref(mem), C.byref(run),
+                                              _lib.current_stream(self.device)))
+
+    def _replay_logs(self, logs: dict, records, batch: int) -> dict:
+        if not self.callbacks.has('on_replay_end'):
+            return logs
+        ups = self.M.experiences(records, batch)
+        logs['replay'] = ups[0] if self.n_envs == 1 else ups
+        return self.callbacks.on_replay_end(logs)
+
+    def _run(self, interface, trials: int, steps: int, batch: int, learn: bool,
+             no_replay: bool) -> None:
+        interface.sync_world()
+        self._bind(interface)
+        M = self.M
+        pol = self.policy      # (agent/pma.py:291: test() selects with self.policy as well)
+        if M.policy is pol and pol.stream is None:
+            pol.stream = _lib.STREAM_POLICY
+        flags = (_lib.F_LEARN if learn else 0) | (_lib.F_NO_REPLAY if no_replay else 0) | \
+                (_lib.F_MASK_ACTIONS if self.mask_actions else 0)
+        self._env_in(interface)
+        flags |= self._policy_in(pol, interface, not learn)
+        M._session(interface.seed, interface.instance_base)
+        shared = M.policy is pol
+        replays = learn and not no_replay
+        first = self.current_trial
+        self.monitors.reserve(first + trials, self.n_envs, self.track_instances)
+        self._mask_dev = self._mask_bits() if self.mask_actions else None
+        self._start_records = None
+        if replays:
+            self._start_records = torch.zeros((self.n_envs, max(batch, 1) * 24), dtype=torch.uint8,
+                                              device=self.device)
+        for t in range(trials):
+            interface.sync_world()
+            logs = self.callbacks.on_trial_begin({'trial_reward': 0, 'steps': 0,
+                                                  'trial': self.current_trial, 'trial_session': t})
+            self._launch(interface, pol, flags, self.current_trial + 1, steps, 0, batch)
+            if shared:       # (the memory's replay below goes on where the trial's draws ended)
+                pol.counter.copy_(self.inst[:, _lib.I_CTR_POLICY])
+            if replays:
+                logs = self._replay_logs(logs, self._start_records, batch)
+                last = self._last.cpu().numpy()
+                M.update_sr()
+                rec = M._replay_device(self._q, self._mask_dev, batch, last, M._need_rows(last),
+                                       None)
+                if shared:
+                    self.inst[:, _lib.I_CTR_POLICY] = pol.counter
+            if self.callbacks.has('on_trial_end', 'on_replay_end'):
+                st = self.inst[:, _lib.I_STEP].cpu().numpy()
+                rw = self._trial_reward()
+                logs['steps'] = logs['step'] = int(st[0]) if self.n_envs == 1 else float(st.mean())
+                logs['trial_reward'] = float(rw[0]) if self.n_envs == 1 else float(rw.mean())
+            if replays:
+                logs = self._replay_logs(logs, rec, batch)
+            self.current_trial += 1
+            logs = self.callbacks.on_trial_end(logs)
+            if self.stop:
+                break
+        self._policy_out(pol)
+        self._env_out(interface)
+
+    def train(self, interface, trials: int, steps: int, batch_size: int = 32,
+              no_replay: bool = False) -> None:
+        self._run(interface, trials, steps, int(batch_size), True, bool(no_replay))
+
+    def test(self, interface, trials: int, steps: int) -> None:
+        self._run(interface, trials, steps, 0, False, True)

@@ -1,0 +1,322 @@
+"""Memory module of the PMA agent — ``cobel.memory.PMAMemory`` (memory/pma.py:20-496).
+
+Same constructor, attributes, switches and methods as the reference.  ``replay``, ``store`` and
+``update_sr`` are device calls (``cobel_pma_replay`` / ``cobel_pma_store`` / ``cobel_pma_update_sr``,
+csrc/pma.hip); inside ``PMA.train`` the stores and the start-of-trial replay are part of the trial
+kernel (``cobel_pma_trial``).  A memory is bound to a device by the agent's first session or,
+without an agent, by ``bind``.  Every table is float64, as the reference's are.
+
+Tables (one leading instance axis on the device; the attributes return NumPy snapshots, squeezed
+for one instance, and assigning uploads):
+
+  ``rewards``      float64 [S, A]        ``states`` / ``terminals``  int [S, A]
+  ``T`` / ``SR``   float64 [S, S]        ``update_mask``             bool [A * S], index a * S + s
+
+The initial ``T`` and ``SR`` are the reference's NumPy expressions evaluated on the host, so until
+the first ``update_sr()`` the SR is the reference's bit for bit.  ``compute_need(None)`` — the
+stationary distribution, the left eigenvector of T for the eigenvalue nearest 1 — runs on the host
+with ``scipy.linalg.eig`` and reaches the kernel as a need vector: a slow path.
+
+Draws: the memory's generator is stream ``STREAM_PMA_MEMORY`` of (seed, instance) at ``counter``;
+the extension actions come from the memory's own policy object — stream ``STREAM_PMA_POLICY`` at
+``policy.counter`` unless that object also acts for an agent.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+
+from .. import _lib
+
+RECORD = np.dtype([('state', '<i4'), ('action', '<i4'), ('next_state', '<i4'),
+                   ('terminal', '<i4'), ('reward', '<f8')])
+
+_TABLES = {'rewards': (torch.float64, np.float64), 'states': (torch.int32, np.int64),
+           'terminals': (torch.int32, np.int64), 'T': (torch.float64, np.float64),
+           'SR': (torch.float64, np.float64), 'update_mask': (torch.uint8, bool)}
+
+
+def _table(name: str):
+    tdt, ndt = _TABLES[name]
+
+    def get(self):
+        if self._dev is None:
+            return self._host[name]
+        a = self._dev[name].cpu().numpy().astype(ndt)
+        return a[0] if a.shape[0] == 1 else a
+
+    def put(self, value) -> None:
+        shape = self._host[name].shape
+        if self._dev is None:
+            self._host[name] = np.array(value, dtype=ndt).reshape(shape)
+            return
+        t = self._dev[name]
+        v = np.asarray(value.cpu().numpy() if torch.is_tensor(value) else value)
+        v = v.astype(ndt).reshape((-1,) + shape)
+        t.copy_(torch.as_tensor(np.ascontiguousarray(v), device=t.device).to(tdt).expand_as(t))
+
+    return property(get, put)
+
+
+class PMAMemory:
+    def __init__(self, sas, policy, learning_rate: float = 0.9, learning_rate_q: float = 0.9,
+                 gamma: float = 0.9, gamma_q: float = 0.9, rng=None) -> None:
+        self.rng = rng
+        self.sas = np.asarray(sas)
+        self.policy = policy
+        self.learning_rate = learning_rate
+        self.learning_rate_q = learning_rate_q
+        self.learning_rate_T = 0.9
+        self.gamma = gamma
+        self.gamma_q = gamma_q
+        self.nb_states = S = int(self.sas.shape[0])
+        self.nb_actions = A = int(self.sas.shape[1])
+        if S > _lib.PMA_MAX_STATES or A > _lib.PMA_MAX_ACTIONS:
+            raise NotImplementedError(
+                'PMAMemory: %d states and %d actions — this version serves worlds of up to %d '
+                'states and %d actions' % (S, A, _lib.PMA_MAX_STATES, _lib.PMA_MAX_ACTIONS))
+        self.min_gain = 10 ** -6
+        self.min_gain_mode = 'original'
+        self.equal_need = False
+        self.equal_gain = False
+        self.ignore_barriers = True
+        self.allow_loops = False
+        # memory/pma.py:135-146, on the host
+        states = np.zeros((S, A)).astype(int)
+        T = np.sum(self.sas, axis=1) / A
+        self._host = {
+            'rewards': np.zeros((S, A)), 'states': states,
+            'terminals': np.zeros((S, A)).astype(int), 'T': np.array(T, dtype=np.float64),
+            'SR': np.linalg.inv(np.eye(T.shape[0]) - self.gamma * T),
+            'update_mask': states.flatten(order='F') != np.tile(np.arange(S), A),
+        }
+        self._dev = None
+        self.counter = None
+        self.seed, self.instance_base = 0, 0
+        self._pows = None
+
+    rewards, states, terminals = _table('rewards'), _table('states'), _table('terminals')
+    T, SR, update_mask = _table('T'), _table('SR'), _table('update_mask')
+
+    # -- device state ---------------------------------------------------------------------------
+    def bind(self, n_envs: int = 1, device=None, seed: int = 0, instance_base: int = 0) -> None:
+        """Put the tables of ``n_envs`` instances on ``device`` (default: the current GPU) for a
+        memory that is used without an agent; instance i draws from the streams of
+        (``seed``, ``instance_base + i``)."""
+        assert self._dev is None, 'the memory is bound already'
+        if device is None:
+            device = torch.device('cuda', torch.cuda.current_device())
+        self._bind(n_envs, torch.device(device))
+        self._session(seed, instance_base)
+
+    def _session(self, seed: int, instance_base: int) -> None:
+        self.seed, self.instance_base = int(seed), int(instance_base)
+
+    def _bind(self, n_envs: int, device) -> None:
+        if self._dev is not None:
+            assert self.n_envs == n_envs, 'a memory stays bound to the instance count it first saw'
+            return
+        dev = {}
+        for name, (tdt, _) in _TABLES.items():
+            h = np.ascontiguousarray(self._host[name])
+            t = torch.as_tensor(h, device=device).to(tdt)
+            dev[name] = t.unsqueeze(0).expand((n_envs,) + tuple(t.shape)).contiguous()
+        self._dev = dev
+        self.n_envs = n_envs
+        self.counter = torch.zeros(n_envs, dtype=torch.int32, device=device)
+
+    @property
+    def device(self):
+        return None if self._dev is None else self._dev['T'].device
+
+    def _policy_counter(self):
+        pol, dev = self.policy, self.device
+        if pol.stream is None:
+            pol.stream = _lib.STREAM_PMA_POLICY
+        if pol.counter is None or pol.counter.numel() != self.n_envs or pol.counter.device != dev:
+            pol.counter = torch.zeros(self.n_envs, dtype=torch.int32, device=dev)
+        return pol.counter
+
+    def _power_tables(self, length: int):
+        """gamma ** k and gamma_q ** k, k = 0 .. length, by Python's ``**`` (memory/pma.py:310,
+        :315, :485, :491): constants, not arithmetic on the data path."""
+        key = (float(self.gamma), float(self.gamma_q))
+        if self._pows is None or self._pows[0] != key or self._pows[1].shape[1] <= length:
+            n = max(length + 1, 34)
+            tab = np.array([[self.gamma ** k for k in range(n)],
+                            [self.gamma_q ** k for k in range(n)]], dtype=np.float64)
+            self._pows = (key, torch.as_tensor(tab, device=self.device))
+        return self._pows[1]
+
+    def flags(self) -> int:
+        return ((_lib.PMA_EQUAL_NEED if self.equal_need else 0) |
+                (_lib.PMA_EQUAL_GAIN if self.equal_gain else 0) |
+                (_lib.PMA_IGNORE_BARRIERS if self.ignore_barriers else 0) |
+                (_lib.PMA_ALLOW_LOOPS if self.allow_loops else 0) |
+                (_lib.PMA_GAIN_ORIGINAL if self.min_gain_mode == 'original' else 0))
+
+    def _mem(self, q=None, mask_bits=None, length: int = 0):
+        assert self._dev is not None, \
+            'the memory has no device tables yet: train an agent with it, or call bind()'
+        d = self._dev
+        m = _lib.PMAMem()
+        m.q = _lib.ptr(q)
+        m.rewards, m.states, m.terminals = (_lib.ptr(d['rewards']), _lib.ptr(d['states']),
+                                            _lib.ptr(d['terminals']))
+        m.T, m.SR, m.update_mask = _lib.ptr(d['T']), _lib.ptr(d['SR']), _lib.ptr(d['update_mask'])
+        m.action_mask = _lib.ptr(mask_bits)
+        m.mem_ctr, m.pol_ctr = _lib.ptr(self.counter), _lib.ptr(self._policy_counter())
+        pows = self._power_tables(length)
+        m.gamma_pow, m.gamma_q_pow = pows[0].data_ptr(), pows[1].data_ptr()
+        m.pow_len = pows.shape[1]
+        m.n, m.n_states, m.n_actions = self.n_envs, self.nb_states, self.nb_actions
+        m.instance_base, m.flags, m.pol_stream = self.instance_base, self.flags(), self.policy.stream
+        m.learning_rate, m.learning_rate_q = self.learning_rate, self.learning_rate_q
+        m.learning_rate_T, m.gamma, m.gamma_q = self.learning_rate_T, self.gamma, self.gamma_q
+        m.min_gain, m.epsilon = self.min_gain, float(self.policy.epsilon)
+        m.seed = self.seed
+        return m
+
+    def launch_plan(self, replay_length: int = 32) -> list:
+        """(LDS bytes, threads) of a replay / trial workgroup and of an update_sr workgroup."""
+        out = (C.c_int32 * 4)()
+        _lib.check(_lib.lib().cobel_pma_plan(self.nb_states, self.nb_actions, int(replay_length),
+                                             C.byref(out)))
+        return list(out)
+
+    def _per_instance(self, value, name: str, limit: int):
+        """scalar / [N] -> int32 [N], range-checked; entries None or < 0 become -1."""
+        if isinstance(value, (list, tuple)):
+            value = [-1 if v is None else v for v in value]
+        a = np.array(np.broadcast_to(np.asarray(value, dtype=np.int64), (self.n_envs,)))
+        if (a >= limit).any():
+            raise IndexError('%s outside [0, %d)' % (name, limit))
+        a[a < 0] = -1
+        return np.ascontiguousarray(a, dtype=np.int32)
+
+    def _mask_bits(self, action_mask):
+        if action_mask is None:
+            return None
+        m = np.asarray(action_mask, dtype=bool).reshape(self.nb_states, self.nb_actions)
+        assert m.any(axis=1).all(), 'The action mask masks all actions!'
+        bits = (m * (1 << np.arange(self.nb_actions, dtype=np.int64))).sum(axis=1).astype(np.uint8)
+        return torch.as_tensor(bits, device=self.device)
+
+    # -- the reference's methods ------------------------------------------------------------------
+    def store(self, experience: dict) -> None:
+        """memory/pma.py:148-166.  One experience per instance: the values of ``experience`` are
+        scalars (the same for all instances) or [N] arrays."""
+        m = self._mem()
+        n = self.n_envs
+        rec = np.zeros(n, dtype=RECORD)
+        rec['state'] = self._per_instance(experience['state'], 'state', self.nb_states)
+        rec['action'] = self._per_instance(experience['action'], 'action', self.nb_actions)
+        rec['next_state'] = self._per_instance(experience['next_state'], 'next_state',
+                                               self.nb_states)
+        rec['terminal'] = np.broadcast_to(np.asarray(experience['terminal'], dtype=np.int64), (n,))
+        rec['reward'] = np.broadcast_to(np.asarray(experience['reward'], dtype=np.float64), (n,))
+        exps = torch.as_tensor(rec.view(np.uint8), device=self.device)
+        _lib.check(_lib.lib().cobel_pma_store(C.byref(m), _lib.ptr(exps),
+                                              _lib.current_stream(self.device)))
+
+    def _replay_device(self, q, mask_bits, length: int, states, need_rows, force_first):
+        """One replay per instance IN PLACE on the device tensor ``q`` [N, S, A]: ``states`` int32
+        [N] host array (-1: the instance's row of ``need_rows`` [N, S]) or None (all from
+        ``need_rows``).  Returns the records as a uint8 device tensor [N, length * 24]."""
+        dev = self.device
+        m = self._mem(q, mask_bits, length)
+        st_d = None if states is None else torch.as_tensor(states, device=dev)
+        nd_d = None if need_rows is None else torch.as_tensor(
+            np.ascontiguousarray(need_rows, dtype=np.float64), device=dev)
+        ff_d = None if force_first is None else torch.as_tensor(force_first, device=dev)
+        records = torch.zeros((self.n_envs, max(length, 1) * RECORD.itemsize), dtype=torch.uint8,
+                              device=dev)
+        _lib.check(_lib.lib().cobel_pma_replay(
+            C.byref(m), int(length), _lib.ptr(st_d), _lib.ptr(nd_d), _lib.ptr(ff_d),
+            _lib.ptr(records), _lib.current_stream(dev)))
+        return records
+
+    @staticmethod
+    def experiences(records, length: int) -> list:
+        """Record tensor -> per instance the reference's list of experience dicts."""
+        raw = records.cpu().numpy().view(RECORD)[:, :length]
+        return [[{'state': int(e['state']), 'action': int(e['action']), 'reward': float(e['reward']),
+                  'next_state': int(e['next_state']), 'terminal': int(e['terminal'])}
+                 for e in row] for row in raw]
+
+    def _need_rows(self, states, instances=None):
+        """The need vectors [N, S] of the instances whose state is -1 / None (host path), or None
+        when every instance names a state."""
+        if states is not None and (states >= 0).all():
+            return None
+        S, n = self.nb_states, self.n_envs
+        idx = np.arange(n) if states is None else np.flatnonzero(states < 0)
+        need = np.asarray(self.compute_need(None, instances=idx), dtype=np.float64)
+        rows = np.zeros((n, S))
+        rows[idx] = need.reshape(-1, self.nb_actions * S)[:, :S]
+        return rows
+
+    def replay(self, q_function, action_mask, replay_length: int, current_state,
+               force_first=None):
+        """memory/pma.py:168-267: one replay per instance on a copy of ``q_function`` ([S, A], or
+        [N, S, A]).  Returns ``(updates, Q)``: the performed updates as a list of experience dicts
+        and the updated copy as a NumPy array for one instance; one list per instance and the
+        device tensor [N, S, A] for several.  ``current_state`` / ``force_first`` are scalars or
+        [N] arrays; ``current_state=None`` takes ``compute_need(None)`` (host, slow)."""
+        assert self._dev is not None, \
+            'the memory has no device tables yet: train an agent with it, or call bind()'
+        n, S, A = self.n_envs, self.nb_states, self.nb_actions
+        if torch.is_tensor(q_function):
+            q = q_function.to(device=self.device, dtype=torch.float64)
+        else:
+            q = torch.as_tensor(np.asarray(q_function, dtype=np.float64), device=self.device)
+        q = q.reshape((-1, S, A)).expand((n, S, A)).clone().contiguous()
+        states = (None if current_state is None
+                  else self._per_instance(current_state, 'current_state', S))
+        ff = None if force_first is None else self._per_instance(force_first, 'force_first', S)
+        rows = self._need_rows(states)
+        length = int(replay_length)
+        records = self._replay_device(q, self._mask_bits(action_mask), length, states, rows, ff)
+        ups = self.experiences(records, length)
+        if n == 1:
+            return ups[0], q[0].cpu().numpy()
+        return ups, q
+
+    def compute_need(self, current_state=None, instances=None):
+        """memory/pma.py:388-411.  ``None``: the stationary distribution of T by
+        ``scipy.linalg.eig`` on the host, of ``instances`` (default: all)."""
+        S, A = self.nb_states, self.nb_actions
+        if current_state is None:
+            from scipy import linalg
+            T = np.asarray(self.T, dtype=np.float64).reshape(-1, S, S)
+            idx = np.arange(T.shape[0]) if instances is None else np.asarray(instances)
+            out = []
+            for i in idx:
+                eig, vec = linalg.eig(T[i], left=True, right=False)
+                best = np.argmin(np.abs(eig - 1))
+                out.append(np.tile(np.abs(vec[:, best].T), A))
+            out = np.array(out)
+            return out[0] if (instances is None and len(out) == 1) else out
+        SR = np.asarray(self.SR).reshape(-1, S, S)
+        cs = np.broadcast_to(np.asarray(current_state, dtype=np.int64), (SR.shape[0],))
+        out = np.array([np.tile(SR[i, cs[i]], A) for i in range(SR.shape[0])])
+        return out[0] if len(out) == 1 else out
+
+    def update_sr(self) -> None:
+        """memory/pma.py:413-415 on the device: SR = inv(I - gamma T) per instance."""
+        m = self._mem()
+        _lib.check(_lib.lib().cobel_pma_update_sr(C.byref(m), _lib.current_stream(self.device)))
+
+    def compute_update_mask(self) -> None:
+        """memory/pma.py:417-421."""
+        S, A = self.nb_states, self.nb_actions
+        if self._dev is None:
+            self._host['update_mask'] = (self._host['states'].flatten(order='F') !=
+                                         np.tile(np.arange(S), A))
+            return
+        st = self._dev['states']
+        flat = st.permute(0, 2, 1).reshape(st.shape[0], A * S)
+        own = torch.arange(S, device=st.device, dtype=st.dtype).repeat(A)
+        self._dev['update_mask'].copy_((flat != own).to(torch.uint8))

@@ -1041,6 +1041,108 @@ typedef struct {
 } cobel_dqn_act_t;
 COBEL_API int cobel_dqn_act(const cobel_world_t* world, const cobel_dqn_act_t* run, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Prioritized Memory Access (Mattar & Daw 2018).  Replaces PMAMemory.replay / store / update_sr
+ * (memory/pma.py:168-267, :148-166, :413-415) and the trial loop of PMA.train / PMA.test
+ * (agent/pma.py:167-317).  Every table is float64, as the reference's are: the gain is a
+ * difference of nearly equal sums clipped at min_gain and the selection an exact-equality tie
+ * test.  Worlds of up to COBEL_PMA_MAX_STATES states and COBEL_PMA_MAX_ACTIONS actions.
+ * Tables per instance: Q, rewards f64 [S][A]; states, terminals i32 [S][A]; T, SR f64 [S][S];
+ * update_mask u8 [A * S], experience index a * S + s as in the reference.
+ * Draws: the memory's generator is COBEL_STREAM_PMA_MEMORY at mem_ctr[i] — one double (sub-stream
+ * COBEL_SUB_DOUBLE) per round for the tie draw, one bounded integer (sub-stream 0) for force_first;
+ * the memory's policy object is pol_stream (COBEL_STREAM_PMA_POLICY unless it is the agent's own
+ * policy object) at pol_ctr[i] — one double per extension action (policy/greedy.py:58).
+ * ------------------------------------------------------------------------------------------ */
+#define COBEL_STREAM_PMA_MEMORY 5u /* c = draws of PMAMemory.rng          (memory/pma.py:252, :258) */
+#define COBEL_STREAM_PMA_POLICY 6u /* c = select_action calls of PMAMemory.policy (memory/pma.py:232) */
+#define COBEL_PMA_MAX_STATES 128
+#define COBEL_PMA_MAX_ACTIONS 8
+#define COBEL_PMA_EQUAL_NEED 1u        /* PMAMemory.equal_need                                   */
+#define COBEL_PMA_EQUAL_GAIN 2u        /* PMAMemory.equal_gain                                   */
+#define COBEL_PMA_IGNORE_BARRIERS 4u   /* PMAMemory.ignore_barriers (default on)                 */
+#define COBEL_PMA_ALLOW_LOOPS 8u       /* PMAMemory.allow_loops                                  */
+#define COBEL_PMA_GAIN_ORIGINAL 16u    /* PMAMemory.min_gain_mode == 'original'                  */
+#define COBEL_PMA_SHARED_POLICY 32u    /* cobel_pma_trial: the memory's policy IS the agent's: its
+                                          extension draws continue inst[COBEL_I_CTR_POLICY]         */
+
+typedef struct {
+  double* q;                  /* [N][S][A] the Q-function the replay updates                    */
+  double* rewards;            /* [N][S][A]                                                      */
+  int32_t* states;            /* [N][S][A]                                                      */
+  int32_t* terminals;         /* [N][S][A] experience['terminal'] = 1 - end_trial               */
+  double* T;                  /* [N][S][S]                                                      */
+  double* SR;                 /* [N][S][S]                                                      */
+  uint8_t* update_mask;       /* [N][A * S]                                                     */
+  const uint8_t* action_mask; /* [S] bit a = action a allowed, or NULL                          */
+  uint32_t* mem_ctr;          /* [N] next index on COBEL_STREAM_PMA_MEMORY                      */
+  uint32_t* pol_ctr;          /* [N] next index on pol_stream                                   */
+  const double* gamma_pow;    /* [pow_len] gamma ** k, filled by the host                       */
+  const double* gamma_q_pow;  /* [pow_len] gamma_q ** k                                         */
+  int32_t n, n_states, n_actions, pow_len;
+  uint32_t instance_base, flags /* COBEL_PMA_* */, pol_stream, reserved_;
+  double learning_rate, learning_rate_q, learning_rate_T, gamma, gamma_q, min_gain, epsilon;
+  uint64_t seed;
+} cobel_pma_mem_t;
+
+/* One performed update (memory/pma.py:263), 24 bytes. */
+typedef struct {
+  int32_t state, action, next_state, terminal;
+  double reward;
+} cobel_pma_rec_t;
+/* One experience per instance (memory/pma.py:148-166), 24 bytes.  state < 0: none. */
+typedef cobel_pma_rec_t cobel_pma_exp_t;
+
+typedef struct {
+  int32_t* inst;              /* [N][COBEL_I_WORDS]                                             */
+  unsigned long long* lat_sum; /* monitors as in cobel_tab_run_t; each may be NULL              */
+  unsigned long long* lat_cnt;
+  double* reward_sum;
+  unsigned long long* resp_cnt;
+  int32_t* lat_trace;         /* [N][trial_cap] or NULL                                         */
+  unsigned long long* occupancy;
+  unsigned long long* steps_done;
+  int32_t* last;              /* [N] out: the terminal state the trial reached, or -1           */
+  cobel_pma_rec_t* replay_out; /* [N][batch] out: the start-of-trial replay                     */
+  int32_t trial_cap, mon_stripes, steps_per_trial, batch;
+  uint32_t flags;             /* COBEL_F_LEARN | COBEL_F_NO_REPLAY | COBEL_F_MASK_ACTIONS |
+                                 COBEL_F_TEST_STREAM, and COBEL_PMA_SHARED_POLICY << 16          */
+  uint32_t reserved_;
+  double alpha;               /* PMA.learning_rate                                              */
+  double gamma_pow1;          /* PMA.gamma ** 1, from the host                                  */
+  double epsilon;             /* of the acting policy                                           */
+} cobel_pma_run_t;
+
+/* Launch shapes: out = {LDS bytes of a replay / trial workgroup (one wavefront per instance),
+ * its threads, LDS bytes of an update_sr workgroup (one per instance), its threads}.
+ * COBEL_E_UNSUPPORTED beyond COBEL_PMA_MAX_STATES / COBEL_PMA_MAX_ACTIONS, or where the sequence
+ * of a replay of that length no longer fits 64 KiB of LDS beside the tables. */
+COBEL_API int cobel_pma_plan(int32_t n_states, int32_t n_actions, int32_t replay_length,
+                             int32_t out[4]);
+/* PMAMemory.replay (memory/pma.py:168-267) once per instance on mem->q: replay_length rounds of
+ * compute_gain_batch (:333-386) / compute_gain (:269-331) for the extended sequence, utility =
+ * gain * need * update_mask, the draw among exact ties (:251-254), force_first (:256-259), the
+ * n-step update_q (:452-496).  current_state [dev] [N] (entry >= 0: need = SR[state], :411) or
+ * NULL; an entry < 0 — or NULL — takes the instance's row of need [dev] [N][S] (compute_need(None),
+ * :403-408, evaluated by the caller).  force_first [dev] [N] (entry < 0: none) or NULL.  records
+ * [dev] [N][replay_length] out. */
+COBEL_API int cobel_pma_replay(const cobel_pma_mem_t* mem, int32_t replay_length,
+                               const int32_t* current_state, const double* need,
+                               const int32_t* force_first, cobel_pma_rec_t* records, void* stream);
+/* One trial of PMA.train (agent/pma.py:192-245; COBEL_F_LEARN) or PMA.test (:274-314) in every
+ * instance: reset, the start-of-trial replay of run->batch rounds with need = SR[start state],
+ * then up to steps_per_trial steps of select_action -> env.step -> the agent's 1-step update_q
+ * (:319-353, alpha / gamma_pow1) -> PMAMemory.store.  The end-of-trial update_sr and replay are
+ * calls of their own (cobel_pma_update_sr, cobel_pma_replay). */
+COBEL_API int cobel_pma_trial(const cobel_world_t* world, const cobel_pma_mem_t* mem,
+                              const cobel_pma_run_t* run, void* stream);
+/* PMAMemory.store (memory/pma.py:148-166) in every instance. */
+COBEL_API int cobel_pma_store(const cobel_pma_mem_t* mem, const cobel_pma_exp_t* experiences,
+                              void* stream);
+/* PMAMemory.update_sr (memory/pma.py:413-415): SR = inv(I - gamma T) per instance, in-place
+ * Gauss-Jordan without pivoting (I - gamma T is strictly diagonally dominant by rows). */
+COBEL_API int cobel_pma_update_sr(const cobel_pma_mem_t* mem, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
