@@ -250,8 +250,9 @@ class SFMAMem(C.Structure):
 
 
 PMA_MAX_STATES, PMA_MAX_ACTIONS = 128, 8
+PMA_WIDE_MAX_STATES = 1024
 (PMA_EQUAL_NEED, PMA_EQUAL_GAIN, PMA_IGNORE_BARRIERS, PMA_ALLOW_LOOPS, PMA_GAIN_ORIGINAL,
- PMA_SHARED_POLICY) = (1 << k for k in range(6))
+ PMA_SHARED_POLICY, PMA_WIDE) = (1 << k for k in range(7))
 
 
 class PMAMem(C.Structure):
@@ -371,6 +372,7 @@ _SIGNATURES = {
                                     _P]),
     'cobel_sfma_random_batch': (C.c_int, [C.POINTER(SFMAMem), C.c_int32, _P, _P, _P]),
     'cobel_pma_plan': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32 * 4)]),
+    'cobel_pma_plan_wide': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32 * 4)]),
     'cobel_pma_replay': (C.c_int, [C.POINTER(PMAMem), C.c_int32, _P, _P, _P, _P, _P]),
     'cobel_pma_trial': (C.c_int, [_P, C.POINTER(PMAMem), C.POINTER(PMARun), _P]),
     'cobel_pma_store': (C.c_int, [C.POINTER(PMAMem), _P, _P]),

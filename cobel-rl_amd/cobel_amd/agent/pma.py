@@ -4,7 +4,8 @@
 Same constructor, ``train(interface, trials, steps, batch_size=32, no_replay=False)``, ``test``,
 ``update_q``, ``predict_on_batch`` and attributes (``Q``, ``M``, ``learning_rate``, ``gamma``,
 ``action_mask``, ``mask_actions``), plus the ``on_replay_end`` callback with ``logs['replay']``.
-``Q`` is float64, as the reference's.  As in the reference, ``test()`` draws its actions from
+``Q`` is float64, as the reference's.  Worlds of more than 128 states take a memory built with
+``PMAMemory(..., wide=True)``; the agent follows ``memory.wide``.  As in the reference, ``test()`` draws its actions from
 ``policy`` (``policy_test`` is stored and not consulted, agent/pma.py:291).
 
 ``train`` runs trial by trial over all instances: ``cobel_pma_trial`` (reset, the start-of-trial
@@ -40,7 +41,10 @@ class PMA(FusedAgent):
         assert type(observation_space) is Discrete, 'PMA requires a discrete observation space!'
         assert type(action_space) is Discrete, 'PMA requires a discrete action space!'
         super().__init__(observation_space, action_space, policy, policy_test, custom_callbacks)
-        if self.n_states > _lib.PMA_MAX_STATES or self.n_actions > _lib.PMA_MAX_ACTIONS:
+        # (the form is the memory's: a wide memory has passed the wide plan for its world, and the
+        # assertion below ties this agent to that world)
+        if not getattr(memory, 'wide', False) and (
+                self.n_states > _lib.PMA_MAX_STATES or self.n_actions > _lib.PMA_MAX_ACTIONS):
             raise NotImplementedError(
                 'PMA: %d states and %d actions — this version serves worlds of up to %d states '
                 'and %d actions' % (self.n_states, self.n_actions, _lib.PMA_MAX_STATES,

@@ -20,6 +20,12 @@ with ``scipy.linalg.eig`` and reaches the kernel as a need vector: a slow path.
 Draws: the memory's generator is stream ``STREAM_PMA_MEMORY`` of (seed, instance) at ``counter``;
 the extension actions come from the memory's own policy object — stream ``STREAM_PMA_POLICY`` at
 ``policy.counter`` unless that object also acts for an agent.
+
+Two forms.  The default serves worlds of up to 128 states.  ``PMAMemory(..., wide=True)`` selects the
+wide form of the kernels: up to 1 024 states and whatever fits 160 KiB of LDS (32 x 32 with four
+actions does, with eight it does not), ``update_sr`` by the blocked kernels on the SR in device
+memory.  It is opt-in because of its memory: ``T`` and ``SR`` take 8 * S * S bytes each per
+instance — 16 MiB per instance at 1 024 states, 16 GiB for a vectorised run of 1 024 instances.
 """
 from __future__ import annotations
 
@@ -62,8 +68,9 @@ def _table(name: str):
 
 class PMAMemory:
     def __init__(self, sas, policy, learning_rate: float = 0.9, learning_rate_q: float = 0.9,
-                 gamma: float = 0.9, gamma_q: float = 0.9, rng=None) -> None:
+                 gamma: float = 0.9, gamma_q: float = 0.9, rng=None, wide: bool = False) -> None:
         self.rng = rng
+        self.wide = bool(wide)
         self.sas = np.asarray(sas)
         self.policy = policy
         self.learning_rate = learning_rate
@@ -73,7 +80,9 @@ class PMAMemory:
         self.gamma_q = gamma_q
         self.nb_states = S = int(self.sas.shape[0])
         self.nb_actions = A = int(self.sas.shape[1])
-        if S > _lib.PMA_MAX_STATES or A > _lib.PMA_MAX_ACTIONS:
+        if self.wide:
+            self._check_wide(S, A)
+        elif S > _lib.PMA_MAX_STATES or A > _lib.PMA_MAX_ACTIONS:
             raise NotImplementedError(
                 'PMAMemory: %d states and %d actions — this version serves worlds of up to %d '
                 'states and %d actions' % (S, A, _lib.PMA_MAX_STATES, _lib.PMA_MAX_ACTIONS))
@@ -97,6 +106,17 @@ class PMAMemory:
         self.seed, self.instance_base = 0, 0
         self._pows = None
 
+    @staticmethod
+    def _check_wide(S: int, A: int) -> None:
+        """The wide plan's word on a world (replay length 0: the tables alone)."""
+        out = (C.c_int32 * 4)()
+        if _lib.lib().cobel_pma_plan_wide(S, A, 0, C.byref(out)) != _lib.OK:
+            raise NotImplementedError(
+                'PMAMemory(wide=True): %d states and %d actions — the default form serves up to %d '
+                'states and %d actions, the wide form up to %d states within 160 KiB of LDS (%s)'
+                % (S, A, _lib.PMA_MAX_STATES, _lib.PMA_MAX_ACTIONS, _lib.PMA_WIDE_MAX_STATES,
+                   _lib.lib().cobel_last_error().decode('utf-8', 'replace')))
+
     rewards, states, terminals = _table('rewards'), _table('states'), _table('terminals')
     T, SR, update_mask = _table('T'), _table('SR'), _table('update_mask')
 
@@ -118,6 +138,14 @@ class PMAMemory:
         if self._dev is not None:
             assert self.n_envs == n_envs, 'a memory stays bound to the instance count it first saw'
             return
+        if self.wide and torch.device(device).type == 'cuda':
+            need = n_envs * self.nb_states ** 2 * 16
+            free = torch.cuda.mem_get_info(device)[0]
+            if need > free:
+                raise MemoryError(
+                    'PMAMemory(wide=True): T and SR of %d instances of %d states take %d bytes '
+                    '(%.1f GiB), %d bytes of device memory are free'
+                    % (n_envs, self.nb_states, need, need / 2.0 ** 30, free))
         dev = {}
         for name, (tdt, _) in _TABLES.items():
             h = np.ascontiguousarray(self._host[name])
@@ -155,7 +183,8 @@ class PMAMemory:
                 (_lib.PMA_EQUAL_GAIN if self.equal_gain else 0) |
                 (_lib.PMA_IGNORE_BARRIERS if self.ignore_barriers else 0) |
                 (_lib.PMA_ALLOW_LOOPS if self.allow_loops else 0) |
-                (_lib.PMA_GAIN_ORIGINAL if self.min_gain_mode == 'original' else 0))
+                (_lib.PMA_GAIN_ORIGINAL if self.min_gain_mode == 'original' else 0) |
+                (_lib.PMA_WIDE if self.wide else 0))
 
     def _mem(self, q=None, mask_bits=None, length: int = 0):
         assert self._dev is not None, \
@@ -182,8 +211,8 @@ class PMAMemory:
     def launch_plan(self, replay_length: int = 32) -> list:
         """(LDS bytes, threads) of a replay / trial workgroup and of an update_sr workgroup."""
         out = (C.c_int32 * 4)()
-        _lib.check(_lib.lib().cobel_pma_plan(self.nb_states, self.nb_actions, int(replay_length),
-                                             C.byref(out)))
+        plan = _lib.lib().cobel_pma_plan_wide if self.wide else _lib.lib().cobel_pma_plan
+        _lib.check(plan(self.nb_states, self.nb_actions, int(replay_length), C.byref(out)))
         return list(out)
 
     def _per_instance(self, value, name: str, limit: int):

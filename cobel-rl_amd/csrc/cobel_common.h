@@ -134,6 +134,10 @@ const char* cobel_debug_env(const char* name);
 size_t cobel_dqn_replay_lds_bytes(int32_t n_inputs, int32_t is_float64);
 int cobel_dqn_replay_lds_launch(const cobel_dqn_replay_t& r, hipStream_t st,
                                 unsigned long long* trace /* experiments, or NULL */);
+// pma_sr.hip: PMAMemory.update_sr by the blocked kernels on the SR blocks in global memory (any S;
+// cobel_pma_update_sr, pma.hip, dispatches), and the LDS of their largest workgroup
+int cobel_pma_sr_blocked(const cobel_pma_mem_t& m, hipStream_t st);
+size_t cobel_pma_sr_blocked_lds();
 int cobel_world_check(const cobel_world* w, const char* who);   // non-NULL, on the current device
 int cobel_world_check4(const cobel_world* w, const char* who);  // ... and a four-action world
 

@@ -15,33 +15,58 @@
 //              again for the position of that tie
 //   update     the n-step update_q: targets by lane, applied in sequence order
 // k_pma_update_sr: one workgroup of 256 lanes per instance, I - gamma T in LDS, in-place
-// Gauss-Jordan without pivoting.
+// Gauss-Jordan without pivoting (up to 128 states; beyond: pma_sr.hip).
+// The replay and trial kernels come in two forms, narrow (the default, up to 128 states) and wide
+// (COBEL_PMA_WIDE, up to 1 024 states): see pma_narrow / pma_wide below.
 //
 // Reference behaviour restated (paths relative to the reference's src/cobel):
 //   memory/pma.py:148-166 (store), :168-267 (replay), :269-331 (compute_gain), :333-386
 //   (compute_gain_batch), :388-411 (compute_need), :413-415 (update_sr), :423-450
 //   (action_probs_batch), :452-496 (update_q); agent/pma.py:167-258 (train), :260-317 (test),
 //   :319-353 (update_q); policy/greedy.py:40-88
+#include <cstring>
+
 #include "cobel_common.h"
 #include "cobel_policy.h"
 
 namespace {
 
-constexpr int kMaxS = COBEL_PMA_MAX_STATES;
 constexpr int kMaxA = COBEL_PMA_MAX_ACTIONS;
-constexpr int kLdsLimit = 64 * 1024;
 constexpr int kSrThreads = 256;
 
+// The two forms of the replay / trial kernels.  They differ in how a performed update is packed
+// into its 32-bit record, in the type that holds a successor state and in the LDS they may ask
+// for; every arithmetic expression, summation order and draw is the same code.
+//   narrow  state:8 | action:8 | next_state:8 | terminal:8     ns uint8_t    64 KiB
+//   wide    state:10 | action:3 | next_state:10 | terminal:9   ns uint16_t  160 KiB
+// (selected by COBEL_PMA_WIDE in cobel_pma_mem_t.flags; the narrow form is the default)
+struct pma_narrow {
+  using ns_t = uint8_t;
+  static constexpr int kMaxS = COBEL_PMA_MAX_STATES, kLdsLimit = 64 * 1024;
+  static constexpr int kShA = 8, kShN = 16, kShT = 24;
+  static constexpr uint32_t kMaskS = 0xffu, kMaskA = 0xffu;
+};
+struct pma_wide {
+  using ns_t = uint16_t;
+  static constexpr int kMaxS = COBEL_PMA_WIDE_MAX_STATES, kLdsLimit = 160 * 1024;
+  static constexpr int kShA = 10, kShN = 13, kShT = 23;
+  static constexpr uint32_t kMaskS = 0x3ffu, kMaskA = 7u;
+};
+
 // the LDS of one instance
+template <class F>
 struct pma_lds {
   double *Q, *R, *U, *need, *sg, *rr;   // [SA] [SA] [SA] [S] [L + 1] [L]
-  uint32_t* rec;                        // [L] state | action << 8 | next_state << 16 | terminal << 24
-  uint8_t *ns, *tm, *um, *am;           // [SA] [SA] [A * S] [S]
+  uint32_t* rec;                        // [L] the performed updates, packed as F says
+  typename F::ns_t* ns;                 // [SA]
+  uint8_t *tm, *um, *am;                // [SA] [A * S] [S]
 };
-__host__ __device__ inline size_t pma_lds_carve(unsigned char* base, int S, int A, int L, pma_lds* out) {
+template <class F>
+__host__ __device__ inline size_t pma_lds_carve(unsigned char* base, int S, int A, int L,
+                                                pma_lds<F>* out) {
   const size_t SA = (size_t)S * A;
   size_t o = 0;
-  pma_lds l;
+  pma_lds<F> l;
   l.Q = (double*)(base + o); o += 8 * SA;
   l.R = (double*)(base + o); o += 8 * SA;
   l.U = (double*)(base + o); o += 8 * SA;
@@ -49,7 +74,7 @@ __host__ __device__ inline size_t pma_lds_carve(unsigned char* base, int S, int 
   l.sg = (double*)(base + o); o += 8 * (size_t)(L + 1);
   l.rr = (double*)(base + o); o += 8 * (size_t)(L > 0 ? L : 1);
   l.rec = (uint32_t*)(base + o); o += 8 * (size_t)((L + 2) / 2);
-  l.ns = base + o; o += SA;
+  l.ns = (typename F::ns_t*)(base + o); o += sizeof(typename F::ns_t) * SA;
   l.tm = base + o; o += SA;
   l.um = base + o; o += SA;
   l.am = base + o; o += (size_t)((S + 7) & ~7);
@@ -157,18 +182,30 @@ struct pma_hyper {
   const double *gpow, *gqpow;
 };
 
-__device__ __forceinline__ uint32_t mask_of(const pma_lds& l, const pma_hyper& h, bool masked, int s) {
+template <class F>
+__device__ __forceinline__ uint32_t mask_of(const pma_lds<F>& l, const pma_hyper& h, bool masked, int s) {
   return masked ? (uint32_t)l.am[s] : 0xffu;
 }
-__device__ __forceinline__ uint32_t rec_pack(const pma_lds& l, const pma_hyper& h, int idx) {
+template <class F>
+__device__ __forceinline__ uint32_t rec_pack(const pma_lds<F>& l, const pma_hyper& h, int idx) {
   const int a = idx / h.S, s = idx - a * h.S;
   const int c = s * h.A + a;
-  return (uint32_t)s | ((uint32_t)a << 8) | ((uint32_t)l.ns[c] << 16) | ((uint32_t)l.tm[c] << 24);
+  return (uint32_t)s | ((uint32_t)a << F::kShA) | ((uint32_t)l.ns[c] << F::kShN) |
+         ((uint32_t)l.tm[c] << F::kShT);
 }
+template <class F>
+__device__ __forceinline__ int rec_state(uint32_t rc) { return (int)(rc & F::kMaskS); }
+template <class F>
+__device__ __forceinline__ int rec_action(uint32_t rc) { return (int)((rc >> F::kShA) & F::kMaskA); }
+template <class F>
+__device__ __forceinline__ int rec_next(uint32_t rc) { return (int)((rc >> F::kShN) & F::kMaskS); }
+template <class F>
+__device__ __forceinline__ uint32_t rec_terminal(uint32_t rc) { return rc >> F::kShT; }
 
 // One replay of L rounds on the LDS tables (memory/pma.py:199-267).  cm: the memory's draw counter,
 // cq: its policy's.  Leaves the performed updates in l.rec / l.rr.
-__device__ __forceinline__ void pma_replay_body(const pma_lds& l, const pma_hyper& h, bool masked,
+template <class F>
+__device__ __forceinline__ void pma_replay_body(const pma_lds<F>& l, const pma_hyper& h, bool masked,
                                                 int L, int force_first, uint32_t& cm, uint32_t& cq,
                                                 int lane) {
   const int S = h.S, A = h.A, SA = h.SA;
@@ -180,12 +217,12 @@ __device__ __forceinline__ void pma_replay_body(const pma_lds& l, const pma_hype
     // ---- the sequence to extend ---------------------------------------------------------------
     int ext = -1, base = upd;   // base: first performed update of the candidate sequence
     if (upd > 0) {
-      const int es = (int)((l.rec[upd - 1] >> 16) & 0xffu);
+      const int es = rec_next<F>(l.rec[upd - 1]);
       ext = es;
       bool loop = false;
       for (int j0 = last_seq; j0 < upd; j0 += 64) {
         const int j = j0 + lane;
-        const bool hit = j < upd && (int)(l.rec[j] & 0xffu) == es;
+        const bool hit = j < upd && rec_state<F>(l.rec[j]) == es;
         loop = loop || (__ballot(hit) != 0ull);
       }
       if (!loop || loops) {
@@ -207,10 +244,10 @@ __device__ __forceinline__ void pma_replay_body(const pma_lds& l, const pma_hype
       wsync();
       const int n = upd - base + 1;
       const uint32_t lastrec = l.rec[upd];
-      const double fv = max_row(l.Q, (int)((lastrec >> 16) & 0xffu), A) * (double)(lastrec >> 24);
+      const double fv = max_row(l.Q, rec_next<F>(lastrec), A) * (double)rec_terminal<F>(lastrec);
       for (int j = lane; j < n; j += 64) {
         const uint32_t rc = l.rec[base + j];
-        const int st = (int)(rc & 0xffu), a = (int)((rc >> 8) & 0xffu);
+        const int st = rec_state<F>(rc), a = rec_action<F>(rc);
         double r = 0.0;
         for (int k = 0; k < n - j; ++k) r += l.rr[base + j + k] * h.gpow[k];
         const double tgt = r + fv * h.gqpow[n - j];
@@ -306,11 +343,11 @@ __device__ __forceinline__ void pma_replay_body(const pma_lds& l, const pma_hype
       if (n > 1)
         for (int j0 = 0; j0 < n; j0 += 64) {
           const int j = j0 + lane;
-          abort_all = abort_all || (__ballot(j < n && (l.rec[from + j] >> 24) == 0u) != 0ull);
+          abort_all = abort_all || (__ballot(j < n && rec_terminal<F>(l.rec[from + j]) == 0u) != 0ull);
         }
       if (!abort_all) {
         const uint32_t lastrec = l.rec[upd];
-        const double fv = max_row(l.Q, (int)((lastrec >> 16) & 0xffu), A) * (double)(lastrec >> 24);
+        const double fv = max_row(l.Q, rec_next<F>(lastrec), A) * (double)rec_terminal<F>(lastrec);
         for (int j = lane; j < n; j += 64) {
           double r = 0.0;
           for (int kk = 0; kk < n - j; ++kk) r += l.rr[from + j + kk] * h.gqpow[kk];
@@ -319,7 +356,7 @@ __device__ __forceinline__ void pma_replay_body(const pma_lds& l, const pma_hype
         wsync();
         for (int j = 0; j < n; ++j) {
           const uint32_t rc = l.rec[from + j];
-          const int cell = (int)(rc & 0xffu) * A + (int)((rc >> 8) & 0xffu);
+          const int cell = rec_state<F>(rc) * A + rec_action<F>(rc);
           const double qv = l.Q[cell];
           const double td = l.sg[j] - qv;
           const double nv = qv + h.lrq * td;
@@ -351,33 +388,37 @@ __device__ __forceinline__ void fill_hyper(const cobel_pma_mem_t& m, int i, pma_
 
 // the instance's tables into LDS (states and terminals clamped to what the layout holds: a table
 // edited by hand must not send a row read outside the instance's slice)
-__device__ __forceinline__ void load_tables(const cobel_pma_mem_t& m, int i, const pma_lds& l,
+template <class F>
+__device__ __forceinline__ void load_tables(const cobel_pma_mem_t& m, int i, const pma_lds<F>& l,
                                             const pma_hyper& h, int lane) {
   const size_t off = (size_t)i * h.SA;
   for (int c = lane; c < h.SA; c += 64) {
     l.Q[c] = m.q[off + c];
     l.R[c] = m.rewards[off + c];
     const int ns = m.states[off + c];
-    l.ns[c] = (uint8_t)(ns < 0 ? 0 : (ns >= h.S ? h.S - 1 : ns));
+    l.ns[c] = (typename F::ns_t)(ns < 0 ? 0 : (ns >= h.S ? h.S - 1 : ns));
     const int tm = m.terminals[off + c];
     l.tm[c] = (uint8_t)(tm < 0 ? 0 : (tm > 255 ? 255 : tm));
     l.um[c] = m.update_mask[off + c];
   }
   for (int s = lane; s < h.S; s += 64) l.am[s] = m.action_mask ? m.action_mask[s] : (uint8_t)0xff;
 }
-__device__ __forceinline__ void store_records(const pma_lds& l, cobel_pma_rec_t* out, int L, int lane) {
+template <class F>
+__device__ __forceinline__ void store_records(const pma_lds<F>& l, cobel_pma_rec_t* out, int L,
+                                              int lane) {
   for (int j = lane; j < L; j += 64) {
     const uint32_t rc = l.rec[j];
     cobel_pma_rec_t e;
-    e.state = (int32_t)(rc & 0xffu);
-    e.action = (int32_t)((rc >> 8) & 0xffu);
-    e.next_state = (int32_t)((rc >> 16) & 0xffu);
-    e.terminal = (int32_t)(rc >> 24);
+    e.state = (int32_t)rec_state<F>(rc);
+    e.action = (int32_t)rec_action<F>(rc);
+    e.next_state = (int32_t)rec_next<F>(rc);
+    e.terminal = (int32_t)rec_terminal<F>(rc);
     e.reward = l.rr[j];
     out[j] = e;
   }
 }
 
+template <class F>
 __global__ __launch_bounds__(64) void k_pma_replay(const pma_args P) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   const int lane = (int)threadIdx.x;
@@ -385,7 +426,7 @@ __global__ __launch_bounds__(64) void k_pma_replay(const pma_args P) {
   const cobel_pma_mem_t& m = P.m;
   pma_hyper h;
   fill_hyper(m, i, &h);
-  pma_lds l;
+  pma_lds<F> l;
   pma_lds_carve(lds_raw, h.S, h.A, P.L, &l);
   load_tables(m, i, l, h, lane);
   int cs = P.current_state ? P.current_state[i] : -1;
@@ -409,6 +450,7 @@ __global__ __launch_bounds__(64) void k_pma_replay(const pma_args P) {
   }
 }
 
+template <class F>
 __global__ __launch_bounds__(64) void k_pma_trial(const pma_trial_args G) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   const int lane = (int)threadIdx.x;
@@ -426,7 +468,7 @@ __global__ __launch_bounds__(64) void k_pma_trial(const pma_trial_args G) {
   const uint32_t act_stream =
       (flags & COBEL_F_TEST_STREAM) ? COBEL_STREAM_POLICY_TEST : COBEL_STREAM_POLICY;
   if (shared) h.pol_stream = act_stream;
-  pma_lds l;
+  pma_lds<F> l;
   pma_lds_carve(lds_raw, S, A, L, &l);
   load_tables(m, i, l, h, lane);
 
@@ -499,7 +541,7 @@ __global__ __launch_bounds__(64) void k_pma_trial(const pma_trial_args G) {
       if (lane == 0) {
         l.Q[c] = nq;
         l.R[c] = nr;
-        l.ns[c] = (uint8_t)ns;
+        l.ns[c] = (typename F::ns_t)ns;
         l.tm[c] = (uint8_t)nt;
         m.rewards[off + c] = nr;
         m.states[off + c] = ns;
@@ -610,13 +652,35 @@ __global__ __launch_bounds__(kSrThreads) void k_pma_update_sr(const cobel_pma_me
 
 size_t sr_lds_bytes(int S) { return 8 * ((size_t)S * S + 2 * (size_t)S); }
 
+bool is_wide(const cobel_pma_mem_t& m) { return (m.flags & COBEL_PMA_WIDE) != 0; }
+size_t carve_bytes(bool wide, int S, int A, int L) {
+  return wide ? pma_lds_carve<pma_wide>(nullptr, S, A, L, nullptr)
+              : pma_lds_carve<pma_narrow>(nullptr, S, A, L, nullptr);
+}
+// update_sr through the blocked kernels (pma_sr.hip): every world past the LDS kernel's, and any
+// world under COBEL_DEBUG_PMA_SR=blocked (tests: the two paths agree bit for bit)
+bool sr_blocked(int S) {
+  if (S > pma_narrow::kMaxS) return true;
+  const char* const v = cobel_debug_env("COBEL_DEBUG_PMA_SR");
+  return v && !strcmp(v, "blocked");
+}
+
 int check_mem(const cobel_pma_mem_t* mem, const char* who, bool replay) {
   COBEL_REQUIRE(mem, COBEL_E_ARG, "%s: NULL mem", who);
   const cobel_pma_mem_t& m = *mem;
-  COBEL_REQUIRE(m.n_states >= 1 && m.n_states <= kMaxS && m.n_actions >= 1 && m.n_actions <= kMaxA,
-                COBEL_E_UNSUPPORTED,
-                "%s: %d states, %d actions (PMA serves up to %d states and %d actions)", who,
-                m.n_states, m.n_actions, kMaxS, kMaxA);
+  if (is_wide(m))
+    COBEL_REQUIRE(m.n_states >= 1 && m.n_states <= pma_wide::kMaxS && m.n_actions >= 1 &&
+                      m.n_actions <= kMaxA,
+                  COBEL_E_UNSUPPORTED,
+                  "%s: %d states, %d actions (PMA serves up to %d states and %d actions, its wide "
+                  "form up to %d states)",
+                  who, m.n_states, m.n_actions, pma_narrow::kMaxS, kMaxA, pma_wide::kMaxS);
+  else
+    COBEL_REQUIRE(m.n_states >= 1 && m.n_states <= pma_narrow::kMaxS && m.n_actions >= 1 &&
+                      m.n_actions <= kMaxA,
+                  COBEL_E_UNSUPPORTED,
+                  "%s: %d states, %d actions (PMA serves up to %d states and %d actions)", who,
+                  m.n_states, m.n_actions, pma_narrow::kMaxS, kMaxA);
   COBEL_REQUIRE(m.n >= 0, COBEL_E_RANGE, "%s: n = %d", who, m.n);
   COBEL_REQUIRE(m.rewards && m.states && m.terminals && m.T && m.SR, COBEL_E_ARG,
                 "%s: rewards, states, terminals, T and SR are required", who);
@@ -637,10 +701,11 @@ int check_mem(const cobel_pma_mem_t* mem, const char* who, bool replay) {
 
 int replay_lds(const cobel_pma_mem_t& m, int L, const char* who, size_t* lds) {
   COBEL_REQUIRE(L >= 0, COBEL_E_RANGE, "%s: replay_length = %d", who, L);
-  *lds = pma_lds_carve(nullptr, m.n_states, m.n_actions, L, nullptr);
-  COBEL_REQUIRE(*lds <= (size_t)kLdsLimit, COBEL_E_UNSUPPORTED,
-                "%s: a replay of %d rounds needs %zu B of LDS (%d are served)", who, L, *lds,
-                kLdsLimit);
+  const bool wide = is_wide(m);
+  const int limit = wide ? pma_wide::kLdsLimit : pma_narrow::kLdsLimit;
+  *lds = carve_bytes(wide, m.n_states, m.n_actions, L);
+  COBEL_REQUIRE(*lds <= (size_t)limit, COBEL_E_UNSUPPORTED,
+                "%s: a replay of %d rounds needs %zu B of LDS (%d are served)", who, L, *lds, limit);
   COBEL_REQUIRE(m.pow_len > L, COBEL_E_ARG, "%s: the power tables hold %d entries, %d are needed",
                 who, m.pow_len, L + 1);
   return COBEL_OK;
@@ -652,19 +717,45 @@ extern "C" int cobel_pma_plan(int32_t n_states, int32_t n_actions, int32_t repla
                               int32_t out[4]) {
   COBEL_REQUIRE(out, COBEL_E_ARG, "cobel_pma_plan: NULL out");
   out[0] = out[1] = out[2] = out[3] = 0;
-  COBEL_REQUIRE(n_states >= 1 && n_states <= kMaxS && n_actions >= 1 && n_actions <= kMaxA,
+  COBEL_REQUIRE(n_states >= 1 && n_states <= pma_narrow::kMaxS && n_actions >= 1 &&
+                    n_actions <= kMaxA,
                 COBEL_E_UNSUPPORTED,
                 "cobel_pma_plan: %d states, %d actions (PMA serves up to %d states and %d actions)",
-                n_states, n_actions, kMaxS, kMaxA);
+                n_states, n_actions, pma_narrow::kMaxS, kMaxA);
   COBEL_REQUIRE(replay_length >= 0, COBEL_E_RANGE, "cobel_pma_plan: replay_length = %d",
                 replay_length);
-  const size_t lds = pma_lds_carve(nullptr, n_states, n_actions, replay_length, nullptr);
-  COBEL_REQUIRE(lds <= (size_t)kLdsLimit, COBEL_E_UNSUPPORTED,
+  const size_t lds = carve_bytes(false, n_states, n_actions, replay_length);
+  COBEL_REQUIRE(lds <= (size_t)pma_narrow::kLdsLimit, COBEL_E_UNSUPPORTED,
                 "cobel_pma_plan: a replay of %d rounds needs %zu B of LDS (%d are served)",
-                replay_length, lds, kLdsLimit);
+                replay_length, lds, pma_narrow::kLdsLimit);
   out[0] = (int32_t)lds;
   out[1] = 64;
   out[2] = (int32_t)sr_lds_bytes(n_states);
+  out[3] = kSrThreads;
+  return COBEL_OK;
+}
+
+extern "C" int cobel_pma_plan_wide(int32_t n_states, int32_t n_actions, int32_t replay_length,
+                                   int32_t out[4]) {
+  COBEL_REQUIRE(out, COBEL_E_ARG, "cobel_pma_plan_wide: NULL out");
+  out[0] = out[1] = out[2] = out[3] = 0;
+  COBEL_REQUIRE(n_states >= 1 && n_states <= pma_wide::kMaxS && n_actions >= 1 && n_actions <= kMaxA,
+                COBEL_E_UNSUPPORTED,
+                "cobel_pma_plan_wide: %d states, %d actions (PMA serves up to %d states and %d "
+                "actions, its wide form up to %d states)",
+                n_states, n_actions, pma_narrow::kMaxS, kMaxA, pma_wide::kMaxS);
+  COBEL_REQUIRE(replay_length >= 0, COBEL_E_RANGE, "cobel_pma_plan_wide: replay_length = %d",
+                replay_length);
+  const size_t lds = carve_bytes(true, n_states, n_actions, replay_length);
+  COBEL_REQUIRE(lds <= (size_t)pma_wide::kLdsLimit, COBEL_E_UNSUPPORTED,
+                "cobel_pma_plan_wide: %d states, %d actions and a replay of %d rounds need %zu B of "
+                "LDS (the wide form serves %d B, the narrow form %d B up to %d states)",
+                n_states, n_actions, replay_length, lds, pma_wide::kLdsLimit, pma_narrow::kLdsLimit,
+                pma_narrow::kMaxS);
+  out[0] = (int32_t)lds;
+  out[1] = 64;
+  const bool blocked = sr_blocked(n_states);
+  out[2] = (int32_t)(blocked ? cobel_pma_sr_blocked_lds() : sr_lds_bytes(n_states));
   out[3] = kSrThreads;
   return COBEL_OK;
 }
@@ -690,8 +781,8 @@ extern "C" int cobel_pma_replay(const cobel_pma_mem_t* mem, int32_t replay_lengt
   P.need = need;
   P.force_first = force_first;
   P.records = records;
-  COBEL_HIP_TRY(cobel_launch(k_pma_replay, dim3((unsigned)mem->n), dim3(64), lds,
-                             (hipStream_t)stream, P));
+  COBEL_HIP_TRY(cobel_launch(is_wide(*mem) ? k_pma_replay<pma_wide> : k_pma_replay<pma_narrow>,
+                             dim3((unsigned)mem->n), dim3(64), lds, (hipStream_t)stream, P));
   return COBEL_OK;
 }
 
@@ -725,11 +816,12 @@ extern "C" int cobel_pma_trial(const cobel_world_t* world, const cobel_pma_mem_t
   G.succ_state = world->succ_state;
   G.succ_cdf = world->succ_cdf;
   G.n_worlds = world->n_worlds;
-  COBEL_HIP_TRY(cobel_launch(k_pma_trial, dim3((unsigned)mem->n), dim3(64), lds,
-                             (hipStream_t)stream, G));
+  COBEL_HIP_TRY(cobel_launch(is_wide(*mem) ? k_pma_trial<pma_wide> : k_pma_trial<pma_narrow>,
+                             dim3((unsigned)mem->n), dim3(64), lds, (hipStream_t)stream, G));
   return COBEL_OK;
 }
 
+// (the store kernel reads 32-bit states from the experience and writes 32-bit tables: one form)
 extern "C" int cobel_pma_store(const cobel_pma_mem_t* mem, const cobel_pma_exp_t* experiences,
                                void* stream) {
   if (int rc = check_mem(mem, "cobel_pma_store", false)) return rc;
@@ -745,6 +837,7 @@ extern "C" int cobel_pma_store(const cobel_pma_mem_t* mem, const cobel_pma_exp_t
 extern "C" int cobel_pma_update_sr(const cobel_pma_mem_t* mem, void* stream) {
   if (int rc = check_mem(mem, "cobel_pma_update_sr", false)) return rc;
   if (mem->n == 0) return COBEL_OK;
+  if (sr_blocked(mem->n_states)) return cobel_pma_sr_blocked(*mem, (hipStream_t)stream);
   COBEL_HIP_TRY(cobel_launch(k_pma_update_sr, dim3((unsigned)mem->n), dim3(kSrThreads),
                              sr_lds_bytes(mem->n_states), (hipStream_t)stream, *mem));
   return COBEL_OK;

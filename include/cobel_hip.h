@@ -1046,7 +1046,11 @@ COBEL_API int cobel_dqn_act(const cobel_world_t* world, const cobel_dqn_act_t* r
  * (memory/pma.py:168-267, :148-166, :413-415) and the trial loop of PMA.train / PMA.test
  * (agent/pma.py:167-317).  Every table is float64, as the reference's are: the gain is a
  * difference of nearly equal sums clipped at min_gain and the selection an exact-equality tie
- * test.  Worlds of up to COBEL_PMA_MAX_STATES states and COBEL_PMA_MAX_ACTIONS actions.
+ * test.  Worlds of up to COBEL_PMA_MAX_STATES states and COBEL_PMA_MAX_ACTIONS actions; with
+ * COBEL_PMA_WIDE in cobel_pma_mem_t.flags the wide form, up to COBEL_PMA_WIDE_MAX_STATES states
+ * (10-bit states in the replay records, 16-bit successors, up to 160 KiB of LDS per instance, and
+ * update_sr by blocked kernels on the SR block in global memory).  The wide form is opt-in: T and
+ * SR cost 8 * S * S bytes each per instance, 8 MiB each at 1 024 states.
  * Tables per instance: Q, rewards f64 [S][A]; states, terminals i32 [S][A]; T, SR f64 [S][S];
  * update_mask u8 [A * S], experience index a * S + s as in the reference.
  * Draws: the memory's generator is COBEL_STREAM_PMA_MEMORY at mem_ctr[i] — one double (sub-stream
@@ -1058,6 +1062,7 @@ COBEL_API int cobel_dqn_act(const cobel_world_t* world, const cobel_dqn_act_t* r
 #define COBEL_STREAM_PMA_POLICY 6u /* c = select_action calls of PMAMemory.policy (memory/pma.py:232) */
 #define COBEL_PMA_MAX_STATES 128
 #define COBEL_PMA_MAX_ACTIONS 8
+#define COBEL_PMA_WIDE_MAX_STATES 1024
 #define COBEL_PMA_EQUAL_NEED 1u        /* PMAMemory.equal_need                                   */
 #define COBEL_PMA_EQUAL_GAIN 2u        /* PMAMemory.equal_gain                                   */
 #define COBEL_PMA_IGNORE_BARRIERS 4u   /* PMAMemory.ignore_barriers (default on)                 */
@@ -1065,6 +1070,9 @@ COBEL_API int cobel_dqn_act(const cobel_world_t* world, const cobel_dqn_act_t* r
 #define COBEL_PMA_GAIN_ORIGINAL 16u    /* PMAMemory.min_gain_mode == 'original'                  */
 #define COBEL_PMA_SHARED_POLICY 32u    /* cobel_pma_trial: the memory's policy IS the agent's: its
                                           extension draws continue inst[COBEL_I_CTR_POLICY]         */
+#define COBEL_PMA_WIDE 64u             /* cobel_pma_mem_t.flags: the wide form (cobel_pma_plan_wide
+                                          says what it serves); clear: every call behaves and
+                                          refuses as the narrow form does                           */
 
 typedef struct {
   double* q;                  /* [N][S][A] the Q-function the replay updates                    */
@@ -1119,6 +1127,12 @@ typedef struct {
  * of a replay of that length no longer fits 64 KiB of LDS beside the tables. */
 COBEL_API int cobel_pma_plan(int32_t n_states, int32_t n_actions, int32_t replay_length,
                              int32_t out[4]);
+/* The same for the wide form (COBEL_PMA_WIDE): COBEL_E_UNSUPPORTED beyond
+ * COBEL_PMA_WIDE_MAX_STATES / COBEL_PMA_MAX_ACTIONS, or where the tables and the sequence do not
+ * fit 160 KiB of LDS (1 024 states with 8 actions do not; the message gives the byte counts).
+ * out[2] / out[3] are those of the blocked update_sr kernels beyond COBEL_PMA_MAX_STATES states. */
+COBEL_API int cobel_pma_plan_wide(int32_t n_states, int32_t n_actions, int32_t replay_length,
+                                  int32_t out[4]);
 /* PMAMemory.replay (memory/pma.py:168-267) once per instance on mem->q: replay_length rounds of
  * compute_gain_batch (:333-386) / compute_gain (:269-331) for the extended sequence, utility =
  * gain * need * update_mask, the draw among exact ties (:251-254), force_first (:256-259), the
@@ -1140,7 +1154,9 @@ COBEL_API int cobel_pma_trial(const cobel_world_t* world, const cobel_pma_mem_t*
 COBEL_API int cobel_pma_store(const cobel_pma_mem_t* mem, const cobel_pma_exp_t* experiences,
                               void* stream);
 /* PMAMemory.update_sr (memory/pma.py:413-415): SR = inv(I - gamma T) per instance, in-place
- * Gauss-Jordan without pivoting (I - gamma T is strictly diagonally dominant by rows). */
+ * Gauss-Jordan without pivoting (I - gamma T is strictly diagonally dominant by rows): in LDS up
+ * to COBEL_PMA_MAX_STATES states, beyond (wide form) blocked over panels of 32 pivots on the SR
+ * block in global memory, the same operations per element in the same order. */
 COBEL_API int cobel_pma_update_sr(const cobel_pma_mem_t* mem, void* stream);
 
 #ifdef __cplusplus
