@@ -17,11 +17,20 @@ from __future__ import annotations
 
 import abc
 import copy
+import functools
 
 import numpy as np
 import torch
 
 from .. import _lib
+from ..memory import _device
+
+
+@functools.lru_cache(maxsize=None)
+def _declared(struct_class, names: tuple) -> tuple:
+    """Those of ``names`` a ctypes struct class declares as fields (looked up once per class: a
+    launcher runs once per env step in per-step callback mode)."""
+    return tuple(n for n in names if hasattr(struct_class, n))
 
 
 class Callbacks:
@@ -83,7 +92,8 @@ class DeviceMonitors:
     kernel adds into copy ``b % stripes``, see ``cobel_tab_run_t.mon_stripes``); ``lat_sum`` /
     ``lat_cnt`` / ``reward_sum`` / ``resp_cnt`` are the sums over the copies, ``raw(name)`` the
     striped tensors the kernels take.  With one stripe the attribute IS the tensor (in-place ops
-    on it are seen by the kernels)."""
+    on it are seen by the kernels).  ``fill(struct)`` is the one place that writes them into a
+    launch struct."""
 
     _PER_TRIAL = {'lat_sum': torch.int64, 'lat_cnt': torch.int64, 'reward_sum': torch.float64,
                   'resp_cnt': torch.int64}
@@ -104,6 +114,17 @@ class DeviceMonitors:
     def raw(self, name: str):
         """The striped tensor ``[stripes, cap]`` handed to the kernels (or None)."""
         return self._raw[name]
+
+    _POINTERS = tuple(_PER_TRIAL) + ('lat_trace', 'occupancy', 'steps_done')
+
+    def fill(self, struct) -> None:
+        """Write the monitor fields a launch struct declares (``cobel_dqn_act_t`` has five): the
+        raw striped per-trial arrays, ``lat_trace``, ``occupancy``, ``steps_done`` (NULL where a
+        monitor is off), ``trial_cap`` and ``mon_stripes``."""
+        raw = self._raw
+        for name in _declared(type(struct), self._POINTERS):
+            setattr(struct, name, _lib.ptr(raw[name] if name in raw else getattr(self, name)))
+        struct.trial_cap, struct.mon_stripes = self.cap, self.stripes
 
     def _get(self, name: str):
         t = self._raw[name]
@@ -262,7 +283,9 @@ class MonitorSums:
 
 
 class FusedAgent(Agent):
-    """Plumbing common to the agents whose whole loop runs in one kernel."""
+    """Plumbing common to the agents whose whole loop runs in one kernel: the device state, the
+    trial driver (``_session``, or its two halves around a loop of the agent's own) and
+    ``_fill_run``, where a launcher starts (it adds its tables, flags and hyper-parameters)."""
 
     general_actions = False    # True: the agent also runs on action counts other than four
 
@@ -288,7 +311,7 @@ class FusedAgent(Agent):
         self.n_envs = None
         self.inst = None
         self.monitors = None
-        self._last_exp = None
+        self._last_exp = self._mask_dev = None
         self._pset_key = self._pset_dev = self._pidx_dev = None
         self._pset_n = 0
 
@@ -384,14 +407,29 @@ class FusedAgent(Agent):
         ...
 
     def _mask_bits(self):
-        m = np.asarray(self.action_mask, dtype=bool).reshape(self.n_states, self.n_actions)
-        assert m.any(axis=1).all(), 'The action mask masks all actions!'
-        # (one byte per state up to eight actions, one 32-bit word beyond: cobel_hip.h)
-        bits = (m * (1 << np.arange(self.n_actions, dtype=np.int64))).sum(axis=1)
-        bits = bits.astype(np.uint8 if self.n_actions <= 8 else np.uint32)
-        if self.n_actions > 8:
-            bits = bits.view(np.int32)
-        return torch.as_tensor(bits, device=self.device)
+        return torch.as_tensor(_device.mask_bits(self.action_mask, self.n_states, self.n_actions),
+                               device=self.device)
+
+    _RUN_FIELDS = ('inst', 'action_mask', 'last_exp', 'n', 'instance_base', 'seed',
+                   'trials_target', 'steps_per_trial', 'step_budget')
+
+    def _fill_run(self, run, interface, flags: int, trials_target: int, steps: int,
+                  budget: int) -> None:
+        """What every launch struct says the same way, where ``run`` declares the field: the
+        monitors, the instance state, the action mask (built when ``flags`` has F_MASK_ACTIONS,
+        else NULL), ``last_exp`` (per-step launches only) and the session's scalars.  ``run.flags``
+        stays with the agent: each adds bits of its own."""
+        self.monitors.fill(run)
+        names = _declared(type(run), self._RUN_FIELDS)
+        if 'action_mask' in names:
+            self._mask_dev = self._mask_bits() if (flags & _lib.F_MASK_ACTIONS) else None
+        values = {'inst': _lib.ptr(self.inst), 'action_mask': _lib.ptr(self._mask_dev),
+                  'last_exp': _lib.ptr(self._last_exp) if budget == 1 else None,
+                  'n': self.n_envs, 'instance_base': interface.instance_base,
+                  'seed': interface.seed, 'trials_target': trials_target,
+                  'steps_per_trial': steps, 'step_budget': budget}
+        for name in names:
+            setattr(run, name, values[name])
 
     def _policy_in(self, pol, interface, test: bool) -> int:
         """Adopt the policy's stream + counter for a run; returns extra flags."""
@@ -438,10 +476,11 @@ class FusedAgent(Agent):
         """Called after the launch(es) of one trial in per-trial mode, before on_trial_end."""
         return logs
 
-    def _session(self, interface, trials: int, steps: int, batch: int, learn: bool,
-                 extra_flags: int = 0, pol=None) -> None:
+    def _session_begin(self, interface, trials: int, learn: bool, extra_flags: int = 0,
+                       pol=None):
+        """Head of a session; returns the acting policy, the launch flags and the first trial."""
         # (the reference's environments read their world at every step: an edit made since the last
-        #  call — or by a callback between two launches below — reaches the device tables here)
+        #  call — or by a callback between two launches of it — reaches the device tables here)
         interface.sync_world()
         self._bind(interface)
         if pol is None:
@@ -453,6 +492,20 @@ class FusedAgent(Agent):
         flags |= self._policy_in(pol, interface, not learn)
         first = self.current_trial
         self.monitors.reserve(first + trials, self.n_envs, self.track_instances)
+        return pol, flags, first
+
+    def _session_end(self, pol, interface) -> None:
+        self._policy_out(pol)
+        self._env_out(interface)
+        # (a sliced launch that gave up waiting for a ring entry leaves incomplete tables: raise here,
+        #  not when somebody happens to ask for the step count — the abort word is sticky)
+        check = getattr(self, 'check_launches', None)
+        if check is not None:
+            check()
+
+    def _session(self, interface, trials: int, steps: int, batch: int, learn: bool,
+                 extra_flags: int = 0, pol=None) -> None:
+        pol, flags, first = self._session_begin(interface, trials, learn, extra_flags, pol)
         per_step = self.n_envs == 1 and self.callbacks.has('on_step_begin', 'on_step_end')
         per_trial = self.n_envs == 1 and (per_step or self.callbacks.has('on_trial_begin',
                                                                          'on_trial_end'))
@@ -504,10 +557,4 @@ class FusedAgent(Agent):
                 logs = self.callbacks.on_trial_end(logs)
                 if self.stop:
                     break
-        self._policy_out(pol)
-        self._env_out(interface)
-        # (a sliced launch that gave up waiting for a ring entry leaves incomplete tables: raise here,
-        #  not when somebody happens to ask for the step count — the abort word is sticky)
-        check = getattr(self, 'check_launches', None)
-        if check is not None:
-            check()
+        self._session_end(pol, interface)

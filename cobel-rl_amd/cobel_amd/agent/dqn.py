@@ -299,12 +299,10 @@ class DQN(Agent):
         act.is_float64, act.epsilon = int(f64), float(pol.epsilon)
         act.trial, act.step, act.trial_reward = _lib.ptr(self.trial), _lib.ptr(step), _lib.ptr(trew)
         act.active, act.adam_steps = _lib.ptr(active), _lib.ptr(counts)
-        act.lat_sum, act.lat_cnt = _lib.ptr(mon.raw('lat_sum')), _lib.ptr(mon.raw('lat_cnt'))
-        act.reward_sum = _lib.ptr(mon.raw('reward_sum'))
+        mon.fill(act)
         act.stepped = _lib.ptr(stepped)
         act.n, act.n_obs, act.batch = n, table.shape[1], batch_size
         act.steps_per_trial, act.trials_target = steps, first + trials
-        act.trial_cap, act.mon_stripes = mon.cap, mon.stripes
         act.instance_base, act.seed = interface.instance_base, interface.seed
         lib = _lib.lib()
 

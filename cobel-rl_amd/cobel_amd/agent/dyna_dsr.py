@@ -286,11 +286,10 @@ class DynaDSR(DynaDQN):
         act.memory_ctr = _lib.ptr(M.counter)
         act.trial, act.step, act.trial_reward = _lib.ptr(self.trial), _lib.ptr(step), _lib.ptr(trew)
         act.active, act.adam_steps = _lib.ptr(active), _lib.ptr(unused_steps)
-        act.lat_sum, act.lat_cnt = _lib.ptr(mon.raw('lat_sum')), _lib.ptr(mon.raw('lat_cnt'))
-        act.reward_sum, act.stepped = _lib.ptr(mon.raw('reward_sum')), _lib.ptr(stepped)
+        mon.fill(act)
+        act.stepped = _lib.ptr(stepped)
         act.n, act.n_obs, act.batch = n, D, 32
         act.steps_per_trial, act.trials_target = steps, first + trials
-        act.trial_cap, act.mon_stripes = mon.cap, mon.stripes
         act.instance_base, act.seed = interface.instance_base, interface.seed
         act.model_rewards, act.model_states = _lib.ptr(M.rewards), _lib.ptr(M.states)
         act.model_nonterminal, act.model_lr = _lib.ptr(M.terminals), float(M.learning_rate)

@@ -18,6 +18,7 @@ import ctypes as C
 import torch
 
 from .. import _lib
+from ..memory import _device
 from ..memory.dyna_q import DynaQMemory, _is_array, pack_experiences
 from ..spaces import Discrete
 from .tabular import TabularAgent
@@ -93,9 +94,8 @@ class DynaQ(TabularAgent):
     def replay_plan(self, batch_size: int, n_batches: int = 1) -> dict:
         """What ``replay`` would launch (``cobel_dynaq_replay_plan``)."""
         run = self._table_run('replay_plan', int(batch_size))
-        out = (C.c_int32 * 4)()
-        _lib.check(_lib.lib().cobel_dynaq_replay_plan(self._handle.ptr, C.byref(run),
-                                                      int(n_batches), C.byref(out)))
+        out = _device.plan4(_lib.lib().cobel_dynaq_replay_plan, self._handle.ptr, C.byref(run),
+                            int(n_batches))
         return {'form': 'lane' if out[0] == _lib.REPLAY_LANE else 'wave', 'lds_bytes': int(out[1]),
                 'threads_per_workgroup': int(out[2]), 'instances_per_workgroup': int(out[3])}
 

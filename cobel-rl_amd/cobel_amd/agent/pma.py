@@ -13,7 +13,8 @@ replay, the steps with the 1-step update and the store), then ``M.update_sr()`` 
 method, then the end-of-trial replay with need from ``SR[last]``.  Instances whose trial timed out
 have no last state: their need is ``M.compute_need(None)`` on the host, so ``last`` [N] is read
 back once per trial.  Host callbacks fire at these boundaries: ``on_replay_end`` of the start
-replay after the trial's kernel, step callbacks not at all.
+replay after the trial's kernel, step callbacks not at all.  The head and the tail of a session
+are ``FusedAgent._session_begin`` / ``_session_end``; the loop between them is this agent's.
 """
 from __future__ import annotations
 
@@ -117,19 +118,14 @@ class PMA(FusedAgent):
 
     # -- launch ---------------------------------------------------------------------------------
     def _launch(self, interface, pol, flags, trials_target, steps, budget, batch) -> None:
-        M, mon = self.M, self.monitors
+        M = self.M
         shared = M.policy is pol
         mem = M._mem(self._q, self._mask_dev, batch)
-        run = _lib.PMARun()
-        run.inst = _lib.ptr(self.inst)
-        run.lat_sum, run.lat_cnt = _lib.ptr(mon.raw('lat_sum')), _lib.ptr(mon.raw('lat_cnt'))
-        run.reward_sum, run.resp_cnt = _lib.ptr(mon.raw('reward_sum')), _lib.ptr(mon.raw('resp_cnt'))
-        run.lat_trace, run.occupancy = _lib.ptr(mon.lat_trace), _lib.ptr(mon.occupancy)
-        run.steps_done = _lib.ptr(mon.steps_done)
+        run = _lib.PMARun()     # (the mask, the instance count and the seed travel in `mem`)
+        self._fill_run(run, interface, flags, trials_target, steps, budget)
         run.last = _lib.ptr(self._last)
         run.replay_out = _lib.ptr(self._start_records)
-        run.trial_cap, run.mon_stripes = mon.cap, mon.stripes
-        run.steps_per_trial, run.batch = steps, batch
+        run.batch = batch
         run.flags = flags | ((_lib.PMA_SHARED_POLICY << 16) if shared else 0)
         run.alpha, run.gamma_pow1 = self.learning_rate, self.gamma ** 1
         run.epsilon = float(pol.epsilon)
@@ -145,21 +141,14 @@ class PMA(FusedAgent):
 
     def _run(self, interface, trials: int, steps: int, batch: int, learn: bool,
              no_replay: bool) -> None:
-        interface.sync_world()
-        self._bind(interface)
+        # (agent/pma.py:291: test() selects with self.policy as well; _policy_in puts it on
+        #  STREAM_POLICY, also where it is the memory's policy object)
+        pol, flags, _ = self._session_begin(interface, trials, learn,
+                                            _lib.F_NO_REPLAY if no_replay else 0, self.policy)
         M = self.M
-        pol = self.policy      # (agent/pma.py:291: test() selects with self.policy as well)
-        if M.policy is pol and pol.stream is None:
-            pol.stream = _lib.STREAM_POLICY
-        flags = (_lib.F_LEARN if learn else 0) | (_lib.F_NO_REPLAY if no_replay else 0) | \
-                (_lib.F_MASK_ACTIONS if self.mask_actions else 0)
-        self._env_in(interface)
-        flags |= self._policy_in(pol, interface, not learn)
         M._session(interface.seed, interface.instance_base)
         shared = M.policy is pol
         replays = learn and not no_replay
-        first = self.current_trial
-        self.monitors.reserve(first + trials, self.n_envs, self.track_instances)
         self._mask_dev = self._mask_bits() if self.mask_actions else None
         self._start_records = None
         if replays:
@@ -191,8 +180,7 @@ class PMA(FusedAgent):
             logs = self.callbacks.on_trial_end(logs)
             if self.stop:
                 break
-        self._policy_out(pol)
-        self._env_out(interface)
+        self._session_end(pol, interface)
 
     def train(self, interface, trials: int, steps: int, batch_size: int = 32,
               no_replay: bool = False) -> None:

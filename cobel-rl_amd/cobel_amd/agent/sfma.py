@@ -18,12 +18,12 @@ import numpy as np
 import torch
 
 from .. import _lib
+from ..memory import _device
+from ..memory.sfma import EVENT
 from ..spaces import Discrete
 from .agent import Callbacks
 from .tabular import TabularAgent
 
-EVENT = np.dtype([('sa', '<u4'), ('next', '<u4'), ('reward', '<f4'), ('trial', '<i4'),
-                  ('td', '<f8')])
 
 
 class CallbacksSFMA(Callbacks):
@@ -71,8 +71,7 @@ class SFMA(TabularAgent):
     def _plan(self, flags: int) -> None:
         """``launch_plan``: (form, LDS bytes, threads per instance, scratch bytes — none) of the
         launch under ``flags``, as ``cobel_sfma_run`` decides it; refreshed by every launch."""
-        self.launch_plan = (C.c_int32 * 4)()
-        _lib.check(_lib.lib().cobel_sfma_plan(self.n_states, flags, C.byref(self.launch_plan)))
+        self.launch_plan = _device.plan4(_lib.lib().cobel_sfma_plan, self.n_states, flags)
 
     @property
     def td(self):
@@ -100,38 +99,22 @@ class SFMA(TabularAgent):
 
     # -- launch ---------------------------------------------------------------------------------
     def _launch(self, interface, pol, flags, trials_target, steps, budget, batch) -> None:
-        M, mon = self.M, self.monitors
+        M = self.M
         if M.error_mod_local or M.error_mod:
             raise KeyError('td')       # what the reference's M.store raises inside train()
-        run = _lib.SFMARun()
+        run = _lib.SFMARun()     # (monitors, instance and session fields: FusedAgent._fill_run)
+        self._fill_run(run, interface, flags, trials_target, steps, budget)
         run.q, run.model = _lib.ptr(self._q), _lib.ptr(M.table)
         run.strength, run.stamp = _lib.ptr(M.strength), _lib.ptr(M.stamp)
-        run.inst, run.sfma_inst = _lib.ptr(self.inst), _lib.ptr(M.state)
+        run.sfma_inst = _lib.ptr(M.state)
         run.metric = _lib.ptr(M._metric_on(self.device, interface.handle.n_worlds))
-        sf = 0
-        for flag, on in ((_lib.SF_RANDOM, self.random), (_lib.SF_DYNAMIC, self.dynamic),
-                         (_lib.SF_START_REPLAY, self.start_replay),
-                         (_lib.SF_DETERMINISTIC, M.deterministic), (_lib.SF_RECENCY, M.recency),
-                         (_lib.SF_C_NORMALIZE, M.C_normalize), (_lib.SF_D_NORMALIZE, M.D_normalize),
-                         (_lib.SF_R_NORMALIZE, M.R_normalize),
-                         (_lib.SF_REWARD_MOD_LOCAL, M.reward_mod_local),
-                         (_lib.SF_REWARD_MOD, M.reward_mod), (_lib.SF_STATE_MOD, M.state_mod)):
-            sf |= flag if on else 0
-        if M.recency:
-            tab = M._recency_table(self.device)
-            run.recency_tab, run.recency_len = _lib.ptr(tab), tab.numel()
+        # (the memory's switches, recency table and parameters: the block its own methods pass)
+        run.sfma_flags = M._fill_params(run) | (_lib.SF_RANDOM if self.random else 0) | \
+            (_lib.SF_DYNAMIC if self.dynamic else 0) | \
+            (_lib.SF_START_REPLAY if self.start_replay else 0)
         if self.random:
             run.random_cdf = _lib.ptr(self._random_cdf())
-        self._mask_dev = self._mask_bits() if (flags & _lib.F_MASK_ACTIONS) else None
-        run.action_mask = _lib.ptr(self._mask_dev)
-        run.lat_sum, run.lat_cnt = _lib.ptr(mon.raw('lat_sum')), _lib.ptr(mon.raw('lat_cnt'))
-        run.reward_sum = _lib.ptr(mon.raw('reward_sum'))
-        run.resp_cnt = _lib.ptr(mon.raw('resp_cnt'))
-        run.mon_stripes = mon.stripes
-        run.lat_trace = _lib.ptr(mon.lat_trace)
-        run.occupancy = _lib.ptr(mon.occupancy)
-        run.steps_done, run.replays_done = _lib.ptr(mon.steps_done), _lib.ptr(self.replays_done)
-        run.last_exp = _lib.ptr(self._last_exp) if budget == 1 else None
+        run.replays_done = _lib.ptr(self.replays_done)
         want_trace = self.keep_replay_trace or self.callbacks.has('on_replay_begin',
                                                                   'on_replay_end')
         if want_trace and (flags & _lib.F_LEARN):
@@ -144,19 +127,9 @@ class SFMA(TabularAgent):
             self._trace_len.zero_()
             run.replay_trace, run.trace_len = _lib.ptr(self._trace), _lib.ptr(self._trace_len)
             run.trace_cap = self._trace.shape[1] // _lib.SFMA_EVENT_BYTES
-        run.n, run.trial_cap = self.n_envs, mon.cap
-        run.instance_base = interface.instance_base
-        run.flags, run.sfma_flags = flags, sf
-        run.trials_target, run.steps_per_trial, run.step_budget = trials_target, steps, budget
+        run.flags = flags
         run.batch, run.nb_replays = batch, self.nb_replays
         run.alpha, run.gamma, run.epsilon = self.learning_rate, self.gamma, pol.epsilon
-        run.model_lr = M.learning_rate
-        run.decay_inhibition, run.decay_strength = M.decay_inhibition, M.decay_strength
-        run.c_step, run.i_step = M.C_step, M.I_step
-        run.r_threshold, run.beta = M.R_threshold, M.beta
-        run.reward_modulation, run.blend = M.reward_modulation, M.blend
-        run.interp_fwd, run.interp_rev = M.interpolation_fwd, M.interpolation_rev
-        run.seed = interface.seed
         # (the memory's own methods, called between sessions, go on in this stream)
         M._session(interface.seed, interface.instance_base, interface.handle.n_worlds)
         M._sync_mode()

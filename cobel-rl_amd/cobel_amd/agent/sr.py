@@ -67,23 +67,10 @@ class SR(FusedAgent):
         return out
 
     def _launch(self, interface, pol, flags, trials_target, steps, budget, batch) -> None:
-        mon = self.monitors
-        run = _lib.SRRun()
+        run = _lib.SRRun()      # (monitors, instance and session fields: FusedAgent._fill_run)
+        self._fill_run(run, interface, flags, trials_target, steps, budget)
         run.sr, run.trans, run.rewards = _lib.ptr(self._sr), _lib.ptr(self._T), _lib.ptr(self._rw)
-        run.inst = _lib.ptr(self.inst)
-        self._mask_dev = self._mask_bits() if (flags & _lib.F_MASK_ACTIONS) else None
-        run.action_mask = _lib.ptr(self._mask_dev)
-        run.lat_sum, run.lat_cnt = _lib.ptr(mon.raw('lat_sum')), _lib.ptr(mon.raw('lat_cnt'))
-        run.reward_sum, run.lat_trace = _lib.ptr(mon.raw('reward_sum')), _lib.ptr(mon.lat_trace)
-        run.resp_cnt = _lib.ptr(mon.raw('resp_cnt'))
-        run.mon_stripes = mon.stripes
-        run.occupancy, run.steps_done = _lib.ptr(mon.occupancy), _lib.ptr(mon.steps_done)
-        run.last_exp = _lib.ptr(self._last_exp) if budget == 1 else None
-        run.n, run.trial_cap = self.n_envs, mon.cap
-        run.instance_base = interface.instance_base
         run.flags = flags | (_lib.F_SR_STREAM_ROWS if self.stream_rows else 0)
-        run.trials_target, run.steps_per_trial, run.step_budget = trials_target, steps, budget
-        run.seed = interface.seed
         run.traffic = _lib.ptr(self.traffic)
         self._hyper(run, self.learning_rate, self.gamma, pol.epsilon)
         _lib.check(_lib.lib().cobel_sr_run(interface.handle.ptr, C.byref(run),

@@ -12,7 +12,7 @@ from .agent import FusedAgent
 
 class TabularAgent(FusedAgent):
     """Q table [N, S, A] float32 on device (A = 4 but for the general kernel) + launch plumbing
-    for ``cobel_tab_run``."""
+    for ``cobel_tab_run``: ``FusedAgent._fill_run`` plus the table, the kind and the flags."""
 
     agent_kind = _lib.AGENT_Q
     general_actions = True     # cobel_tab_run's general kernel takes any action count
@@ -95,29 +95,14 @@ class TabularAgent(FusedAgent):
 
     def _launch(self, interface, pol, flags, trials_target, steps, budget, batch,
                 describe=None) -> None:
-        mon = self.monitors
         run = _lib.TabRun()
+        self._fill_run(run, interface, flags, trials_target, steps, budget)
         run.q = _lib.ptr(self._q)
-        run.inst = _lib.ptr(self.inst)
-        self._mask_dev = self._mask_bits() if (flags & _lib.F_MASK_ACTIONS) else None
-        run.action_mask = _lib.ptr(self._mask_dev)
-        run.lat_sum, run.lat_cnt = _lib.ptr(mon.raw('lat_sum')), _lib.ptr(mon.raw('lat_cnt'))
-        run.reward_sum = _lib.ptr(mon.raw('reward_sum'))
-        run.resp_cnt = _lib.ptr(mon.raw('resp_cnt'))
-        run.mon_stripes = mon.stripes
-        run.lat_trace = _lib.ptr(mon.lat_trace)
-        run.occupancy = _lib.ptr(mon.occupancy)
-        run.steps_done = _lib.ptr(mon.steps_done)
         run.batches_done = _lib.ptr(self.batches_done)
         run.scratch, run.scratch_bytes = _lib.ptr(self._scratch), self._scratch.numel() * 4
-        run.last_exp = _lib.ptr(self._last_exp) if budget == 1 else None
-        run.n, run.trial_cap = self.n_envs, mon.cap
-        run.instance_base = interface.instance_base
         run.agent = self.agent_kind
         run.flags = flags | self.extra_flags | (_lib.F_TAB_GENERAL if self.force_general else 0)
-        run.trials_target, run.steps_per_trial, run.step_budget = trials_target, steps, budget
         run.batch = batch
-        run.seed = interface.seed
         self._hyper(run, self.learning_rate, self.gamma, pol.epsilon, self._model_lr())
         self._extra(run)
         if describe is not None:
@@ -129,7 +114,6 @@ class TabularAgent(FusedAgent):
         ev = getattr(self, 'launch_events', None)
         pair = None
         if ev is not None:
-            import torch
             pair = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             pair[0].record()
         # (the entry point SURVEY.md section 8b names for this agent: cobel_tab_run with the kind checked)

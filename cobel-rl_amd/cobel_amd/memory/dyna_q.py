@@ -2,7 +2,8 @@
 
 On device the model is one packed 8-byte record per (state, action):
 ``{float32 reward estimate, uint16 next state, uint8 nonterminal flag}``, ``[N, S, 4]``.
-``rewards`` / ``states`` / ``terminals`` decode it into the reference's three tables.  During
+``rewards`` / ``states`` / ``terminals`` decode it into the reference's three tables
+(memory/_device.py, shared with ``SFMAMemory``).  During
 ``agent.train`` ``store`` and ``retrieve_batch`` are folded into the fused agent kernel
 (cobel_tab_run); the methods here serve single host-side calls (memory/dyna_q.py:77-157) on one
 instance and go through the same device table, the same float32 arithmetic and the same memory
@@ -16,6 +17,11 @@ import numpy as np
 import torch
 
 from .. import _lib
+from . import _device
+
+
+TAB_EXP = np.dtype([('state', '<i4'), ('action', '<i4'), ('next_state', '<i4'),
+                    ('nonterminal', '<i4'), ('reward', '<f4'), ('reserved_', '<i4')])
 
 
 def _is_array(v) -> bool:
@@ -41,17 +47,10 @@ def pack_experiences(experience: dict, n: int, n_states: int, device):
             else:
                 out[:, col] = v.to(torch.int32).expand(n)
         return out
-    host = np.zeros((n, 6), dtype=np.int32)
-    for col, v in enumerate(vals):
-        v = np.asarray(v)
-        assert v.ndim == 0 or v.shape == (n,), \
-            'experience values are scalars or one entry per instance (%d)' % n
-        if col == 4:
-            host[:, col] = np.broadcast_to(v.astype(np.float32), (n,)).view(np.int32)
-        elif col == 3:
-            host[:, col] = np.broadcast_to(v != 0, (n,))
-        else:
-            host[:, col] = np.broadcast_to(v.astype(np.int64), (n,))
+    assert all(np.ndim(v) == 0 or np.shape(v) == (n,) for v in vals), \
+        'experience values are scalars or one entry per instance (%d)' % n
+    host = _device.records(experience, n, TAB_EXP, {}, skip=('reserved_',)).view(np.int32)
+    host = host.reshape(n, 6)
     on = host[:, 0] >= 0
     if (host[on, 0] >= n_states).any() or (host[on, 2] < 0).any() or \
             (host[on, 2] >= n_states).any() or (host[on, 1] < 0).any() or (host[on, 1] >= 4).any():
@@ -59,7 +58,7 @@ def pack_experiences(experience: dict, n: int, n_states: int, device):
     return torch.as_tensor(host, device=device)
 
 
-class DynaQMemory:
+class DynaQMemory(_device.PackedModel):
     def __init__(self, states: int, actions: int, learning_rate: float = 0.9, rng=None) -> None:
         self.rng = rng
         self.number_of_states = states
@@ -95,27 +94,6 @@ class DynaQMemory:
         _lib.check(_lib.lib().cobel_model_index_build(
             _lib.ptr(self.table), _lib.ptr(self.index), self.table.shape[0],
             self.number_of_states, _lib.current_stream(self.table.device)))
-
-    def _decode(self):
-        raw = self.table.cpu().numpy()
-        lo = (raw & 0xFFFFFFFF).astype(np.uint32).view(np.float32)
-        hi = (raw >> 32) & 0xFFFFFFFF
-        return lo, (hi & 0xFFFF).astype(np.int64), ((hi >> 16) & 1).astype(np.int64)
-
-    def _squeeze(self, a):
-        return a[0] if a.shape[0] == 1 else a
-
-    @property
-    def rewards(self):
-        return self._squeeze(self._decode()[0])
-
-    @property
-    def states(self):
-        return self._squeeze(self._decode()[1])
-
-    @property
-    def terminals(self):
-        return self._squeeze(self._decode()[2])
 
     def _record(self, instance: int, state: int, action: int):
         """(float32 reward estimate, next state, nonterminal flag) of one pair."""

@@ -4,7 +4,8 @@ Same constructor, attributes, switches and methods as the reference.  ``replay``
 ``update_sr`` are device calls (``cobel_pma_replay`` / ``cobel_pma_store`` / ``cobel_pma_update_sr``,
 csrc/pma.hip); inside ``PMA.train`` the stores and the start-of-trial replay are part of the trial
 kernel (``cobel_pma_trial``).  A memory is bound to a device by the agent's first session or,
-without an agent, by ``bind``.  Every table is float64, as the reference's are.
+without an agent, by ``bind``.  Every table is float64, as the reference's are.  The host
+plumbing shared with ``SFMAMemory`` (``bind``, argument checks, records) is memory/_device.py's.
 
 Tables (one leading instance axis on the device; the attributes return NumPy snapshots, squeezed
 for one instance, and assigning uploads):
@@ -35,6 +36,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from . import _device
 
 RECORD = np.dtype([('state', '<i4'), ('action', '<i4'), ('next_state', '<i4'),
                    ('terminal', '<i4'), ('reward', '<f8')])
@@ -66,7 +68,7 @@ def _table(name: str):
     return property(get, put)
 
 
-class PMAMemory:
+class PMAMemory(_device.DeviceMemory):
     def __init__(self, sas, policy, learning_rate: float = 0.9, learning_rate_q: float = 0.9,
                  gamma: float = 0.9, gamma_q: float = 0.9, rng=None, wide: bool = False) -> None:
         self.rng = rng
@@ -121,19 +123,6 @@ class PMAMemory:
     T, SR, update_mask = _table('T'), _table('SR'), _table('update_mask')
 
     # -- device state ---------------------------------------------------------------------------
-    def bind(self, n_envs: int = 1, device=None, seed: int = 0, instance_base: int = 0) -> None:
-        """Put the tables of ``n_envs`` instances on ``device`` (default: the current GPU) for a
-        memory that is used without an agent; instance i draws from the streams of
-        (``seed``, ``instance_base + i``)."""
-        assert self._dev is None, 'the memory is bound already'
-        if device is None:
-            device = torch.device('cuda', torch.cuda.current_device())
-        self._bind(n_envs, torch.device(device))
-        self._session(seed, instance_base)
-
-    def _session(self, seed: int, instance_base: int) -> None:
-        self.seed, self.instance_base = int(seed), int(instance_base)
-
     def _bind(self, n_envs: int, device) -> None:
         if self._dev is not None:
             assert self.n_envs == n_envs, 'a memory stays bound to the instance count it first saw'
@@ -187,8 +176,7 @@ class PMAMemory:
                 (_lib.PMA_WIDE if self.wide else 0))
 
     def _mem(self, q=None, mask_bits=None, length: int = 0):
-        assert self._dev is not None, \
-            'the memory has no device tables yet: train an agent with it, or call bind()'
+        assert self._is_bound, _device.NOT_BOUND
         d = self._dev
         m = _lib.PMAMem()
         m.q = _lib.ptr(q)
@@ -210,42 +198,27 @@ class PMAMemory:
 
     def launch_plan(self, replay_length: int = 32) -> list:
         """(LDS bytes, threads) of a replay / trial workgroup and of an update_sr workgroup."""
-        out = (C.c_int32 * 4)()
         plan = _lib.lib().cobel_pma_plan_wide if self.wide else _lib.lib().cobel_pma_plan
-        _lib.check(plan(self.nb_states, self.nb_actions, int(replay_length), C.byref(out)))
-        return list(out)
+        return list(_device.plan4(plan, self.nb_states, self.nb_actions, int(replay_length)))
 
     def _per_instance(self, value, name: str, limit: int):
         """scalar / [N] -> int32 [N], range-checked; entries None or < 0 become -1."""
-        if isinstance(value, (list, tuple)):
-            value = [-1 if v is None else v for v in value]
-        a = np.array(np.broadcast_to(np.asarray(value, dtype=np.int64), (self.n_envs,)))
-        if (a >= limit).any():
-            raise IndexError('%s outside [0, %d)' % (name, limit))
-        a[a < 0] = -1
-        return np.ascontiguousarray(a, dtype=np.int32)
+        return _device.per_instance(value, self.n_envs, name, limit, none_as=-1)
 
     def _mask_bits(self, action_mask):
         if action_mask is None:
             return None
-        m = np.asarray(action_mask, dtype=bool).reshape(self.nb_states, self.nb_actions)
-        assert m.any(axis=1).all(), 'The action mask masks all actions!'
-        bits = (m * (1 << np.arange(self.nb_actions, dtype=np.int64))).sum(axis=1).astype(np.uint8)
-        return torch.as_tensor(bits, device=self.device)
+        return torch.as_tensor(_device.mask_bits(action_mask, self.nb_states, self.nb_actions),
+                               device=self.device)
 
     # -- the reference's methods ------------------------------------------------------------------
     def store(self, experience: dict) -> None:
         """memory/pma.py:148-166.  One experience per instance: the values of ``experience`` are
         scalars (the same for all instances) or [N] arrays."""
         m = self._mem()
-        n = self.n_envs
-        rec = np.zeros(n, dtype=RECORD)
-        rec['state'] = self._per_instance(experience['state'], 'state', self.nb_states)
-        rec['action'] = self._per_instance(experience['action'], 'action', self.nb_actions)
-        rec['next_state'] = self._per_instance(experience['next_state'], 'next_state',
-                                               self.nb_states)
-        rec['terminal'] = np.broadcast_to(np.asarray(experience['terminal'], dtype=np.int64), (n,))
-        rec['reward'] = np.broadcast_to(np.asarray(experience['reward'], dtype=np.float64), (n,))
+        S = self.nb_states
+        rec = _device.records(experience, self.n_envs, RECORD,
+                              {'state': S, 'action': self.nb_actions, 'next_state': S}, none_as=-1)
         exps = torch.as_tensor(rec.view(np.uint8), device=self.device)
         _lib.check(_lib.lib().cobel_pma_store(C.byref(m), _lib.ptr(exps),
                                               _lib.current_stream(self.device)))
@@ -294,8 +267,7 @@ class PMAMemory:
         and the updated copy as a NumPy array for one instance; one list per instance and the
         device tensor [N, S, A] for several.  ``current_state`` / ``force_first`` are scalars or
         [N] arrays; ``current_state=None`` takes ``compute_need(None)`` (host, slow)."""
-        assert self._dev is not None, \
-            'the memory has no device tables yet: train an agent with it, or call bind()'
+        assert self._is_bound, _device.NOT_BOUND
         n, S, A = self.n_envs, self.nb_states, self.nb_actions
         if torch.is_tensor(q_function):
             q = q_function.to(device=self.device, dtype=torch.float64)

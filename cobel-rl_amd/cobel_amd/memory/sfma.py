@@ -7,7 +7,9 @@ the replay are folded into the fused kernel (``cobel_sfma_run``); called on the 
 the kernel code of the fused kernel), and ``replay_batch`` runs K independent replays of every
 instance side by side.  A memory is bound to a device by the agent's first session or, without an
 agent, by ``bind``.  The methods draw from the memory stream of the session (seed, instance base)
-at ``counter``, where ``train`` left it and where ``train`` goes on afterwards.
+at ``counter``, where ``train`` left it and where ``train`` goes on afterwards.  ``bind``, the
+per-instance argument checks and the decoding of the packed model table are memory/_device.py's,
+shared with ``PMAMemory`` and ``DynaQMemory``; ``_fill_params`` serves the agent's launcher too.
 
 This class owns the parameters and the device tables:
 
@@ -28,6 +30,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from . import _device
 
 EXPERIENCE = np.dtype([('state', '<i4'), ('action', '<i4'), ('next_state', '<i4'),
                        ('nonterminal', '<i4'), ('reward', '<f8'), ('td', '<f8')])
@@ -35,7 +38,7 @@ EVENT = np.dtype([('sa', '<u4'), ('next', '<u4'), ('reward', '<f4'), ('trial', '
                   ('td', '<f8')])
 
 
-class SFMAMemory:
+class SFMAMemory(_device.DeviceMemory, _device.PackedModel):
     def __init__(self, metric, nb_states: int, nb_actions: int, decay_inhibition: float = 0.9,
                  decay_strength: float = 1.0, learning_rate: float = 0.9, rng=None) -> None:
         assert nb_actions == 4, 'the model record layout covers 4-action worlds'
@@ -68,19 +71,6 @@ class SFMAMemory:
         self._inhibition = None
 
     # -- device state ---------------------------------------------------------------------------
-    def bind(self, n_envs: int = 1, device=None, seed: int = 0, instance_base: int = 0) -> None:
-        """Put the tables of ``n_envs`` instances on ``device`` (default: the current GPU) for a
-        memory that is used without an agent; instance i draws from the memory stream of
-        (``seed``, ``instance_base + i``)."""
-        assert self.table is None, 'the memory is bound already'
-        if device is None:
-            device = torch.device('cuda', torch.cuda.current_device())
-        self._bind(n_envs, torch.device(device))
-        self._session(seed, instance_base, 1)
-
-    def _session(self, seed: int, instance_base: int, n_worlds: int) -> None:
-        self.seed, self.instance_base, self._n_worlds = int(seed), int(instance_base), int(n_worlds)
-
     def _bind(self, n_envs: int, device) -> None:
         if self.table is not None:
             return
@@ -140,27 +130,6 @@ class SFMAMemory:
             self.mode = self._mode_seen = _lib.SFMA_MODES[int(self.state[0, _lib.SI_MODE])]
 
     # -- the reference's tables -----------------------------------------------------------------
-    def _squeeze(self, a):
-        return a[0] if a.shape[0] == 1 else a
-
-    def _decode(self):
-        raw = self.table.cpu().numpy()
-        lo = (raw & 0xFFFFFFFF).astype(np.uint32).view(np.float32)
-        hi = (raw >> 32) & 0xFFFFFFFF
-        return lo, (hi & 0xFFFF).astype(np.int64), ((hi >> 16) & 1).astype(np.int64)
-
-    @property
-    def rewards(self):
-        return self._squeeze(self._decode()[0])
-
-    @property
-    def states(self):
-        return self._squeeze(self._decode()[1])
-
-    @property
-    def terminals(self):
-        return self._squeeze(self._decode()[2])
-
     @property
     def C(self):
         return self._squeeze(self.strength.cpu().numpy())
@@ -199,14 +168,9 @@ class SFMAMemory:
                 'next_state': s[0, state, action], 'terminal': t[0, state, action]}
 
     # -- the reference's methods as device calls (csrc/sfma_mem.hip) ------------------------------
-    def _mem(self, mem_flags: int = 0):
-        assert self.table is not None, \
-            'the memory has no device tables yet: train an agent with it, or call bind()'
-        dev = self.table.device
-        m = _lib.SFMAMem()
-        m.model, m.strength, m.stamp = _lib.ptr(self.table), _lib.ptr(self.strength), _lib.ptr(self.stamp)
-        m.sfma_inst, m.counter = _lib.ptr(self.state), _lib.ptr(self.counter)
-        m.metric = _lib.ptr(self._metric_on(dev, self._n_worlds))
+    def _fill_params(self, struct) -> int:
+        """The recency table, ``model_lr`` and the eleven doubles of a ``cobel_sfma_run_t`` or
+        ``cobel_sfma_mem_t``; returns the memory's ``SF_*`` switches (the caller ORs in its own)."""
         sf = 0
         for flag, on in ((_lib.SF_DETERMINISTIC, self.deterministic), (_lib.SF_RECENCY, self.recency),
                          (_lib.SF_C_NORMALIZE, self.C_normalize),
@@ -216,36 +180,38 @@ class SFMAMemory:
                          (_lib.SF_REWARD_MOD, self.reward_mod), (_lib.SF_STATE_MOD, self.state_mod)):
             sf |= flag if on else 0
         if self.recency:
-            tab = self._recency_table(dev)
-            m.recency_tab, m.recency_len = _lib.ptr(tab), tab.numel()
+            tab = self._recency_table(self.table.device)
+            struct.recency_tab, struct.recency_len = _lib.ptr(tab), tab.numel()
+        struct.model_lr = self.learning_rate
+        struct.decay_inhibition, struct.decay_strength = self.decay_inhibition, self.decay_strength
+        struct.c_step, struct.i_step = self.C_step, self.I_step
+        struct.r_threshold, struct.beta = self.R_threshold, self.beta
+        struct.reward_modulation, struct.blend = self.reward_modulation, self.blend
+        struct.interp_fwd, struct.interp_rev = self.interpolation_fwd, self.interpolation_rev
+        return sf
+
+    def _mem(self, mem_flags: int = 0):
+        assert self._is_bound, _device.NOT_BOUND
+        dev = self.table.device
+        m = _lib.SFMAMem()
+        m.model, m.strength, m.stamp = _lib.ptr(self.table), _lib.ptr(self.strength), _lib.ptr(self.stamp)
+        m.sfma_inst, m.counter = _lib.ptr(self.state), _lib.ptr(self.counter)
+        m.metric = _lib.ptr(self._metric_on(dev, self._n_worlds))
         m.n, m.n_states, m.n_worlds = self.table.shape[0], self.nb_states, self._n_worlds
         m.instance_base = self.instance_base
-        m.flags, m.sfma_flags, m.mem_flags = self.launch_flags, sf, mem_flags
-        m.model_lr = self.learning_rate
-        m.decay_inhibition, m.decay_strength = self.decay_inhibition, self.decay_strength
-        m.c_step, m.i_step = self.C_step, self.I_step
-        m.r_threshold, m.beta = self.R_threshold, self.beta
-        m.reward_modulation, m.blend = self.reward_modulation, self.blend
-        m.interp_fwd, m.interp_rev = self.interpolation_fwd, self.interpolation_rev
+        m.flags, m.sfma_flags, m.mem_flags = self.launch_flags, self._fill_params(m), mem_flags
         m.seed = self.seed
         self._sync_mode()
         return m, dev
 
     def launch_plan(self):
         """(form, LDS bytes, threads per workgroup, streaming tier) of the memory's launches."""
-        out = (C.c_int32 * 4)()
-        _lib.check(_lib.lib().cobel_sfma_mem_plan(self.nb_states, self.launch_flags, C.byref(out)))
-        return list(out)
+        return list(_device.plan4(_lib.lib().cobel_sfma_mem_plan, self.nb_states,
+                                  self.launch_flags))
 
     def _per_instance(self, value, name: str, limit: int):
-        """None / scalar / [N] -> int32 [N] with -1 for None, range-checked."""
-        n = self.table.shape[0]
-        if value is None:
-            return None
-        a = np.broadcast_to(np.asarray(value, dtype=np.int64), (n,))
-        if ((a < 0) | (a >= limit)).any():
-            raise IndexError('%s outside [0, %d)' % (name, limit))
-        return np.ascontiguousarray(a, dtype=np.int32)
+        """None / scalar / [N] -> None / int32 [N], range-checked."""
+        return _device.per_instance(value, self.table.shape[0], name, limit)
 
     def store(self, experience: dict) -> None:
         """memory/sfma.py:195-236.  One experience per instance: with several instances the values
@@ -255,15 +221,10 @@ class SFMAMemory:
         flags = (_lib.SFM_ERROR_MOD_LOCAL if self.error_mod_local else 0) | \
                 (_lib.SFM_ERROR_MOD if self.error_mod else 0)
         m, dev = self._mem(flags)
-        n, S = m.n, self.nb_states
-        rec = np.zeros(n, dtype=EXPERIENCE)
-        rec['state'] = self._per_instance(experience['state'], 'state', S)
-        rec['action'] = self._per_instance(experience['action'], 'action', self.nb_actions)
-        rec['next_state'] = self._per_instance(experience['next_state'], 'next_state', S)
-        rec['nonterminal'] = np.broadcast_to(np.asarray(experience['terminal']), (n,)) != 0
-        rec['reward'] = np.broadcast_to(np.asarray(experience['reward'], dtype=np.float64), (n,))
-        if flags:
-            rec['td'] = np.broadcast_to(np.asarray(experience['td'], dtype=np.float64), (n,))
+        S = self.nb_states
+        rec = _device.records(experience, m.n, EXPERIENCE,
+                              {'state': S, 'action': self.nb_actions, 'next_state': S},
+                              skip=() if flags else ('td',))
         exps = torch.as_tensor(rec.view(np.uint8), device=dev)
         _lib.check(_lib.lib().cobel_sfma_store(C.byref(m), _lib.ptr(exps), _lib.current_stream(dev)))
 
