@@ -288,6 +288,38 @@ class PMARun(C.Structure):
     ]
 
 
+MFEC_MAX_STATES, MFEC_MAX_ACTIONS, MFEC_MAX_CAPACITY, MFEC_MAX_K = 1024, 8, 2048, 32
+MFEC_MAX_FEATURES = 65536
+
+
+class MFECMem(C.Structure):
+    """``cobel_mfec_mem_t``."""
+    _fields_ = [
+        ('rdist', C.c_void_p), ('same', C.c_void_p), ('ids', C.c_void_p), ('values', C.c_void_p),
+        ('times', C.c_void_p), ('len', C.c_void_p), ('clock', C.c_void_p),
+        ('n', C.c_int32), ('n_states', C.c_int32), ('n_actions', C.c_int32),
+        ('capacity', C.c_int32), ('k', C.c_int32), ('reserved_', C.c_int32),
+    ]
+
+
+class MFECRun(C.Structure):
+    """``cobel_mfec_run_t``."""
+    _fields_ = [
+        ('inst', C.c_void_p),
+        ('lat_sum', C.c_void_p), ('lat_cnt', C.c_void_p), ('reward_sum', C.c_void_p),
+        ('resp_cnt', C.c_void_p), ('lat_trace', C.c_void_p), ('occupancy', C.c_void_p),
+        ('steps_done', C.c_void_p), ('last_exp', C.c_void_p),
+        ('ep_sa', C.c_void_p), ('ep_value', C.c_void_p),
+        ('trace', C.c_void_p), ('trace_len', C.c_void_p),
+        ('n', C.c_int32), ('trial_cap', C.c_int32), ('mon_stripes', C.c_int32),
+        ('trace_cap', C.c_int32),
+        ('instance_base', C.c_uint32), ('flags', C.c_uint32),
+        ('trials_target', C.c_int32), ('steps_per_trial', C.c_int32), ('step_budget', C.c_int32),
+        ('reserved_', C.c_int32),
+        ('gamma', C.c_double), ('epsilon', C.c_double), ('seed', C.c_uint64),
+    ]
+
+
 class SRRun(C.Structure):
     """``cobel_sr_run_t``."""
     _fields_ = [
@@ -377,6 +409,9 @@ _SIGNATURES = {
     'cobel_pma_trial': (C.c_int, [_P, C.POINTER(PMAMem), C.POINTER(PMARun), _P]),
     'cobel_pma_store': (C.c_int, [C.POINTER(PMAMem), _P, _P]),
     'cobel_pma_update_sr': (C.c_int, [C.POINTER(PMAMem), _P]),
+    'cobel_mfec_pairs': (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P]),
+    'cobel_mfec_run': (C.c_int, [_P, C.POINTER(MFECMem), C.POINTER(MFECRun), _P]),
+    'cobel_mfec_estimate': (C.c_int, [C.POINTER(MFECMem), _P, C.c_int32, _P, _P]),
     'cobel_adam_step': (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int32,
                                   C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _P,
                                   C.c_double, _P]),

@@ -1159,6 +1159,82 @@ COBEL_API int cobel_pma_store(const cobel_pma_mem_t* mem, const cobel_pma_exp_t*
  * block in global memory, the same operations per element in the same order. */
 COBEL_API int cobel_pma_update_sr(const cobel_pma_mem_t* mem, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Model-Free Episodic Control (Blundell et al. 2016).  Replaces ActionBuffer / QEC
+ * (agent/mfec.py:28-237: find_state, find_neighbors, add, replace, estimate, update,
+ * update_episode) and the trial loops of MFEC.train / MFEC.test / predict_on_batch
+ * (agent/mfec.py:423-559).  Everything is float64, as in the reference.
+ *
+ * The observation of a tabular world is a function of the node, so the buffers hold node ids and
+ * the k-d tree's arithmetic is done once per world: cobel_mfec_pairs turns the feature table
+ * F[S][D] (row = process_observation of that node's observation, agent/mfec.py:362-403) into the
+ * S x S table of reduced distances (scikit-learn's euclidean_rdist: sum over d of (x - y)^2,
+ * sequential, multiply and add rounded separately) and the S x S table of find_state's
+ * np.allclose(stored, query, rtol=1e-4, atol=1e-6) (agent/mfec.py:76; not symmetric).  A query
+ * follows a KDTree of one leaf: every entry in index order onto a max-heap of k (sklearn/utils/
+ * _heap.pyx), then simultaneous_sort (sklearn/utils/_sorting.pyx) — the order among equidistant
+ * entries, and so the float64 sum of estimate (agent/mfec.py:195-200), is the tree's.  Time stamps
+ * are a per-instance counter that advances by one per training step (the reference stamps
+ * time.time(), of which only the order matters). */
+#define COBEL_MFEC_MAX_STATES 1024
+#define COBEL_MFEC_MAX_ACTIONS 8
+#define COBEL_MFEC_MAX_CAPACITY 2048
+#define COBEL_MFEC_MAX_K 32
+#define COBEL_MFEC_MAX_FEATURES 65536
+
+typedef struct {
+  const double* rdist;        /* [S][S] reduced distances (cobel_mfec_pairs)                    */
+  const uint8_t* same;        /* [S][S] same[q * S + j] = allclose(F[j], F[q]): 0 / 1           */
+  int32_t* ids;               /* [N][A][capacity] node ids (ActionBuffer.states)                */
+  double* values;             /* [N][A][capacity] ActionBuffer.values                           */
+  int32_t* times;             /* [N][A][capacity] ActionBuffer.times                            */
+  int32_t* len;               /* [N][A] len(ActionBuffer)                                       */
+  int32_t* clock;             /* [N] the stamp of the last training step                        */
+  int32_t n, n_states, n_actions, capacity, k, reserved_;
+} cobel_mfec_mem_t;
+
+typedef struct {
+  int32_t* inst;              /* [N][COBEL_I_WORDS]; COBEL_I_FLAGS bit 0: a trial is under way  */
+  unsigned long long* lat_sum; /* monitors as in cobel_tab_run_t; each may be NULL              */
+  unsigned long long* lat_cnt;
+  double* reward_sum;
+  unsigned long long* resp_cnt;
+  int32_t* lat_trace;         /* [N][trial_cap] or NULL                                         */
+  unsigned long long* occupancy;
+  unsigned long long* steps_done;
+  int32_t* last_exp;          /* [N][6] as in cobel_tab_run_t (td = 0), or NULL                 */
+  int32_t* ep_sa;             /* [N][steps_per_trial] scratch: the episode, state | action << 16 */
+  double* ep_value;           /* [N][steps_per_trial] scratch: its rewards, then its returns    */
+  double* trace;              /* [N][trace_cap][4 + A] or NULL: state, action, reward, end and the
+                                 estimates handed to the policy, of every step                 */
+  int32_t* trace_len;         /* [N] rows of trace written so far (NULL iff trace is)           */
+  int32_t n, trial_cap, mon_stripes, trace_cap;
+  uint32_t instance_base, flags; /* COBEL_F_LEARN (train: episodes are written back) |
+                                    COBEL_F_TEST_STREAM                                         */
+  int32_t trials_target, steps_per_trial, step_budget, reserved_;
+  double gamma;               /* MFEC.gamma                                                     */
+  double epsilon;             /* of the acting policy                                           */
+  uint64_t seed;
+} cobel_mfec_run_t;
+
+/* The two S x S tables of a world from its features [dev] [S][D]; rdist [dev] [S][S] and same
+ * [dev] [S][S] out.  COBEL_E_UNSUPPORTED beyond COBEL_MFEC_MAX_STATES / COBEL_MFEC_MAX_FEATURES. */
+COBEL_API int cobel_mfec_pairs(const double* features, int32_t n_states, int32_t n_features,
+                               double* rdist, uint8_t* same, void* stream);
+/* MFEC.train (agent/mfec.py:423-484; COBEL_F_LEARN) or MFEC.test (:486-532) in every instance, one
+ * wavefront each, until trials_target trials are done or step_budget (> 0) steps: reset, then per
+ * step retrieve_q (:405-421, QEC.estimate :173-200 per action) -> select_action -> env.step -> the
+ * episode row; at a terminal step the discounted returns backward through the episode (:472-476)
+ * and QEC.update_episode (:202-236) event by event.  A trial that times out leaves the memory as it
+ * was.  The world must be a single one (the tables of mem are its).  COBEL_E_UNSUPPORTED beyond
+ * COBEL_MFEC_MAX_STATES / _ACTIONS / _CAPACITY / _K. */
+COBEL_API int cobel_mfec_run(const cobel_world_t* world, const cobel_mfec_mem_t* mem,
+                             const cobel_mfec_run_t* run, void* stream);
+/* MFEC.predict_on_batch (agent/mfec.py:534-559) on frozen buffers: nodes [dev] [B], out [dev]
+ * [N][B][A]. */
+COBEL_API int cobel_mfec_estimate(const cobel_mfec_mem_t* mem, const int32_t* nodes,
+                                  int32_t n_nodes, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
