@@ -320,6 +320,40 @@ class MFECRun(C.Structure):
     ]
 
 
+RW_MAX_DIM = 64
+RW_POLICY_NONE, RW_POLICY_PROPORTIONAL, RW_POLICY_THRESHOLD, RW_POLICY_SIGMOID = range(4)
+
+
+class Seq(C.Structure):
+    """``cobel_seq_t``."""
+    _fields_ = [
+        ('obs_table', C.c_void_p), ('step_obs', C.c_void_p), ('step_action', C.c_void_p),
+        ('step_scalar', C.c_void_p), ('step_reward', C.c_void_p), ('trial_off', C.c_void_p),
+        ('schedule_of', C.c_void_p), ('cur_trial', C.c_void_p), ('cur_step', C.c_void_p),
+        ('n', C.c_int32), ('dim', C.c_int32), ('n_obs', C.c_int32), ('n_actions', C.c_int32),
+        ('n_schedules', C.c_int32), ('n_trials', C.c_int32), ('n_steps', C.c_int32),
+        ('overwrite', C.c_int32),
+    ]
+
+
+class RWRun(C.Structure):
+    """``cobel_rw_run_t``."""
+    _fields_ = [
+        ('W', C.c_void_p), ('lr', C.c_void_p), ('pol', C.c_void_p), ('pol_ctr', C.c_void_p),
+        ('instance_ids', C.c_void_p), ('mid', C.c_void_p), ('trew', C.c_void_p),
+        ('trial_reward', C.c_void_p), ('trial_steps', C.c_void_p), ('trial_action', C.c_void_p),
+        ('trace', C.c_void_p), ('trace_len', C.c_void_p), ('steps_done', C.c_void_p),
+        ('n', C.c_int32), ('trial_cap', C.c_int32), ('trace_cap', C.c_int32),
+        ('lr_rows', C.c_int32), ('pol_rows', C.c_int32), ('policy', C.c_int32),
+        ('code_reverse', C.c_int32), ('reserved_', C.c_int32),
+        ('instance_base', C.c_uint32), ('flags', C.c_uint32),
+        ('pol_stream', C.c_uint32), ('reserved2_', C.c_uint32),
+        ('trial_first', C.c_int32), ('trials', C.c_int32), ('steps_per_trial', C.c_int32),
+        ('step_budget', C.c_int32),
+        ('seed', C.c_uint64),
+    ]
+
+
 class SRRun(C.Structure):
     """``cobel_sr_run_t``."""
     _fields_ = [
@@ -412,6 +446,11 @@ _SIGNATURES = {
     'cobel_mfec_pairs': (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P]),
     'cobel_mfec_run': (C.c_int, [_P, C.POINTER(MFECMem), C.POINTER(MFECRun), _P]),
     'cobel_mfec_estimate': (C.c_int, [C.POINTER(MFECMem), _P, C.c_int32, _P, _P]),
+    'cobel_rw_plan': (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32 * 4)]),
+    'cobel_rw_run': (C.c_int, [C.POINTER(Seq), C.POINTER(RWRun), _P]),
+    'cobel_rw_predict': (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P]),
+    'cobel_seq_step': (C.c_int, [C.POINTER(Seq), _P, _P, _P, _P, _P, _P]),
+    'cobel_seq_reset': (C.c_int, [C.POINTER(Seq), _P, _P]),
     'cobel_adam_step': (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int32,
                                   C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _P,
                                   C.c_double, _P]),

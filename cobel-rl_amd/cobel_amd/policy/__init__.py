@@ -1,2 +1,3 @@
 from .greedy import EpsilonGreedy  # noqa: F401
 from .policy import Policy  # noqa: F401
+from .scalar import Proportional, Sigmoid, Threshold  # noqa: F401

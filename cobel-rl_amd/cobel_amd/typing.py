@@ -2,7 +2,7 @@
 import unchanged.  Only the names the accelerated path's demos and tests use."""
 from __future__ import annotations
 
-from typing import Any, Callable
+from typing import Any, Callable, TypedDict
 
 import numpy as np
 
@@ -15,3 +15,15 @@ Logs = dict
 Callback = Callable[[dict], Any]
 CallbackDict = dict    # {'on_trial_begin' | 'on_step_begin' | 'on_step_end' | 'on_trial_end' | ...: [callables]}
 NDArray = np.ndarray
+
+
+class TrialStep(TypedDict):
+    """One step of a predefined trial (interface/sequence.py:16-19): the name of its observation,
+    its reward — one float, or an array indexed by the action — and an action that may overwrite
+    the agent's."""
+    observation: str
+    reward: Any            # float | NDArray
+    action: Any            # None | int
+
+
+Trial = list               # list[TrialStep] (interface/sequence.py:22)

@@ -1235,6 +1235,86 @@ COBEL_API int cobel_mfec_run(const cobel_world_t* world, const cobel_mfec_mem_t*
 COBEL_API int cobel_mfec_estimate(const cobel_mfec_mem_t* mem, const int32_t* nodes,
                                   int32_t n_nodes, double* out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Associative learning: the Sequence environment (interface/sequence.py:25-215), the scalar
+ * policies Proportional / Threshold / Sigmoid (policy/scalar.py:13-300) and the agents
+ * RescorlaWagner / BinaryRescorlaWagner (agent/rw.py:15-376).  Everything is float64.
+ *
+ * A Sequence is compiled once into tables shared by all instances: the observation table (row 0 is
+ * the zero observation of zero_current(), sequence.py:115-127), per schedule step the index of its
+ * observation, its reward row with the flag "the reward is one float" (sequence.py:159), its forced
+ * action (-1: None), and per schedule the offsets of its trials.  An instance follows one schedule;
+ * its position (current_trial, current_step) lives on the device.
+ *
+ * An instance takes a group of G lanes, G = dim rounded up to a power of two, one lane per weight.
+ * W @ state is the balanced binary tree over G leaves W[j] * state[j] (each rounded; leaves beyond
+ * dim are +0.0), adjacent leaves first. */
+#define COBEL_RW_MAX_DIM 64
+#define COBEL_RW_POLICY_NONE 0          /* RescorlaWagner: the value itself is the action        */
+#define COBEL_RW_POLICY_PROPORTIONAL 1  /* policy/scalar.py:52-68, one double draw per step      */
+#define COBEL_RW_POLICY_THRESHOLD 2     /* :151-172, one bounded draw per step inside the window */
+#define COBEL_RW_POLICY_SIGMOID 3       /* :256-274, one double draw per step                    */
+
+typedef struct {
+  const double* obs_table;    /* [n_obs][dim]; row 0 is all zero                                */
+  const int32_t* step_obs;    /* [n_steps] row of obs_table                                     */
+  const int32_t* step_action; /* [n_steps] TrialStep['action'], -1 for None                     */
+  const uint8_t* step_scalar; /* [n_steps] 1: the reward is one float (column 0 of its row)     */
+  const double* step_reward;  /* [n_steps][n_actions]                                           */
+  const int32_t* trial_off;   /* [n_schedules][n_trials + 1] first step of every trial          */
+  const int32_t* schedule_of; /* [n] schedule of every instance, or NULL: schedule 0            */
+  int32_t* cur_trial;         /* [n] Sequence.current_trial                                     */
+  int32_t* cur_step;          /* [n] Sequence.current_step                                      */
+  int32_t n, dim, n_obs, n_actions, n_schedules, n_trials, n_steps, overwrite;
+} cobel_seq_t;
+
+typedef struct {
+  double* W;                  /* [n][dim] the weights                                           */
+  const double* lr;           /* [lr_rows][dim] learning rates                                  */
+  const double* pol;          /* [pol_rows][4] threshold, window / 2, scale, value_max; or NULL */
+  uint32_t* pol_ctr;          /* [n] draws taken from the policy's stream so far; or NULL       */
+  const uint32_t* instance_ids; /* [n] stream instance numbers, or NULL: instance_base + i      */
+  int32_t* mid;               /* [n] 1: a trial is under way (step_budget ran out inside it)    */
+  double* trew;               /* [n] its reward so far                                          */
+  double* trial_reward;       /* [n][trial_cap] logs['trial_reward'] of every trial, or NULL    */
+  int32_t* trial_steps;       /* [n][trial_cap] logs['steps'] (index of its last step), or NULL */
+  int32_t* trial_action;      /* [n][trial_cap] logs['action'] (its last action), or NULL       */
+  double* trace;              /* [n][trace_cap][4] value, action, reward, end of every step, or
+                                 NULL                                                           */
+  int32_t* trace_len;         /* [n] rows of trace written so far (NULL iff trace is)           */
+  unsigned long long* steps_done; /* env steps executed, added to; or NULL                      */
+  int32_t n, trial_cap, trace_cap, lr_rows, pol_rows, policy, code_reverse, reserved_;
+  uint32_t instance_base, flags;  /* COBEL_F_LEARN: train (the weights are updated)             */
+  uint32_t pol_stream, reserved2_;
+  int32_t trial_first;        /* row of the per-trial traces the session's first trial takes    */
+  int32_t trials;             /* trials to run                                                  */
+  int32_t steps_per_trial;    /* the cap of train(interface, trials, steps)                     */
+  int32_t step_budget;        /* > 0: stop after that many steps (launch per step)              */
+  uint64_t seed;
+} cobel_rw_run_t;
+
+/* Launch shape of cobel_rw_run for n instances of dim weights: out = {lanes per instance,
+ * instances per wavefront, instances per workgroup, workgroups}.  COBEL_E_UNSUPPORTED beyond
+ * COBEL_RW_MAX_DIM. */
+COBEL_API int cobel_rw_plan(int32_t dim, int32_t n, int32_t out[4]);
+/* RescorlaWagner.train / test (agent/rw.py:76-174) or BinaryRescorlaWagner.train / test
+ * (:267-376) with Sequence.reset / step and the policy's select_action inside, `trials` trials in
+ * every instance in one launch.  A trial cut by steps_per_trial is replayed from its first step.
+ * The caller guarantees that no instance runs past its last trial (the position depends on the
+ * schedule and the caps alone). */
+COBEL_API int cobel_rw_run(const cobel_seq_t* seq, const cobel_rw_run_t* run, void* stream);
+/* RescorlaWagner.predict_on_batch (agent/rw.py:176-192): out [dev] [n][n_batch] = W [dev] [n][dim]
+ * times batch [dev] [n_batch][dim], row by row in the summation order of cobel_rw_run. */
+COBEL_API int cobel_rw_predict(const double* W, int32_t n, int32_t dim, const double* batch,
+                               int32_t n_batch, double* out, void* stream);
+/* Sequence.step (interface/sequence.py:129-186) in every instance: action [dev] [n] in; obs [dev]
+ * [n][dim], reward [dev] [n], end [dev] [n] and info [dev] [n][2] = {'action', 'step_action'}
+ * (-1: None) out. */
+COBEL_API int cobel_seq_step(const cobel_seq_t* seq, const int32_t* action, double* obs,
+                             double* reward, uint8_t* end, int32_t* info, void* stream);
+/* Sequence.reset (interface/sequence.py:188-204) in every instance: obs [dev] [n][dim] out. */
+COBEL_API int cobel_seq_reset(const cobel_seq_t* seq, double* obs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
