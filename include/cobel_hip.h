@@ -886,23 +886,31 @@ COBEL_API int cobel_dqn_replay(const cobel_dqn_replay_t* run, void* stream);
  *
  * cobel_mlp_forward: out[j] = net[j / net_div](inputs of instance j), 32 rows per instance; the
  *   inputs are rows in_table[in_index[j / in_div][s]] of a float64 table or a dense block
- *   in_dense[j][32][D] in the network's dtype.
+ *   in_dense[j][32][D] in the network's dtype.  active[j / act_div] == 0: out[j] is not written.
+ *   Every array that a divisor indexes (in_index, active, the parameters by net_div; in
+ *   cobel_mlp_fit also targets by tgt_div and ep_index by ep_div) has ceil(n / divisor) entries:
+ *   n need not be a multiple of any of them.
  * cobel_mlp_fit: network j takes ONE optimisation step towards targets[j / tgt_div][32][O] on its
  *   32 input rows: loss = mean over the samples marked in sample_mask[j] (NULL: all) and the O
  *   outputs of (out - target)^2, torch.optim.Adam with the network's own step count steps[j]
- *   (incremented here), then w_target += tau * (w - w_target).  train[j] == 0: no optimiser step
- *   (parameters, moments and step count untouched) but the blend still happens, as the reference
+ *   (incremented here), then w_target += tau * (w - w_target).  The divisor of the mean is
+ *   max(number of marked samples, 1) * O: a network that trains with NOTHING marked (train NULL or
+ *   train[j] != 0 and an all-zero mask row) takes an Adam step on a zero gradient — its moments
+ *   decay, its parameters move by what is left of them, its step count goes up.
+ *   train[j] == 0: no optimiser step (parameters, moments and step count untouched, whatever the
+ *   mask says) but the blend still happens, as the reference
  *   blends every network pair every step (agent/dyna_q.py:1134-1143).  active[j / act_div] == 0:
- *   nothing at all.  Afterwards ep_out[j][ep_rows][O] receives the (updated) network's outputs
- *   for ep_rows <= 4 extra rows — row ep_table[ep_index[j / ep_div]] or ep_dense[j][ep_rows][D] —
- *   which is what the next action selection needs.
+ *   nothing at all (ep_out[j] included).  Afterwards ep_out[j][ep_rows][O] receives the (updated)
+ *   network's outputs — also of a network with train[j] == 0 — for ep_rows <= 4 extra rows: ONE
+ *   row ep_table[ep_index[j / ep_div]] (ep_rows == 1) or ep_dense[j][ep_rows][D]; that is what the
+ *   next action selection needs.  ep_rows == 0 or ep_out NULL: no extra rows, ep_out is not written.
  * ------------------------------------------------------------------------------------------ */
 typedef struct {
-  const void* w[3];        /* [M][out][in], network dtype */
+  const void* w[3];        /* [M][out][in], network dtype; M = ceil(n / net_div) */
   const void* b[3];        /* [M][out]                    */
-  const uint8_t* active;   /* [n / act_div] or NULL       */
+  const uint8_t* active;   /* [ceil(n / act_div)] or NULL */
   const double* in_table;  /* [rows][D] float64, or NULL  */
-  const int32_t* in_index; /* [n / in_div][32]            */
+  const int32_t* in_index; /* [ceil(n / in_div)][32]      */
   const void* in_dense;    /* [n][32][D], network dtype   */
   void* out;               /* [n][32][O]                  */
   int32_t n, n_inputs, n_outputs, is_float64;
@@ -920,14 +928,14 @@ typedef struct {
   void* v_b[3];
   double* steps;           /* [n] Adam step counts, += 1 for every network that trains            */
   const uint8_t* train;    /* [n] or NULL (= all)                                                 */
-  const uint8_t* active;   /* [n / act_div] or NULL                                               */
+  const uint8_t* active;   /* [ceil(n / act_div)] or NULL                                         */
   const double* in_table;  /* inputs as for cobel_mlp_forward                                     */
   const int32_t* in_index;
   const void* in_dense;
-  const void* targets;     /* [n / tgt_div][32][O], network dtype                                 */
+  const void* targets;     /* [ceil(n / tgt_div)][32][O], network dtype                           */
   const uint8_t* sample_mask; /* [n][32] or NULL                                                  */
   const double* ep_table;  /* extra rows: one row of a float64 table ...                          */
-  const int32_t* ep_index; /* ... [n / ep_div]                                                    */
+  const int32_t* ep_index; /* ... [ceil(n / ep_div)]                                              */
   const void* ep_dense;    /* ... or [n][ep_rows][D], network dtype                               */
   void* ep_out;            /* [n][ep_rows][O] or NULL                                             */
   int32_t n, n_inputs, n_outputs, is_float64;
