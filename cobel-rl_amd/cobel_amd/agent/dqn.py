@@ -174,6 +174,9 @@ class DQN(Agent):
             boot = self._target.forward(next_states)
             pick = (self._online.forward(next_states) if self.DDQN else boot).argmax(dim=2)
             boot = torch.gather(boot, 2, pick[..., None])[..., 0]
+            # (a terminal sample does not look at the target network, as in cobel_dqn_replay: its
+            #  target is the reward even where that network holds NaN or infinity)
+            boot = torch.where(terminals != 0, boot, torch.zeros_like(boot))
             new = rewards + boot * terminals * self.gamma
             targets.scatter_(2, actions[..., None], new[..., None])
         if self.target_update < 1.0:    # optimizer step and target blend in one pass

@@ -132,6 +132,8 @@ class DynaDQN(DQN):
             boot = self._target.forward(next_states)
             pick = (self._online.forward(next_states) if self.DDQN else boot).argmax(dim=2)
             boot = torch.gather(boot, 2, pick[..., None])[..., 0]
+            # (a terminal sample does not look at the target network, as in cobel_dqn_replay)
+            boot = torch.where(nt != 0, boot, torch.zeros_like(boot))
             new = r.to(self.dtype) + boot * nt.to(self.dtype) * self.gamma
             targets.scatter_(2, a[..., None], new[..., None])
         self.last_update += 1

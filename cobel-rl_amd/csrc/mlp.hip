@@ -559,6 +559,9 @@ __device__ __forceinline__ void dqn_replay_body(const mlp_args& A) {
 #pragma unroll
       for (int a = 1; a < kA; ++a) boot = L.qt[t * kA + a] > boot ? L.qt[t * kA + a] : boot;
     }
+    // (a terminal sample does not look at the target network: its target is the reward even where
+    //  that network holds NaN or infinity, which boot * 0 would carry into every parameter)
+    boot = my_nt != (T)0 ? boot : (T)0;
     L.boot[t] = my_r + (boot * my_nt) * (T)R.gamma;
   }
   lds_barrier();

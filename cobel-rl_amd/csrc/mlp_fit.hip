@@ -656,6 +656,9 @@ __device__ __forceinline__ void mlp_fit_body(const fit_args& A) {
         boot = L.qt[t * NA];
         for (int a = 1; a < NA; ++a) boot = L.qt[t * NA + a] > boot ? L.qt[t * NA + a] : boot;
       }
+      // (a terminal sample does not look at the target network: its target is the reward even
+      //  where that network holds NaN or infinity, which boot * 0 would carry into every parameter)
+      boot = my_nt != (T)0 ? boot : (T)0;
       L.tg[t] = my_reward + (boot * my_nt) * (T)A.gamma;
       L.aux[kB + t] = my_action;
     }

@@ -824,7 +824,9 @@ COBEL_API int cobel_adam_step(void* param /* [dev] [N][per_instance] */,
  * A = 4 (1 .. 8 on the streaming form: the six neighbours of a hexagonal Topology),
  * batches of 32, float64 or float32, MSE loss, torch.optim.Adam without amsgrad:
  *   targets = Q_online(s); targets[a] = r + gamma * nt * max_a' Q_target(s')   (agent/dqn.py:346-364;
- *             ddqn != 0: a' = argmax Q_online(s'), :352-355)
+ *             ddqn != 0: a' = argmax Q_online(s'), :352-355; a sample with nt == 0 does not look at
+ *             Q_target: its target is r even where the target network holds NaN or infinity — the
+ *             package's PyTorch paths, agent/dqn.py and agent/dyna_dqn.py, do the same)
  *   loss = mean((Q_online(s) - targets)^2); backward; Adam step   (network/network_torch.py:160-167)
  *   w_target += tau * (w_online - w_target)                       (agent/dqn.py:366-371; tau 0 = none)
  * Parameters are torch.nn.Linear tensors stacked over instances: w[l] [N][out][in], b[l] [N][out]

@@ -17,7 +17,6 @@ atol 1e-12.  float32: no number fixed in advance — the kernel's error against 
 (max-norm relative per tensor) must stay within 4x of the error torch's float32 on the CPU makes on
 the same inputs, with 64 * 2^-24 (a 64-term sum) as the floor.  Measured figures: docs/MEASUREMENTS.md
 section 14."""
-import ctypes as C
 import os
 import sys
 
@@ -27,22 +26,16 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import mlp_common as mc  # noqa: E402
 
+from mlp_gpu_common import (DEV, SENTINEL_U8, Framed, _dev, _host, _launch, _np,  # noqa: E402
+                            _stack_dev, _stack_host, _t32_fit_step, _t32_forward, _t32_grads,
+                            _torch_dtype, agree)
+
 pytestmark = pytest.mark.gpu
 
-DEV = 'cuda'
 SHAPES = [(1, 1), (7, 17), (8, 16), (9, 15), (17, 31), (24, 2), (31, 32), (32, 1)]
 RAGGED = [(9, 15), (17, 31)]
 DTYPES = ['f64', 'f32']
 HYPER = dict(lr=3e-3, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, tau=0.07)
-PAD = 96                   # sentinel elements in front of and behind every output
-SENTINEL, SENTINEL_U8 = -777.25, 0xA5
-# What torch's float32 may differ from the float64 reference by before the comparison is void (a
-# wrong reference would otherwise widen the kernel's bound with it).  Forward passes and gradients
-# are sums of at most 64 products: 1e-4 is 100x the largest figure measured (1e-6, D = O = 1).
-# After an Adam step a gradient's error is divided by sqrt(v) + eps — at most lr / eps = 3e5 times
-# a gradient error of ~1e-8 absolute for a network that starts from zero moments, measured 5e-5 —
-# and everything later follows the parameters: 1e-2.
-YARD_CAP, YARD_CAP_FIT = 1e-4, 1e-2
 FIGURES = {}               # (what, dtype, D, O) -> (kernel error, torch float32 error), the worst seen
 
 
@@ -55,105 +48,10 @@ def torch_cuda():
         print('mlp-edges figure %-12s %s D %2d O %2d  kernel %.2e  torch-f32 %.2e' % (key + FIGURES[key]))
 
 
-def _np(name):
-    return np.float64 if name == 'f64' else np.float32
-
-
-def _dev(torch, a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _host(t):
-    return t.detach().cpu().numpy()
-
-
-def _stack_dev(torch, stack):
-    return {k: _dev(torch, a) for k, a in stack.items()}
-
-
-def _launch(name, run):
-    from cobel_amd import _lib
-    _lib.check(getattr(_lib.lib(), name)(C.byref(run), None))
-
-
-class Framed:
-    """An output tensor in the middle of a buffer of sentinels."""
-
-    def __init__(self, torch, shape, dtype, fill=SENTINEL):
-        count = int(np.prod(shape))
-        self.fill = fill
-        self.buf = torch.full((count + 2 * PAD,), fill, dtype=dtype, device=DEV)
-        self.view = self.buf[PAD:PAD + count].view(shape)
-
-    def intact(self):
-        return bool((self.buf[:PAD] == self.fill).all() and (self.buf[-PAD:] == self.fill).all())
-
-    def untouched(self, j):
-        return bool((self.view[j] == self.fill).all())
-
-
-def _torch_dtype(torch, name):
-    return torch.float64 if name == 'f64' else torch.float32
-
-
-# ---------------------------------------------------------------------------------------------
-# torch's float32 on the CPU: the yardstick of the float32 kernels
-def _t32_forward(torch, p, x):
-    h = torch.relu(x @ p['w1'].T + p['b1'])
-    h = torch.relu(h @ p['w2'].T + p['b2'])
-    return h @ p['w3'].T + p['b3']
-
-
-def _t32_loss(torch, p, x, y, mask):
-    q = _t32_forward(torch, p, x)
-    on = torch.ones(x.shape[0]) if mask is None else torch.from_numpy((mask != 0).astype(np.float32))
-    return (((q - y) ** 2) * on[:, None]).sum() / (max(float(on.sum()), 1.0) * q.shape[1])
-
-
-def _t32_grads(torch, p, x, y, mask):
-    leaf = {k: a.clone().requires_grad_() for k, a in p.items()}
-    _t32_loss(torch, leaf, x, y, mask).backward()
-    return {k: a.grad for k, a in leaf.items()}
-
-
-def _t32_fit_step(torch, net, x, y, mask, train, hyper):
-    out = dict(net)
-    if train:
-        leaf = {k: a.clone().requires_grad_() for k, a in net['p'].items()}
-        opt = torch.optim.Adam([leaf[k] for k in mc.KEYS], lr=hyper['lr'], eps=hyper['eps'],
-                               betas=(hyper['beta1'], hyper['beta2']),
-                               weight_decay=hyper['weight_decay'])
-        for k in mc.KEYS:
-            opt.state[leaf[k]] = {'step': torch.tensor(float(net['steps'])),
-                                  'exp_avg': net['m'][k].clone(), 'exp_avg_sq': net['v'][k].clone()}
-        _t32_loss(torch, leaf, x, y, mask).backward()
-        opt.step()
-        out['p'] = {k: leaf[k].detach() for k in mc.KEYS}
-        out['m'] = {k: opt.state[leaf[k]]['exp_avg'] for k in mc.KEYS}
-        out['v'] = {k: opt.state[leaf[k]]['exp_avg_sq'] for k in mc.KEYS}
-        out['steps'] = net['steps'] + 1.0
-    if hyper['tau'] != 0.0 and net.get('t') is not None:
-        out['t'] = {k: torch.lerp(net['t'][k], out['p'][k], hyper['tau']) for k in mc.KEYS}
-    return out
-
-
 def _agree(what, name, D, O, got, ref, t32=None, grad=False, where=None):
     """The kernel's ``got`` against the float64 ``ref``; float32: measured against torch's."""
-    if name == 'f64':
-        if grad:
-            err = mc.rel_err(got, ref)
-            assert err <= 1e-12, (what, where, err)
-        else:
-            assert np.allclose(got, ref, rtol=1e-9, atol=1e-12), \
-                (what, where, float(np.abs(got - ref).max()))
-        return
-    kernel, yard = mc.rel_err(got, ref), mc.rel_err(_host(t32), ref)
-    # (the yardstick has to be one: torch's float32 and the reference compute the same thing)
-    assert yard <= (YARD_CAP_FIT if what.startswith('fit-') else YARD_CAP), (what, where, yard)
-    key = (what, name, D, O)
-    if key not in FIGURES or kernel > FIGURES[key][0]:
-        FIGURES[key] = (kernel, yard)
-    assert kernel <= mc.f32_bound(yard), (what, where, 'kernel %.3e torch %.3e' % (kernel, yard))
+    agree(FIGURES, (what, name, D, O), name, got, ref, t32, grad, where,
+          after_adam=what.startswith('fit-'))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -421,10 +319,6 @@ def test_fit_backward_pass_in_isolation(torch_cuda, name, D, O):
                        g32[k] if g32 else None, grad=True, where=(masked, j, k))
                 _agree('gradsq', name, D, O, v[k][j].astype(np.float64) / c2, g[k] * g[k],
                        g32[k] * g32[k] if g32 else None, grad=True, where=(masked, j, k))
-
-
-def _stack_host(stack):
-    return {k: _host(a) for k, a in stack.items()}
 
 
 @pytest.mark.parametrize('D,O', RAGGED)

@@ -1779,7 +1779,9 @@ def test_fused_dqn_replay_equals_torch_path(torch_cuda, dtype_name, n_in, ddqn, 
     both Adam moments after every one of 10 steps fed with the same batches (duplicated samples,
     terminal transitions, an activity mask that changes from step to step, weight decay).
     kernel: the form of the step cobel_dqn_replay picks by itself (None), or one of the two pinned
-    (COBEL_DEBUG_DQN_KERNEL: parameters staged in LDS / weight operands streamed from memory)."""
+    (COBEL_DEBUG_DQN_KERNEL: parameters staged in LDS / weight operands streamed from memory).
+    One step of either form against a float64 reference — targets, gradients, DDQN ties, ring slots,
+    q_out, 1 .. 8 actions, every width boundary — is tests/test_gpu_dqn_replay_edges.py."""
     if kernel:
         os.environ['COBEL_DEBUG'], os.environ['COBEL_DEBUG_DQN_KERNEL'] = '1', kernel
         try:

@@ -1,7 +1,7 @@
 """The float64 reference of the stacked-network kernels (tests/mlp_common.py) against torch on
 the CPU — autograd, torch.optim.Adam, lerp, and the torch expressions of DynaDSR.replay's PyTorch
-path — and the argument checks of cobel_mlp_query / cobel_mlp_forward / cobel_mlp_fit /
-cobel_dsr_targets, which return before any launch.  No GPU."""
+path and of the DQN replay step's — and the argument checks of cobel_mlp_query / cobel_mlp_forward /
+cobel_mlp_fit / cobel_dsr_targets / cobel_dqn_replay, which return before any launch.  No GPU."""
 import ctypes as C
 import os
 import sys
@@ -142,6 +142,129 @@ def test_reference_dsr_targets_match_torch_expressions(A, switches):
 
 
 # ---------------------------------------------------------------------------------------------
+# the DQN replay step
+@pytest.mark.parametrize('ddqn', [False, True])
+@pytest.mark.parametrize('D,A', [(6, 4), (25, 4), (31, 6), (1, 1)])
+def test_reference_dqn_step_matches_torch_replay_path(D, A, ddqn):
+    """dqn_step against this package's PyTorch replay path restated in float64 on the CPU
+    (targets = forward(s).clone(), scatter_ of r + boot * nt * gamma, MSE, autograd,
+    torch.optim.Adam, lerp), from a pre-seeded optimizer state with weight decay: gradients to
+    1e-12, parameters, moments, the blended target and q_out to rtol 1e-9 / atol 1e-12."""
+    import torch
+    gamma = 0.8
+    c = mc.dqn_case(10 * D + A, 3, D, A, np.float64, ddqn=ddqn)
+    for j in range(3):
+        net = {'p': mc.one(c['P'], j), 't': mc.one(c['T'], j), 'm': mc.one(c['M'], j),
+               'v': mc.one(c['V'], j), 'steps': float(c['steps'][j])}
+        b = mc.dqn_rows(c, j)
+        obs = c['table'][j]
+        out, g, q_out = mc.dqn_step(net, b, HYPER, gamma, ddqn, obs)
+        assert out['steps'] == net['steps']
+
+        tp = {k: torch.tensor(a, requires_grad=True) for k, a in net['p'].items()}
+        tt = {k: torch.tensor(a) for k, a in net['t'].items()}
+        opt = torch.optim.Adam([tp[k] for k in mc.KEYS], lr=HYPER['lr'], eps=HYPER['eps'],
+                               betas=(HYPER['beta1'], HYPER['beta2']),
+                               weight_decay=HYPER['weight_decay'])
+        for k in mc.KEYS:     # (the optimizer counts the steps before this one)
+            opt.state[tp[k]] = {'step': torch.tensor(net['steps'] - 1.0),
+                                'exp_avg': torch.tensor(net['m'][k]),
+                                'exp_avg_sq': torch.tensor(net['v'][k])}
+        s, ns = torch.tensor(b['states']), torch.tensor(b['next_states'])
+        a, r, nt = torch.tensor(b['actions']), torch.tensor(b['rewards']), torch.tensor(b['nonterminal'])
+        with torch.no_grad():
+            targets = torch_forward(torch, tp, s).clone()
+            boot = torch_forward(torch, tt, ns)
+            pick = (torch_forward(torch, tp, ns) if ddqn else boot).argmax(dim=1)
+            boot = torch.gather(boot, 1, pick[:, None])[:, 0]
+            new = r + boot * nt * gamma
+            targets.scatter_(1, a[:, None], new[:, None])
+        assert np.allclose(mc.dqn_targets(net['p'], net['t'], b['next_states'], b['rewards'],
+                                          b['nonterminal'], gamma, ddqn), new.numpy(),
+                           rtol=1e-9, atol=1e-12)
+        ((torch_forward(torch, tp, s) - targets) ** 2).mean().backward()
+        for k in mc.KEYS:
+            assert mc.rel_err(g[k], tp[k].grad.numpy()) <= 1e-12, (j, k)
+        opt.step()
+        with torch.no_grad():
+            for k in mc.KEYS:
+                tt[k] = torch.lerp(tt[k], tp[k], HYPER['tau'])
+            want_q = torch_forward(torch, tp, torch.tensor(obs)[None])[0]
+        for k in mc.KEYS:
+            st = opt.state[tp[k]]
+            for name, got, want in (('p', out['p'][k], tp[k].detach()), ('m', out['m'][k], st['exp_avg']),
+                                    ('v', out['v'][k], st['exp_avg_sq']), ('t', out['t'][k], tt[k])):
+                assert np.allclose(got, want.numpy(), rtol=1e-9, atol=1e-12), (j, k, name)
+            assert float(st['step']) == net['steps']
+        assert np.allclose(q_out, want_q.numpy(), rtol=1e-9, atol=1e-12)
+
+
+@pytest.mark.parametrize('A', [1, 2, 3, 4, 8])
+def test_reference_dqn_targets_on_planted_ties(A):
+    """Tied actions planted so that they are exact in any summation order (zero rows of w3, equal
+    b3): the first tied action is taken, and the target network's value at it is the bootstrap."""
+    rng = np.random.default_rng(A)
+    D, gamma = 5, 0.9
+    x = rng.standard_normal((mc.B, D))
+    r, nt = rng.standard_normal(mc.B), np.ones(mc.B)
+    t = mc.one(mc.draw_networks(rng, 1, D, A, np.float64), 0)
+    qt = mc.forward(t, x)[2]
+    plans = [(list(range(A)), 0.3), ([0], 10.0), ([A - 1], 10.0),
+             (sorted({min(1, A - 1), min(3, A - 1)}), 10.0)]
+    for tied, value in plans:
+        stack = mc.draw_networks(rng, 1, D, A, np.float32)
+        mc.plant_tie(stack, 0, tied, value)
+        p = mc.one(stack, 0)
+        q = mc.forward(p, x)[2]
+        assert (q[:, tied] == np.float64(np.float32(value))).all()        # exact, every sample
+        assert (mc.first_maximum(q.T[None])[0] == tied[0]).all()
+        new = mc.dqn_targets(p, t, x, r, nt, gamma, True)
+        assert np.array_equal(new, r + (qt[:, tied[0]] * nt) * gamma)
+        if len(tied) > 1:        # ... which is not what a later tied action would have given
+            assert (qt[:, tied[0]] != qt[:, tied[-1]]).all()
+    # a terminal sample does not look at the target network
+    nan = {k: np.full_like(a, np.nan) for k, a in t.items()}
+    assert np.array_equal(mc.dqn_targets(p, nan, x, r, np.zeros(mc.B), gamma, False), r)
+    assert np.array_equal(mc.dqn_targets(p, nan, x, r, np.zeros(mc.B), gamma, True), r)
+
+
+def _gpu_test_shapes():
+    lds = [(D, 4) for D in (1, 8, 9, 16, 17, 32)]
+    return lds + [(1, 1), (7, 8), (8, 4), (9, 3), (17, 5), (24, 2), (31, 6), (32, 4)]
+
+
+@pytest.mark.parametrize('D,A', sorted(set(_gpu_test_shapes())))
+def test_dqn_case_seed_search_succeeds_for_every_gpu_case(D, A):
+    """Every case the GPU tests draw (mlp_common.dqn_gpu_cases: their seed bases, instance counts
+    and plants), at every shape they use and in both dtypes: dqn_case finds a seed within its 64
+    tries, the gap condition holds at that seed for every instance the plant does not exempt, and
+    the search is deterministic."""
+    for key, kw in mc.dqn_gpu_cases(D, A).items():
+        for dt in (np.float64, np.float32):
+            c = mc.dqn_gpu_case(key, D, A, dt)
+            n, ddqn = kw['n'], kw['ddqn']
+            assert kw['seed'] <= c['seed'] < kw['seed'] + 64 and c['n'] == n, key
+            assert bool(c['exempt']) == (key == 'ties' or key[0] == 'plain'), key
+            for j in set(range(n)) - c['exempt']:
+                p, t, b = mc.one(c['P'], j), mc.one(c['T'], j), mc.dqn_rows(c, j)
+                assert mc.top_two_gap(mc.forward(t, b['next_states'])[2]) >= mc.GAP, (key, j)
+                if ddqn:
+                    assert mc.top_two_gap(mc.forward(p, b['next_states'])[2]) >= mc.GAP, (key, j)
+                assert not np.array_equal(c['P']['w2'][j], c['T']['w2'][j])
+            assert c['P']['w1'].dtype == dt and c['rewards'].dtype == dt
+            if kw.get('steps') is None:
+                assert len(set(c['steps'].tolist())) == n
+            zero = not any(c['V'][k].any() for k in mc.KEYS)
+            assert zero == bool(kw.get('zero_moments')), key
+        again = mc.dqn_gpu_case(key, D, A, np.float32)
+        assert again['seed'] == c['seed']
+        assert all(np.array_equal(again[k], c[k]) for k in ('table', 'next_index', 'actions'))
+        assert np.array_equal(again['P']['w3'], c['P']['w3'])
+    q = np.array([[0.0, 1.0, 1.0 - 0.5e-3], [2.0, -1.0, 0.0]])
+    assert abs(mc.top_two_gap(q) - 0.25e-3) < 1e-12 and mc.top_two_gap(q[:, :1]) == np.inf
+
+
+# ---------------------------------------------------------------------------------------------
 # argument checks through the C ABI: every call below returns before it would launch anything
 FAKE = 0x10000           # a 16-byte aligned address nobody dereferences
 
@@ -274,3 +397,68 @@ def test_mlp_argument_checks():
         assert 50000 < lds.value <= 53 * 1024         # activations only, whatever the shape
         _lib.check(lib.cobel_mlp_query(D, 64, 64, O, 32, 0, C.byref(lds)))
         assert 25000 < lds.value <= 27 * 1024
+
+
+def _dqn_run(_lib):
+    run = _lib.DQNReplay()
+    for field in (run.w, run.b, run.w_target, run.b_target, run.m_w, run.m_b, run.v_w, run.v_b):
+        for k in range(3):
+            field[k] = FAKE
+    run.steps = run.states = run.next_states = run.actions = run.rewards = run.nonterminal = FAKE
+    run.n, run.n_inputs, run.n_hidden1, run.n_hidden2, run.n_actions, run.batch = 0, 9, 64, 64, 4, 32
+    run.is_float64 = 1
+    run.gamma, run.lr, run.beta1, run.beta2, run.eps, run.tau = 0.9, 3e-3, 0.9, 0.999, 1e-8, 0.07
+    return run
+
+
+def test_dqn_replay_argument_checks():
+    from cobel_amd import _lib
+    lib = _lib.lib()
+
+    def call(run):
+        _lib.check(lib.cobel_dqn_replay(C.byref(run), None))
+
+    call(_dqn_run(_lib))                              # nothing to do: OK, before any launch
+    run = _dqn_run(_lib)                              # the batch as table rows ...
+    run.states = run.next_states = None
+    run.state_index = run.next_index = run.obs_table = FAKE
+    call(run)
+    run.batch_slots, run.ring_slots = FAKE, 40        # ... which the rings' slots do not go with
+    with pytest.raises(AssertionError):
+        call(run)
+    for missing in ('next_index', 'obs_table'):
+        run = _dqn_run(_lib)
+        run.state_index = run.next_index = run.obs_table = FAKE
+        setattr(run, missing, None)
+        with pytest.raises(AssertionError):
+            call(run)
+    run = _dqn_run(_lib)                              # q_out: the row number of every instance
+    run.q_out = run.obs_table = FAKE
+    with pytest.raises(AssertionError):
+        call(run)
+    run.obs_index = FAKE
+    call(run)
+    run.obs_table = None
+    with pytest.raises(AssertionError):
+        call(run)
+    run = _dqn_run(_lib)                              # slots into rings of no rows
+    run.batch_slots = FAKE
+    with pytest.raises(IndexError):
+        call(run)
+    run.ring_slots = 1
+    call(run)
+    for field, layer in (('w', 1), ('w', 2), ('w_target', 1), ('w_target', 2)):
+        run = _dqn_run(_lib)                          # the 64-wide matrices: whole vector loads
+        getattr(run, field)[layer] = FAKE + 8
+        with pytest.raises(AssertionError):
+            call(run)
+    for field, bad in (('n_actions', 9), ('n_actions', 0), ('batch', 31), ('n_hidden1', 32),
+                       ('n_hidden2', 32), ('n_inputs', 33)):
+        run = _dqn_run(_lib)
+        setattr(run, field, bad)
+        with pytest.raises(NotImplementedError):
+            call(run)
+    for A in (1, 8):                                  # every accepted action count
+        run = _dqn_run(_lib)
+        run.n_actions = A
+        call(run)
