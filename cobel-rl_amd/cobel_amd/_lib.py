@@ -354,6 +354,29 @@ class RWRun(C.Structure):
     ]
 
 
+ANET_MAX_ACTIONS = 9
+
+
+class ANetRun(C.Structure):
+    """``cobel_anet_run_t``."""
+    _fields_ = [
+        ('We', C.c_void_p), ('Wi', C.c_void_p), ('sat_e', C.c_void_p), ('sat_i', C.c_void_p),
+        ('lr_e', C.c_void_p), ('lr_i', C.c_void_p), ('eps', C.c_void_p), ('pol_ctr', C.c_void_p),
+        ('agent_ctr', C.c_void_p), ('instance_ids', C.c_void_p), ('mid', C.c_void_p),
+        ('trew', C.c_void_p), ('trial_reward', C.c_void_p), ('trial_steps', C.c_void_p),
+        ('trial_action', C.c_void_p), ('trace', C.c_void_p), ('trace_len', C.c_void_p),
+        ('steps_done', C.c_void_p),
+        ('n', C.c_int32), ('n_actions', C.c_int32), ('trial_cap', C.c_int32),
+        ('trace_cap', C.c_int32), ('sat_rows', C.c_int32), ('lr_rows', C.c_int32),
+        ('eps_rows', C.c_int32), ('linear_update', C.c_int32),
+        ('instance_base', C.c_uint32), ('flags', C.c_uint32),
+        ('pol_stream', C.c_uint32), ('reserved_', C.c_uint32),
+        ('trial_first', C.c_int32), ('trials', C.c_int32), ('steps_per_trial', C.c_int32),
+        ('step_budget', C.c_int32),
+        ('alpha', C.c_double), ('noise', C.c_double), ('seed', C.c_uint64),
+    ]
+
+
 class SRRun(C.Structure):
     """``cobel_sr_run_t``."""
     _fields_ = [
@@ -451,6 +474,10 @@ _SIGNATURES = {
     'cobel_rw_predict': (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P]),
     'cobel_seq_step': (C.c_int, [C.POINTER(Seq), _P, _P, _P, _P, _P, _P]),
     'cobel_seq_reset': (C.c_int, [C.POINTER(Seq), _P, _P]),
+    'cobel_anet_plan': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32 * 4)]),
+    'cobel_anet_run': (C.c_int, [C.POINTER(Seq), C.POINTER(ANetRun), _P]),
+    'cobel_anet_predict': (C.c_int, [C.POINTER(ANetRun), C.c_int32, _P, C.c_int32, _P, _P]),
+    'cobel_anet_update': (C.c_int, [C.POINTER(ANetRun), C.c_int32, _P, _P, _P, _P]),
     'cobel_adam_step': (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int32,
                                   C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _P,
                                   C.c_double, _P]),

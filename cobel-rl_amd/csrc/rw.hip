@@ -24,18 +24,11 @@
 //
 // The file is compiled with -ffp-contract=off: lr * (v - target) * state is two rounded
 // multiplications, the subtraction from W a third rounding, as NumPy evaluates it.
-#include "cobel_common.h"
+#include "cobel_seq.h"
 
 namespace {
 
-constexpr int kWaves = 4;   // wavefronts per workgroup
-
-__device__ __forceinline__ double group_sum(double p, int G) {
-  for (int o = 1; o < G; o <<= 1) p = p + __shfl_xor(p, o);
-  return p;
-}
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+using namespace cobel_seq;
 
 // int(action) of interface/sequence.py:155 for a float64 (truncation; what Python refuses — NaN,
 // infinities — and what does not fit becomes a bound)
@@ -55,7 +48,7 @@ struct rw_args {
 __global__ __launch_bounds__(64 * kWaves) void k_rw_run(const rw_args K) {
   const cobel_seq_t& S = K.s;
   const cobel_rw_run_t& R = K.r;
-  const int G = K.G, D = S.dim, A = S.n_actions;
+  const int G = K.G, D = S.dim;
   const int per_wave = 64 / G;
   const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
   const int j = lane & (G - 1);
@@ -73,8 +66,7 @@ __global__ __launch_bounds__(64 * kWaves) void k_rw_run(const rw_args K) {
   const double* const pp = R.pol ? R.pol + (size_t)(R.pol_rows > 1 ? i : 0) * 4 : nullptr;
   const double p_thr = pp ? pp[0] : 0.0, p_win = pp ? pp[1] : 0.0, p_scale = pp ? pp[2] : 0.0,
                p_vmax = pp ? pp[3] : 1.0;
-  const int sched = clampi(S.schedule_of ? S.schedule_of[i] : 0, 0, S.n_schedules - 1);
-  const int32_t* const toff = S.trial_off + (size_t)sched * (S.n_trials + 1);
+  const int32_t* const toff = trial_offsets(S, i);
 
   int ct = S.cur_trial[i], cs = S.cur_step[i];
   bool mid = R.mid[i] != 0;
@@ -92,10 +84,8 @@ __global__ __launch_bounds__(64 * kWaves) void k_rw_run(const rw_args K) {
       trew = 0.0;
       mid = true;
     }
-    const int tc = clampi(ct, 0, S.n_trials - 1);
-    const int base = toff[tc];
-    const int len = toff[tc + 1] - base;
-    const int at = clampi(base + clampi(cs, 0, len - 1), 0, S.n_steps - 1);
+    int base, len;
+    const int at = step_at(S, toff, ct, cs, base, len);
     const int oi = clampi(S.step_obs[at], 0, S.n_obs - 1);
     const double x = (mine && alive) ? S.obs_table[(size_t)oi * D + j] : 0.0;
     // predict_on_batch (agent/rw.py:176-192)
@@ -122,14 +112,7 @@ __global__ __launch_bounds__(64 * kWaves) void k_rw_run(const rw_args K) {
       action = abs(R.code_reverse - (u < prob ? 1 : 0));
     }
     // Sequence.step (interface/sequence.py:129-186)
-    const int forced = S.step_action[at];
-    double reward;
-    if (S.step_scalar[at]) {
-      reward = S.step_reward[(size_t)at * A];
-    } else {
-      const int a = clampi((S.overwrite && forced >= 0) ? forced : action, 0, A - 1);
-      reward = S.step_reward[(size_t)at * A + a];
-    }
+    const double reward = step_reward(S, at, action);
     const bool end = cs + 1 >= len;
     if (alive) {
       if (learn) {   // W -= learning_rate * (v - target) * state (agent/rw.py:110, 303-309)
@@ -209,25 +192,16 @@ __global__ __launch_bounds__(256) void k_seq_step(const cobel_seq_t S,
                                                   int32_t* __restrict__ info) {
   const int i = (int)(blockIdx.x * 256u + threadIdx.x);
   if (i >= S.n) return;
-  const int D = S.dim, A = S.n_actions;
-  const int sched = clampi(S.schedule_of ? S.schedule_of[i] : 0, 0, S.n_schedules - 1);
-  const int32_t* const toff = S.trial_off + (size_t)sched * (S.n_trials + 1);
+  const int D = S.dim;
+  const int32_t* const toff = trial_offsets(S, i);
   const int ct = S.cur_trial[i];
   int cs = S.cur_step[i];
-  const int tc = clampi(ct, 0, S.n_trials - 1);
-  const int base = toff[tc];
-  const int len = toff[tc + 1] - base;
+  int base, len;
+  const int at = step_at(S, toff, ct, cs, base, len);
   if (action) {
-    const int at = clampi(base + clampi(cs, 0, len - 1), 0, S.n_steps - 1);
     const int forced = S.step_action[at];
     const int a_agent = action[i];
-    double reward;
-    if (S.step_scalar[at]) {
-      reward = S.step_reward[(size_t)at * A];
-    } else {
-      const int a = clampi((S.overwrite && forced >= 0) ? forced : a_agent, 0, A - 1);
-      reward = S.step_reward[(size_t)at * A + a];
-    }
+    const double reward = step_reward(S, at, a_agent);
     cs += 1;
     const bool end = cs >= len;
     // the next step's observation, or the zero observation (row 0) at the trial's end
@@ -241,44 +215,10 @@ __global__ __launch_bounds__(256) void k_seq_step(const cobel_seq_t S,
     S.cur_step[i] = cs;
     if (end) S.cur_trial[i] = ct + 1;
   } else {
-    const int at = clampi(base, 0, S.n_steps - 1);
-    const int oi = clampi(S.step_obs[at], 0, S.n_obs - 1);
+    const int oi = clampi(S.step_obs[clampi(base, 0, S.n_steps - 1)], 0, S.n_obs - 1);
     for (int d = 0; d < D; ++d) obs[(size_t)i * D + d] = S.obs_table[(size_t)oi * D + d];
     S.cur_step[i] = 0;
   }
-}
-
-int group_lanes(int dim) {
-  int G = 1;
-  while (G < dim) G <<= 1;
-  return G;
-}
-
-int check_seq(const cobel_seq_t* s, const char* who) {
-  COBEL_REQUIRE(s, COBEL_E_ARG, "%s: NULL sequence", who);
-  COBEL_REQUIRE(s->dim >= 1 && s->dim <= COBEL_RW_MAX_DIM, COBEL_E_UNSUPPORTED,
-                "%s: observations of %d components (a Sequence serves 1 to %d)", who, s->dim,
-                COBEL_RW_MAX_DIM);
-  COBEL_REQUIRE(s->n >= 0, COBEL_E_RANGE, "%s: n = %d", who, s->n);
-  COBEL_REQUIRE(s->n_obs >= 1 && s->n_actions >= 1 && s->n_schedules >= 1 && s->n_trials >= 1 &&
-                    s->n_steps >= s->n_trials,
-                COBEL_E_RANGE,
-                "%s: %d observation rows, %d actions, %d schedules of %d trials, %d steps", who,
-                s->n_obs, s->n_actions, s->n_schedules, s->n_trials, s->n_steps);
-  COBEL_REQUIRE(s->obs_table && s->step_obs && s->step_action && s->step_scalar && s->step_reward &&
-                    s->trial_off && s->cur_trial && s->cur_step,
-                COBEL_E_ARG, "%s: NULL table", who);
-  COBEL_REQUIRE((((uintptr_t)s->obs_table | (uintptr_t)s->step_reward) & 7u) == 0 &&
-                    (((uintptr_t)s->step_obs | (uintptr_t)s->step_action | (uintptr_t)s->trial_off |
-                      (uintptr_t)s->schedule_of | (uintptr_t)s->cur_trial |
-                      (uintptr_t)s->cur_step) & 3u) == 0,
-                COBEL_E_ARG, "%s: misaligned table", who);
-  return COBEL_OK;
-}
-
-unsigned group_blocks(long long groups, int G) {
-  const long long per_block = (long long)kWaves * (64 / G);
-  return (unsigned)((groups + per_block - 1) / per_block);
 }
 
 }  // namespace

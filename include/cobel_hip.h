@@ -1325,6 +1325,77 @@ COBEL_API int cobel_seq_step(const cobel_seq_t* seq, const int32_t* action, doub
 /* Sequence.reset (interface/sequence.py:188-204) in every instance: obs [dev] [n][dim] out. */
 COBEL_API int cobel_seq_reset(const cobel_seq_t* seq, double* obs, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * AssociativeNetwork (agent/anet.py:15-374, Donoso et al. 2021) on a Sequence: excitatory and
+ * inhibitory weights [dim][n_actions - 1] with saturation, noisy outputs, an epsilon-greedy choice
+ * among the n_actions - 1 outputs.  Everything is float64.
+ *
+ * Packing and summation order are cobel_rw_run's: an instance takes a group of G lanes, lane j
+ * holds row j of both matrices; each of the 2 (n_actions - 1) dot products is the balanced tree
+ * over G leaves w[j][a] * state[j].  q[a] = (state @ We - state @ Wi)[a] + noise * u[a], the u[a]
+ * being n_actions - 1 consecutive double draws of COBEL_STREAM_AGENT at the instance's agent_ctr
+ * (anet.py:325-333); the selection is one double draw of pol_stream at pol_ctr (policy/greedy.py:
+ * 56-58, also where there is one output only). */
+#define COBEL_ANET_MAX_ACTIONS 9   /* n_actions 2 .. 9: one to eight outputs */
+
+typedef struct {
+  double* We;                 /* [n][dim][n_actions - 1] weights['excitatory']                  */
+  double* Wi;                 /* [n][dim][n_actions - 1] weights['inhibitory']                  */
+  const double* sat_e;        /* [sat_rows][dim][n_actions - 1] saturation['excitatory']        */
+  const double* sat_i;        /* ... ['inhibitory']                                             */
+  const double* lr_e;         /* [lr_rows][dim][n_actions - 1] learning_rate['excitatory']      */
+  const double* lr_i;         /* ... ['inhibitory']                                             */
+  const double* eps;          /* [eps_rows] epsilon of the policy                               */
+  uint32_t* pol_ctr;          /* [n] draws taken from the policy's stream so far                */
+  uint32_t* agent_ctr;        /* [n] draws taken from COBEL_STREAM_AGENT so far                 */
+  const uint32_t* instance_ids; /* [n] stream instance numbers, or NULL: instance_base + i      */
+  int32_t* mid;               /* [n] 1: a trial is under way (step_budget ran out inside it)    */
+  double* trew;               /* [n] its reward so far                                          */
+  double* trial_reward;       /* [n][trial_cap] logs['trial_reward'] of every trial, or NULL    */
+  int32_t* trial_steps;       /* [n][trial_cap] logs['steps'] (index of its last step), or NULL */
+  int32_t* trial_action;      /* [n][trial_cap] logs['action'] (its last action), or NULL       */
+  double* trace;              /* [n][trace_cap][3 + n_actions - 1] action, reward, end, q[0] ..
+                                 of every step, or NULL                                         */
+  int32_t* trace_len;         /* [n] rows of trace written so far (NULL iff trace is)           */
+  unsigned long long* steps_done; /* env steps executed, added to; or NULL                      */
+  int32_t n, n_actions;       /* n_actions: action_space.n of the agent (not the Sequence's)    */
+  int32_t trial_cap, trace_cap, sat_rows, lr_rows, eps_rows;
+  int32_t linear_update;      /* 1: delta.fill(1.0) (anet.py:354-355)                           */
+  uint32_t instance_base, flags;  /* COBEL_F_LEARN: train (update_q after every step)           */
+  uint32_t pol_stream, reserved_;
+  int32_t trial_first;        /* row of the per-trial traces the session's first trial takes    */
+  int32_t trials;             /* trials to run                                                  */
+  int32_t steps_per_trial;    /* the cap of train(interface, trials, steps)                     */
+  int32_t step_budget;        /* > 0: stop after that many steps (launch per step)              */
+  double alpha;               /* anet.py:353                                                    */
+  double noise;               /* noise_amplitude, anet.py:325                                   */
+  uint64_t seed;
+} cobel_anet_run_t;
+
+/* Launch shape of cobel_anet_run for n instances of dim observation components: out = {lanes per
+ * instance, instances per wavefront, instances per workgroup, workgroups}.  COBEL_E_UNSUPPORTED
+ * beyond COBEL_RW_MAX_DIM components or outside 2 .. COBEL_ANET_MAX_ACTIONS actions.  (No line of the
+ * reference corresponds: the launch shape is this library's.) */
+COBEL_API int cobel_anet_plan(int32_t dim, int32_t n_actions, int32_t n, int32_t out[4]);
+/* AssociativeNetwork.train / test (agent/anet.py:181-296) with Sequence.reset / step, retrieve_q
+ * (:311-333), EpsilonGreedy.select_action and, under COBEL_F_LEARN, update_q (:335-356) inside:
+ * `trials` trials in every instance in one launch.  A trial cut by steps_per_trial is replayed from
+ * its first step.  The caller guarantees that no instance runs past its last trial. */
+COBEL_API int cobel_anet_run(const cobel_seq_t* seq, const cobel_anet_run_t* run, void* stream);
+/* AssociativeNetwork.retrieve_q / predict_on_batch (agent/anet.py:311-333, 358-374): out [dev]
+ * [n][n_batch][n_actions - 1] for batch [dev] [n_batch][dim], the same rows for every instance.
+ * Row b of instance i takes the draws agent_ctr[i] + b (n_actions - 1) + a of COBEL_STREAM_AGENT;
+ * agent_ctr[i] advances by n_batch (n_actions - 1).  Of run: We, Wi, agent_ctr, instance_ids, n,
+ * n_actions, instance_base, noise and seed are read. */
+COBEL_API int cobel_anet_predict(const cobel_anet_run_t* run, int32_t dim, const double* batch,
+                                 int32_t n_batch, double* out, void* stream);
+/* AssociativeNetwork.update_q (agent/anet.py:335-356), one experience per instance: state [dev]
+ * [n][dim], action [dev] [n] (outside 0 .. n_actions - 2: nothing changes, as the reference's
+ * action_vector is all zero then), reward [dev] [n].  Of run: We, Wi, sat_*, lr_*, sat_rows,
+ * lr_rows, n, n_actions, linear_update and alpha are read. */
+COBEL_API int cobel_anet_update(const cobel_anet_run_t* run, int32_t dim, const double* state,
+                                const int32_t* action, const double* reward, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
