@@ -82,6 +82,49 @@ def adam_from_moments(p, m_new, v_new, step, lr, b1, b2, eps):
     return {k: p[k] - step_size * (m_new[k] / (np.sqrt(v_new[k]) / bc2_sqrt + eps)) for k in p}
 
 
+def _nudged(x, ulps):
+    """x moved by ``ulps`` floating-point neighbours (per element)."""
+    x = np.array(x, dtype=np.float64)
+    for _ in range(abs(int(ulps))):
+        x = np.nextafter(x, np.inf if ulps > 0 else -np.inf)
+    return x
+
+
+def adam_kernel(p, g, m, v, steps, hyper, dtype, target=None, active=None, pow_ulps=(0, 0)):
+    """cobel_adam_step as k_adam (csrc/adam.hip) performs it: the kernel's operations in the
+    kernel's order and dtype, one rounding each (the library builds with -ffp-contract=off), on
+    arrays [n, per_instance] of ``dtype`` with ``steps`` [n] the counts INCLUDING this step.
+    1 - beta1, beta2, eps, lr, weight_decay and tau are cast to ``dtype`` where the kernel casts
+    them; the bias corrections 1 - beta1^t and sqrt(1 - beta2^t) are formed in Python float64 and
+    cast (``pow_ulps``: beta1^t and beta2^t moved by that many float64 neighbours first — what
+    another pow may return).  Rows of instances outside ``active`` come back as they are.
+    Returns (param, exp_avg, exp_avg_sq, target or None)."""
+    T = np.dtype(dtype).type
+    for a in (p, g, m, v) + (() if target is None else (target,)):
+        assert a.dtype == np.dtype(dtype) and a.ndim == 2
+    lr, b1, b2, eps, wd, tau = (hyper[k] for k in ('lr', 'beta1', 'beta2', 'eps', 'weight_decay',
+                                                   'tau'))
+    x1 = _nudged([float(b1) ** float(t) for t in steps], pow_ulps[0])
+    x2 = _nudged([float(b2) ** float(t) for t in steps], pow_ulps[1])
+    with np.errstate(all='ignore'):
+        bc1 = (1.0 - x1).astype(dtype)[:, None]
+        bc2_sqrt = np.sqrt(1.0 - x2).astype(dtype)[:, None]
+        step_size = T(lr) / bc1
+        ge = g if wd == 0.0 else g + T(wd) * p
+        mn = m + T(1.0 - b1) * (ge - m)
+        vn = v * T(b2) + (T(1.0 - b2) * ge) * ge
+        denom = np.sqrt(vn) / bc2_sqrt + T(eps)
+        pn = p - step_size * (mn / denom)
+        tn = None if target is None else target + T(tau) * (pn - target)
+    for a in (mn, vn, pn) + (() if tn is None else (tn,)):
+        assert a.dtype == np.dtype(dtype)
+    if active is not None:
+        on = (np.asarray(active) != 0)[:, None]
+        pn, mn, vn = np.where(on, pn, p), np.where(on, mn, m), np.where(on, vn, v)
+        tn = None if tn is None else np.where(on, tn, target)
+    return pn, mn, vn, tn
+
+
 def blend(t, p, tau):
     """The target network moved towards the online one: t + tau (p - t)."""
     return {k: t[k] + tau * (p[k] - t[k]) for k in t}

@@ -76,6 +76,53 @@ def test_reference_matches_torch_autograd_and_adam(D, O):
             assert float(st['step']) == net['steps'] == 6.0 + it
 
 
+def test_adam_in_kernel_order_matches_torch_adam():
+    """mlp_common.adam_kernel (k_adam's operations in k_adam's order) in float64 against
+    torch.optim.Adam on the CPU: 5 steps with weight decay from non-zero moments and step counts
+    0 and 7, three instances with one sitting out — parameters and both moments to rtol 1e-12,
+    the blended target against torch.lerp; in float32 the same function stays in float32."""
+    import torch
+    rng = np.random.default_rng(17)
+    n, per = 3, 41
+    hyper = dict(lr=3e-3, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=1e-3, tau=0.05)
+    p = rng.standard_normal((n, per))
+    m, v = 0.01 * rng.standard_normal((n, per)), 1e-4 * rng.random((n, per))
+    m[0], v[0] = 0.0, 0.0
+    t = rng.standard_normal((n, per))
+    steps = np.array([0.0, 7.0, 3.0])
+    active = np.array([1, 1, 0], dtype=np.uint8)
+    tp = [torch.tensor(p[j], requires_grad=True) for j in range(n)]
+    tt = [torch.tensor(t[j]) for j in range(n)]
+    opts = []
+    for j in range(n):
+        opt = torch.optim.Adam([tp[j]], lr=hyper['lr'], eps=hyper['eps'],
+                               betas=(hyper['beta1'], hyper['beta2']),
+                               weight_decay=hyper['weight_decay'])
+        opt.state[tp[j]] = {'step': torch.tensor(steps[j]), 'exp_avg': torch.tensor(m[j]),
+                            'exp_avg_sq': torch.tensor(v[j])}
+        opts.append(opt)
+    for it in range(5):
+        g = rng.standard_normal((n, per)) * 10.0 ** rng.integers(-6, 1, size=(n, per))
+        steps = steps + active
+        p, m, v, t = mc.adam_kernel(p, g, m, v, steps, hyper, np.float64, target=t, active=active)
+        for j in range(n):
+            if not active[j]:
+                continue
+            tp[j].grad = torch.tensor(g[j])
+            opts[j].step()
+            with torch.no_grad():
+                tt[j] = torch.lerp(tt[j], tp[j], hyper['tau'])
+        for j in range(n):
+            st = opts[j].state[tp[j]]
+            for name, got, want in (('p', p[j], tp[j].detach()), ('m', m[j], st['exp_avg']),
+                                    ('v', v[j], st['exp_avg_sq']), ('t', t[j], tt[j])):
+                assert np.allclose(got, want.numpy(), rtol=1e-12, atol=0.0), (it, j, name)
+            assert float(st['step']) == steps[j]
+    f32 = [a.astype(np.float32) for a in (p, g, m, v, t)]
+    out = mc.adam_kernel(f32[0], f32[1], f32[2], f32[3], steps, hyper, np.float32, target=f32[4])
+    assert all(a.dtype == np.float32 for a in out)
+
+
 def test_reference_empty_mask_and_no_training():
     """Nothing marked: the count clamps to 1 and the gradient is exactly zero, as torch's; a
     network that does not train keeps everything but its blended target."""
