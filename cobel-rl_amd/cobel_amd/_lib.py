@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get('COBEL_LIB') or os.path.join(os.path.dirname(_HERE), '
 OK, E_ARG, E_RANGE, E_HIP, E_UNSUPPORTED = 0, -1, -2, -3, -4
 STREAM_ENV, STREAM_POLICY, STREAM_MEMORY, STREAM_POLICY_TEST, STREAM_AGENT = 0, 1, 2, 3, 4
 STREAM_PMA_MEMORY, STREAM_PMA_POLICY = 5, 6
+STREAM_ADQN_MEMORY = 7
 SUB_DOUBLE = 1
 AGENT_Q, AGENT_DYNAQ = 0, 1
 F_LEARN, F_NO_REPLAY, F_EPISODIC, F_MASK_ACTIONS, F_TEST_STREAM, F_FORCE_WAVE = 1, 2, 4, 8, 16, 32
@@ -377,6 +378,38 @@ class ANetRun(C.Structure):
     ]
 
 
+ADQN_RPE = 1
+
+
+class ADQNMem(C.Structure):
+    """``cobel_adqn_mem_t``."""
+    _fields_ = [
+        ('states', C.c_void_p), ('reinforcements', C.c_void_p), ('errors', C.c_void_p),
+        ('priorities', C.c_void_p), ('count', C.c_void_p), ('draw_ctr', C.c_void_p),
+        ('instance_ids', C.c_void_p), ('scratch', C.c_void_p),
+        ('n', C.c_int32), ('dim', C.c_int32), ('cap', C.c_int32),
+        ('count_min', C.c_int32), ('count_max', C.c_int32),
+        ('instance_base', C.c_uint32), ('flags', C.c_uint32), ('reserved_', C.c_uint32),
+        ('decay', C.c_double), ('seed', C.c_uint64),
+    ]
+
+
+class ADQNStep(C.Structure):
+    """``cobel_adqn_step_t``."""
+    _fields_ = [
+        ('value', C.c_void_p), ('in_index', C.c_void_p), ('targets', C.c_void_p),
+        ('idx', C.c_void_p), ('ep_index', C.c_void_p), ('active', C.c_void_p),
+        ('alive', C.c_void_p), ('done', C.c_void_p), ('mid', C.c_void_p), ('trew', C.c_void_p),
+        ('trial_reward', C.c_void_p), ('trial_steps', C.c_void_p), ('step_rec', C.c_void_p),
+        ('trace', C.c_void_p), ('idx_trace', C.c_void_p), ('trace_len', C.c_void_p),
+        ('steps_done', C.c_void_p),
+        ('n', C.c_int32), ('batch', C.c_int32), ('is_float64', C.c_int32),
+        ('trial_cap', C.c_int32), ('trace_cap', C.c_int32), ('flags', C.c_uint32),
+        ('trial_first', C.c_int32), ('trials', C.c_int32), ('steps_per_trial', C.c_int32),
+        ('reserved_', C.c_int32),
+    ]
+
+
 class SRRun(C.Structure):
     """``cobel_sr_run_t``."""
     _fields_ = [
@@ -478,6 +511,10 @@ _SIGNATURES = {
     'cobel_anet_run': (C.c_int, [C.POINTER(Seq), C.POINTER(ANetRun), _P]),
     'cobel_anet_predict': (C.c_int, [C.POINTER(ANetRun), C.c_int32, _P, C.c_int32, _P, _P]),
     'cobel_anet_update': (C.c_int, [C.POINTER(ANetRun), C.c_int32, _P, _P, _P, _P]),
+    'cobel_adqn_plan': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64 * 4)]),
+    'cobel_adqn_store': (C.c_int, [C.POINTER(ADQNMem), C.c_int32, _P, _P, _P, _P]),
+    'cobel_adqn_sample': (C.c_int, [C.POINTER(ADQNMem), C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    'cobel_adqn_step': (C.c_int, [C.POINTER(Seq), C.POINTER(ADQNMem), C.POINTER(ADQNStep), _P]),
     'cobel_adam_step': (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int32,
                                   C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _P,
                                   C.c_double, _P]),

@@ -1,4 +1,5 @@
 from .agent import Agent, Callbacks  # noqa: F401
+from .adqn import ADQN  # noqa: F401
 from .anet import AssociativeNetwork  # noqa: F401
 from .dqn import DQN  # noqa: F401
 from .dyna_dqn import DynaDQN  # noqa: F401

@@ -1396,6 +1396,102 @@ COBEL_API int cobel_anet_predict(const cobel_anet_run_t* run, int32_t dim, const
 COBEL_API int cobel_anet_update(const cobel_anet_run_t* run, int32_t dim, const double* state,
                                 const int32_t* action, const double* reward, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * ADQN (agent/adqn.py:18-279) and ADQNMemory (memory/adqn.py:29-198) on a Sequence: a network
+ * predicts one value per observation, the value IS the action, every experience is kept, and every
+ * step replays a batch drawn with recency-decayed prediction-error priorities.
+ *
+ * The memory of instance j is rows [j][0 .. count[j]) of caller-owned arrays of capacity `cap`; it
+ * only ever grows.  One wavefront serves one instance.  The cumulative distribution of a draw is
+ * formed in ONE fixed order: the count[j] entries are cut into 64
+ * consecutive chunks of c = ceil(count / 64) entries, lane l holding [l c, min((l + 1) c, count));
+ *   prob_sum = balanced tree (adjacent lanes first) over the lanes' sequential chunk sums of the
+ *              priorities;
+ *   p_i      = priority_i / prob_sum, or 1.0 / count each where prob_sum == 0;
+ *   cdf_i    = (sum of the chunk totals of p of the lanes before, as a Hillis-Steele inclusive scan
+ *               over the lanes hands it to the next lane) + (the sequential sum of p inside the
+ *               chunk up to and including i);
+ *   index    = min(#{i : cdf_i / cdf_last <= u}, count - 1)
+ * for each of the `batch` draws u, draw b being the double at (counter draw_ctr[j], sub b) of
+ * COBEL_STREAM_ADQN_MEMORY: what Generator.choice(n, p=probs, size=batch) consumes as ONE call.
+ * Non-finite rewards or values are outside the contract: NumPy's choice raises on NaN
+ * probabilities, these kernels do not look. */
+#define COBEL_STREAM_ADQN_MEMORY 7u /* c = sample_batch calls, sub = position in the batch
+                                       (memory/adqn.py:160)                                    */
+#define COBEL_ADQN_RPE 1u           /* ADQNMemory.rpe: priority |error| instead of 1            */
+
+typedef struct {
+  double* states;             /* [n][cap][dim] ADQNMemory.states                                */
+  double* reinforcements;     /* [n][cap]                                                       */
+  double* errors;             /* [n][cap] action - reward                                       */
+  double* priorities;         /* [n][cap]                                                       */
+  int32_t* count;             /* [n] experiences held, <= cap                                   */
+  uint32_t* draw_ctr;         /* [n] sample_batch calls so far (store: not read)                */
+  const uint32_t* instance_ids; /* [n] stream instance numbers, or NULL: instance_base + i      */
+  double* scratch;            /* [n][cap] the cdf of a draw (cobel_adqn_plan; store: not read)  */
+  int32_t n, dim, cap;
+  int32_t count_min, count_max; /* the host's bounds on count[]: they decide the refusals       */
+  uint32_t instance_base, flags;  /* COBEL_ADQN_RPE                                             */
+  uint32_t reserved_;
+  double decay;               /* ADQNMemory.decay, 0 .. 1                                       */
+  uint64_t seed;
+} cobel_adqn_mem_t;
+
+typedef struct {
+  const void* value;          /* [n] the network's value of the current observation = the action,
+                                 in the network's dtype (widened exactly, as float() does)      */
+  int32_t* in_index;          /* [n][batch] out: row j cap + index of states viewed [n cap][dim] */
+  void* targets;              /* [n][batch] out: reinforcements[index], network dtype           */
+  int32_t* idx;               /* [n][batch] out: the drawn indices, or NULL                     */
+  int32_t* ep_index;          /* [n] out: the observation-table row the instance sees next      */
+  uint8_t* active;            /* [n] out: 1 = the instance stored (and drew) in this step       */
+  uint8_t* alive;             /* [n] out: 1 = the instance has steps of this session left       */
+  int32_t* done;              /* [n] trials finished in this session (the caller zeroes it)     */
+  int32_t* mid;               /* [n] 1: a trial is under way                                    */
+  double* trew;               /* [n] its reward so far                                          */
+  double* trial_reward;       /* [n][trial_cap] logs['trial_reward'] of every trial, or NULL    */
+  int32_t* trial_steps;       /* [n][trial_cap] logs['steps'] (index of its last step), or NULL */
+  double* step_rec;           /* [n][4] value, reward, end_trial, terminal of this step, or NULL */
+  double* trace;              /* [n][trace_cap][3] value, reward, end of every step, or NULL    */
+  int32_t* idx_trace;         /* [n][trace_cap][batch] the drawn indices of every step, or NULL */
+  int32_t* trace_len;         /* [n] rows of trace written so far (NULL iff trace is)           */
+  unsigned long long* steps_done; /* env steps executed, added to; or NULL                      */
+  int32_t n, batch, is_float64, trial_cap, trace_cap;
+  uint32_t flags;             /* COBEL_F_LEARN: train (store and draw); 0: test                 */
+  int32_t trial_first;        /* row of the per-trial traces the session's first trial takes    */
+  int32_t trials;             /* trials of the session                                          */
+  int32_t steps_per_trial;    /* the cap of train(interface, trials, steps)                     */
+  int32_t reserved_;
+} cobel_adqn_step_t;
+
+/* Launch shape and scratch of the three entry points below for n instances of capacity cap: out =
+ * {instances per workgroup, workgroups, bytes of cobel_adqn_mem_t.scratch, lanes per instance}.
+ * COBEL_E_UNSUPPORTED beyond COBEL_RW_MAX_DIM components, COBEL_E_RANGE unless n cap < 2^31.  (No
+ * line of the reference corresponds: the launch shape is this library's.) */
+COBEL_API int cobel_adqn_plan(int32_t dim, int32_t n, int32_t cap, int64_t out[4]);
+/* ADQNMemory.store (memory/adqn.py:119-138), k experiences per instance one after the other: states
+ * [dev] [n][k][dim], actions [dev] [n][k], rewards [dev] [n][k].  Per experience: append state,
+ * reward and action - reward; multiply every stored priority by decay (one rounded multiplication
+ * per entry per store, the reference's repeated *=); append |error| ** int(rpe).  COBEL_E_RANGE if
+ * count_max + k > cap; the kernel itself never writes past cap either. */
+COBEL_API int cobel_adqn_store(const cobel_adqn_mem_t* mem, int32_t k, const double* states,
+                               const double* actions, const double* rewards, void* stream);
+/* ADQNMemory.sample_batch (memory/adqn.py:140-164): idx [dev] [n][batch] (or NULL), in_index [dev]
+ * [n][batch] and targets [dev] [n][batch] (float64, or float32 with is_float64 == 0) as in
+ * cobel_adqn_step_t; draw_ctr[j] += 1.  batch >= 1.  COBEL_E_RANGE if count_min == 0: an empty
+ * memory has nothing to draw, the reference's choice raises. */
+COBEL_API int cobel_adqn_sample(const cobel_adqn_mem_t* mem, int32_t batch, int32_t is_float64,
+                                int32_t* idx, int32_t* in_index, void* targets, void* stream);
+/* One lockstep step of ADQN.train / test (agent/adqn.py:128-156, :187-212) without the network: in
+ * every instance with trials of the session left, Sequence.reset where a trial begins, Sequence.step
+ * (interface/sequence.py:129-186; rewards one float per step, or array rewards under overwrite),
+ * under COBEL_F_LEARN memory.store of (observation, value, reward) and the draw of
+ * memory.sample_batch, then the trial bookkeeping and ep_index.  The caller then hands in_index,
+ * targets, active and ep_index to cobel_mlp_fit nb_replays times (agent/adqn.py:234-236); its
+ * ep_out is the next step's value.  COBEL_E_RANGE if a store could pass cap (count_max + 1 > cap). */
+COBEL_API int cobel_adqn_step(const cobel_seq_t* seq, const cobel_adqn_mem_t* mem,
+                              const cobel_adqn_step_t* run, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
