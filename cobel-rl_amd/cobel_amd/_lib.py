@@ -410,6 +410,24 @@ class ADQNStep(C.Structure):
     ]
 
 
+C2D_MAX_EDGES, C2D_MAX_REWARDS = 1024, 32
+C2D_STEP, C2D_WHEEL = 0, 1
+
+
+class C2D(C.Structure):
+    """``cobel_c2d_t``."""
+    _fields_ = [
+        ('edges', C.c_void_p), ('spawn_edges', C.c_void_p), ('rewards', C.c_void_p),
+        ('state', C.c_void_p), ('env_ctr', C.c_void_p),
+        ('box', C.c_double * 4), ('fallback', C.c_double * 2),
+        ('step_size', C.c_double), ('body_radius', C.c_double), ('wheel_distance', C.c_double),
+        ('buffer', C.c_double), ('seed', C.c_uint64),
+        ('n', C.c_int32), ('n_edges', C.c_int32), ('n_spawn_edges', C.c_int32),
+        ('n_rewards', C.c_int32), ('robot_type', C.c_int32), ('punish_wall', C.c_int32),
+        ('lanes_per_instance', C.c_int32), ('instance_base', C.c_uint32),
+    ]
+
+
 class SRRun(C.Structure):
     """``cobel_sr_run_t``."""
     _fields_ = [
@@ -526,6 +544,9 @@ _SIGNATURES['cobel_mlp_query'] = (C.c_int, [C.c_int32] * 6 + [C.POINTER(C.c_int3
 _SIGNATURES['cobel_mlp_forward'] = (C.c_int, [C.POINTER(MLPForward), _P])
 _SIGNATURES['cobel_mlp_fit'] = (C.c_int, [C.POINTER(MLPFit), _P])
 _SIGNATURES['cobel_dsr_targets'] = (C.c_int, [C.POINTER(DSRTargets), _P])
+_SIGNATURES['cobel_c2d_plan'] = (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32 * 4)])
+_SIGNATURES['cobel_c2d_step'] = (C.c_int, [C.POINTER(C2D), _P, _P, _P, _P, _P])
+_SIGNATURES['cobel_c2d_reset'] = (C.c_int, [C.POINTER(C2D), _P, _P, _P])
 EXPORTS = tuple(sorted(_SIGNATURES))
 
 _lib = None

@@ -1,3 +1,4 @@
+from .continuous import Continuous2D  # noqa: F401
 from .gridworld import Gridworld, WorldHandle  # noqa: F401
 from .interface import Interface  # noqa: F401
 from .sequence import Sequence  # noqa: F401

@@ -1492,6 +1492,75 @@ COBEL_API int cobel_adqn_sample(const cobel_adqn_mem_t* mem, int32_t batch, int3
 COBEL_API int cobel_adqn_step(const cobel_seq_t* seq, const cobel_adqn_mem_t* mem,
                               const cobel_adqn_step_t* run, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The continuous 2D arena (interface/continuous.py:21-438): a "step" robot that moves in the four
+ * cardinal directions or a differential-wheel robot, inside one exterior ring with hole rings
+ * (room, obstacles).  Everything is float64, every operation rounded by itself.
+ *
+ * The arena is a table of directed edges a -> b with the interior to the left (exterior
+ * counter-clockwise, holes clockwise), eight columns of n_edges doubles computed on the host:
+ * ax, ay, bx, by, ex = bx - ax, ey = by - ay, nx = -ey / L, ny = ex / L (L = sqrt(ex ex + ey ey)).
+ * With m = |buffer|:
+ *   inside(p)  even-odd rule: an edge toggles when (ay > py) != (by > py) and
+ *              px < ax + (py - ay) / (by - ay) * ex
+ *   clear(p)   inside(p), and every edge is at least m / 2 away (squared distance to the point at
+ *              s = ((px - ax) ex + (py - ay) ey) / (ex ex + ey ey) clamped to [0, 1])
+ *   move(p, target), d = target - p: among the edges with den = dx nx + dy ny < 0,
+ *              t = ((px - ax) nx + (py - ay) ny) / (-den) in [0, 1] and the hit point h = p + t d at
+ *              u = ((hx - ax) ex + (hy - ay) ey) / (ex ex + ey ey) in [-1e-9, 1 + 1e-9], take the
+ *              least t (the lowest edge on ties): the robot ends at h + m n of that edge, at the
+ *              target itself (bit for bit) with no hit, and stays at p where that point is not
+ *              clear.  wall_hit: the end differs from the target.
+ * This replaces shapely's polygon / line-string intersection and buffered-polygon projection
+ * (continuous.py:311-329): the robot lands m inside the wall instead of on it.
+ *
+ * An instance takes G = 1, 4, 16 or 64 lanes, which split the edges; the results are the same bits
+ * for every G. */
+#define COBEL_C2D_MAX_EDGES 1024
+#define COBEL_C2D_MAX_REWARDS 32
+#define COBEL_C2D_STEP 0   /* 4 actions: -x, +y, +x, -y by step_size (continuous.py:211-219)   */
+#define COBEL_C2D_WHEEL 1  /* 3 actions: turn on either wheel, straight (continuous.py:220-251) */
+
+typedef struct {
+  const double* edges;        /* [dev] [8][n_edges] the arena                                    */
+  const double* spawn_edges;  /* [dev] [8][n_spawn_edges] the rings of the spawn area            */
+  const double* rewards;      /* [dev] [n_rewards][3] x, y, magnitude; NULL with none            */
+  double* state;              /* [dev] [n][3] x, y, orientation                                  */
+  uint32_t* env_ctr;          /* [dev] [n] next index on COBEL_STREAM_ENV (kept even)            */
+  double box[4];              /* lo_x, lo_y, hi_x, hi_y of the candidates of a reset             */
+  double fallback[2];         /* the start where 1 024 candidates were all refused               */
+  double step_size, body_radius, wheel_distance, buffer;
+  uint64_t seed;
+  int32_t n, n_edges, n_spawn_edges, n_rewards;
+  int32_t robot_type;         /* COBEL_C2D_STEP / COBEL_C2D_WHEEL                                */
+  int32_t punish_wall;        /* reward -10 for a step that hit a wall                           */
+  int32_t lanes_per_instance; /* 0: the planner's choice; 1, 4, 16, 64                           */
+  uint32_t instance_base;
+} cobel_c2d_t;
+
+/* Launch shape for n instances in an arena of n_edges edges: out = {lanes per instance, lanes per
+ * workgroup, bytes of LDS per workgroup, workgroups}.  The largest G of 1, 4, 16, 64 within the
+ * lane budget (n G <= 262 144 for G = 4 and 16, <= 65 536 for G = 64; docs/MEASUREMENTS.md §19)
+ * and with G <= the next power of two >= n_edges.  COBEL_E_RANGE outside 1 .. COBEL_C2D_MAX_EDGES
+ * edges. */
+COBEL_API int cobel_c2d_plan(int32_t n, int32_t n_edges, int32_t out[4]);
+/* Continuous2D.step (continuous.py:185-266, clip_movement :295-329) in every instance: action
+ * [dev] [n] in; the state is updated in place; reward [dev] [n], done [dev] [n] (end_trial) and
+ * wall [dev] [n] (wall_hit) out.  The first reward row within 2 body_radius pays and ends the
+ * trial; else -10 for a wall hit under punish_wall.  An action the robot does not have leaves the
+ * instance where it is: reward 0, not done, no wall hit.  COBEL_E_ARG / COBEL_E_RANGE for a
+ * malformed arena, before any HIP call. */
+COBEL_API int cobel_c2d_step(const cobel_c2d_t* c2d, const uint8_t* action, double* reward,
+                             uint8_t* done, uint8_t* wall, void* stream);
+/* Continuous2D.reset (continuous.py:268-293) in every instance whose mask byte is set (mask NULL:
+ * all): candidate k = box.lo + (box.hi - box.lo) * (draws c + 2k, c + 2k + 1 of COBEL_STREAM_ENV,
+ * c = env_ctr[i]); the first of k = 0 .. 1023 inside the spawn rings and clear in the arena is the
+ * start, the orientation 2 pi times draw c + 2k + 2 (0 for the step robot, the draw is consumed),
+ * env_ctr += 2k + 4.  Where none is accepted: the fallback point, the draw c + 2048,
+ * env_ctr += 2052 and *fallbacks += 1.  This bounds the reference's `while` loop (:282-283). */
+COBEL_API int cobel_c2d_reset(const cobel_c2d_t* c2d, const uint8_t* mask, int32_t* fallbacks,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif
