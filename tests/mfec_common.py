@@ -138,6 +138,7 @@ class RefQEC:
         self.R, self.same = pair_tables(F) if tables is None else tables
         self.buffers = tuple(RefActionBuffer(capacity) for _ in range(nb_actions))
         self.k = k
+        self.evicted = 0       # entries of a full buffer replaced by a newer one
 
     def find_state(self, b, s):
         if not b.ids:
@@ -168,6 +169,7 @@ class RefQEC:
             m = int(np.argmin(b.times))
             if time > b.times[m]:
                 b.ids[m], b.values[m], b.times[m] = s, value, time
+                self.evicted += 1
 
 
 class RefMFEC:

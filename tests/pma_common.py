@@ -21,12 +21,36 @@ def memory_rngs(seed, inst):
             TapeRNG(seed, inst, STREAM_PMA_POLICY))
 
 
+def gauss_jordan(T, gamma):
+    """k_pma_update_sr's operations element by element: pivots ascending, no pivoting, the pivot
+    row scaled by 1 / pivot, every other element M - col[r] * row[c] (0 - ... in column k)."""
+    S = T.shape[0]
+    M = np.eye(S) - gamma * T
+    for k in range(S):
+        inv = 1.0 / M[k, k]
+        col = M[:, k].copy()
+        row = M[k, :].copy()
+        row[k] = 1.0
+        row = row * inv
+        M[:, k] = 0.0
+        M = M - col[:, None] * row[None, :]
+        M[k, :] = row
+    return M
+
+
 class RefPMAMemory:
     """memory/pma.py:20-496."""
 
     def __init__(self, sas, policy, learning_rate=0.9, learning_rate_q=0.9, gamma=0.9, gamma_q=0.9,
-                 rng=None):
+                 rng=None, sr_by_elimination=False):
         self.rng, self.policy = rng, policy
+        # update_sr by ``gauss_jordan``, the device kernels' operations, not by LAPACK (the
+        # constructor's SR below is numpy.linalg.inv on both sides either way)
+        self.sr_by_elimination = sr_by_elimination
+        # what the replays held, for the tests that ask what a sweep contains: per replay() call
+        # whether an extended (n-step, n > 1) sequence was chosen and whether the largest utility
+        # was tied so that the draw decided
+        self.seen = {'replays': 0, 'extended': 0, 'tied': 0}
         self.learning_rate, self.learning_rate_q, self.learning_rate_T = learning_rate, learning_rate_q, 0.9
         self.gamma, self.gamma_q = gamma, gamma_q
         self.nb_states, self.nb_actions = S, A = sas.shape[0], sas.shape[1]
@@ -46,7 +70,10 @@ class RefPMAMemory:
                                                                      self.nb_actions)
 
     def update_sr(self):
-        self.SR = np.linalg.inv(np.eye(self.nb_states) - self.gamma * self.T)
+        if self.sr_by_elimination:
+            self.SR = gauss_jordan(self.T, self.gamma)
+        else:
+            self.SR = np.linalg.inv(np.eye(self.nb_states) - self.gamma * self.T)
 
     def store(self, e):
         s, a = e['state'], e['action']
@@ -132,6 +159,7 @@ class RefPMAMemory:
     def replay(self, q_function, action_mask, replay_length, current_state, force_first=None):
         S, A = self.nb_states, self.nb_actions
         done, Q, last_seq = [], np.copy(q_function), 0
+        extended = tied = False
         for upd in range(replay_length):
             ext, seq = -1, None
             if done:
@@ -154,13 +182,18 @@ class RefPMAMemory:
                 utility *= self.update_mask
             ties = utility == np.amax(utility)
             best = self.rng.choice(np.arange(S * A), p=ties / np.sum(ties))
+            tied |= int(np.sum(ties)) > 1 and not (not done and force_first is not None)
             if not done and force_first is not None:
                 best = force_first + self.rng.integers(A) * S
             chosen = seq if (seq and best == ext) else [self._step(best)]
+            extended |= len(chosen) > 1
             Q = self.update_q(Q, chosen)
             done += [chosen[-1]]
             if ext != best:
                 last_seq = upd
+        self.seen['replays'] += 1
+        self.seen['extended'] += int(extended)
+        self.seen['tied'] += int(tied)
         return done, Q
 
 
@@ -217,13 +250,17 @@ def rows_of(exps):
     return np.array([[float(e[k]) for k in KEYS] for e in exps], dtype=np.float64).reshape(-1, 5)
 
 
-def make_ref_agent(tabs, sas, seed, inst, gamma_q=0.99, epsilon=0.1):
-    """The restatement's env, agent and memory of instance ``inst`` on the project's streams."""
+def make_ref_agent(tabs, sas, seed, inst, gamma_q=0.99, epsilon=0.1, shared_policy=False,
+                   sr_by_elimination=False):
+    """The restatement's env, agent and memory of instance ``inst`` on the project's streams.
+    ``shared_policy``: the memory's policy object is the agent's (one stream for both)."""
     env = RefGridworld(tabs, TapeRNG(seed, inst, STREAM_ENV))
     rm, rp = memory_rngs(seed, inst)
-    mem = RefPMAMemory(sas, RefEpsilonGreedy(epsilon, rp), gamma_q=gamma_q, rng=rm)
+    pol = RefEpsilonGreedy(epsilon, TapeRNG(seed, inst, STREAM_POLICY))
+    mem = RefPMAMemory(sas, pol if shared_policy else RefEpsilonGreedy(epsilon, rp), gamma_q=gamma_q,
+                       rng=rm, sr_by_elimination=sr_by_elimination)
     S, A = sas.shape[0], sas.shape[1]
-    agent = RefPMA(S, A, RefEpsilonGreedy(epsilon, TapeRNG(seed, inst, STREAM_POLICY)), mem)
+    agent = RefPMA(S, A, pol, mem)
     return env, agent, mem
 
 
@@ -269,13 +306,19 @@ def seeded_world(height, width, seed):
 WORLDS = {'demo_5x5': demo_world, 'small_3x4': small_world}
 
 
+def sas_of(nxt):
+    """Dense ``sas[S, A, S]`` of a deterministic successor table ``next[S, A]``, any action count."""
+    nxt = np.asarray(nxt).astype(np.int64)
+    S, A = nxt.shape
+    sas = np.zeros((S, A, S))
+    sas[np.arange(S)[:, None], np.arange(A)[None, :], nxt] = 1.0
+    return sas
+
+
 def tables_of(world):
     """(compact tables for RefGridworld, dense sas) of a World."""
     tabs = world.compact()
-    S = int(world['states'])
-    sas = np.zeros((S, 4, S))
-    sas[np.arange(S)[:, None], np.arange(4)[None, :], tabs['next'].astype(np.int64)] = 1.0
-    return tabs, sas
+    return tabs, sas_of(tabs['next'])
 
 
 def walk_stores(tabs, n, seed, repeat=None):
@@ -330,7 +373,7 @@ def masked_actions(tabs):
 
 def script_for(stores, start, lengths=(1, 2, 7, 32), none_state=True):
     """The calls of one case: ['store', s, a, r, ns, t], ['set', name, value], ['mask'] (the
-    update mask), ['replay', length, state or None, force_first or None, masked]."""
+    update mask), ['update_sr'], ['replay', length, state or None, force_first or None, masked]."""
     half = len(stores) // 2
     ops = [['store'] + r for r in stores[:half]]
     ops += [['replay', n, start, None, False] for n in lengths]
@@ -374,6 +417,8 @@ class ScriptMemory:
                            'next_state': int(ns), 'terminal': int(t)})
             elif op[0] == 'mask':
                 mem.compute_update_mask()
+            elif op[0] == 'update_sr':
+                mem.update_sr()
             elif op[0] == 'replay':
                 _, length, state, first, masked = op
                 if self.sr is not None:

@@ -4,7 +4,12 @@ lists), hyper-parameters, batch sizes 0..130, 1..257 instances, masks, episodic 
 sessions, forced general kernel / row-streaming SR kernel — every table, counter and per-trial
 monitor of DynaQ / QAgent / SR bit for bit against the C oracle.  The sweep found, in its first
 300 cases: QAgent sessions with batch_size 0 did not log their experiences (the reference does,
-q.py:213), and SR's transition table was not initialised for worlds of fewer than four states."""
+q.py:213), and SR's transition table was not initialised for worlds of fewer than four states.
+Below it: slices of the sweeps for SFMA, topologies, stochastic worlds, the network agents and their
+kernels.  The sweeps for PMA, AssociativeNetwork, Continuous2D and MFEC have their slices in
+tests/test_gpu_fuzz_agents.py (what those contain: tests/test_host_fuzz_agents.py); several hundred
+seeds of each beyond the slice found no mismatch (docs/MEASUREMENTS.md section 20), so there is no
+regression case of theirs next to test_sweep_regressions."""
 import os
 import sys
 

@@ -10,6 +10,7 @@ import pytest
 
 import pma_common as pc
 import pma_wide_common as pw
+from pma_common import gauss_jordan
 from oracle.ref_loop import RefEpsilonGreedy
 
 pytestmark = pytest.mark.gpu
@@ -141,23 +142,6 @@ def filled(world, n, wide, gamma=0.9, stores=40):
         mem.store({'state': [s, rows[0][0]][:n], 'action': [a, rows[0][1]][:n], 'reward': r,
                    'next_state': [ns, rows[0][3]][:n], 'terminal': t})
     return mem
-
-
-def gauss_jordan(T, gamma):
-    """k_pma_update_sr's operations element by element: pivots ascending, no pivoting, the pivot
-    row scaled by 1 / pivot, every other element M - col[r] * row[c] (0 - ... in column k)."""
-    S = T.shape[0]
-    M = np.eye(S) - gamma * T
-    for k in range(S):
-        inv = 1.0 / M[k, k]
-        col = M[:, k].copy()
-        row = M[k, :].copy()
-        row[k] = 1.0
-        row = row * inv
-        M[:, k] = 0.0
-        M = M - col[:, None] * row[None, :]
-        M[k, :] = row
-    return M
 
 
 @pytest.mark.parametrize('shape', [(5, 5), (8, 16)])
