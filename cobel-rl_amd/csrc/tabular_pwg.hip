@@ -3,20 +3,31 @@
 // would hold).
 //
 // k_tab_wpi keeps an instance's Q table (16 B per state) in LDS, so at 32 x 32 states nine
-// instances fit on a CU (17 408 B each).  The step is a chain of dependent work, not a stream:
-// measured on trained agents, the same kernel on 24 x 24 mazes padded to 9 / 10 / 11 / 12 / 14 / 16
-// instances per CU takes 16.75 / 15.45 / 14.37 / 13.43 / 12.05 / 11.03 ms per launch
-// (scripts/experiments/exp_occ_trained.py) — every further resident wave is throughput.  LDS is
-// handed out in blocks of 1 280 B, so nine workgroups of k_tab_wpi fill it; ONE workgroup that owns
-// a CU for the whole launch takes all of it, and ten tables of 16 KiB fit.  That is the production
-// form: `nl` = ten waves at 32 x 32 (as many as tables fit, sixteen at most), each keeping its
-// instance's Q table in LDS exactly as k_tab_wpi does.  Waves that work on the caller's Q table
-// where it lies, in global memory (L2 resident while the instance is in flight: 16 KiB) — `ng` of
-// them — exist only for COBEL_F_PWG_GLOBAL and forced mixes (tests, experiments): next to ten LDS
-// waves they cost more than they add (cobel_tab_pwg_plan).  All waves take instances from one
-// atomic counter until it runs out, so the two kinds may run at different speeds.
+// instances fit on a CU (17 408 B each: LDS is handed out in blocks of 1 280 B).  The step is a
+// chain of dependent work, not a stream: measured on trained agents, the same kernel on 24 x 24
+// mazes padded to 9 / 10 / 11 / 12 / 14 / 16 instances per CU takes 16.75 / 15.45 / 14.37 / 13.43 /
+// 12.05 / 11.03 ms per launch (scripts/experiments/exp_occ_trained.py) — every further resident
+// wave is throughput.  ONE workgroup that owns a CU for the whole launch takes all of its LDS, and
+// ten tables of 16 KiB are exactly the 160 KiB.  That is the production form: `nl` = ten waves at
+// 32 x 32 (as many as tables fit, sixteen at most), no workgroup barrier, each wave keeping its
+// instance's Q table in LDS exactly as k_tab_wpi does and taking instances (tickets) from per-XCD
+// queues until they run out (k_tab_pwg below).
 //
-// Q in global memory (QG) without a memory round trip per planning round:
+// The step loop of an LDS wave (pwg_instance):
+//   * which lanes of a planning batch must wait for an earlier lane is found in the table itself
+//     (tags raised with ds_max_u32, run_batch_lds) — nothing lies in LDS beside the tables;
+//   * what the next step needs from memory (the successors' world records, the next state's digest
+//     entries, the next batch's pairs) is requested a step ahead, unconditionally;
+//   * one Philox evaluation serves four steps, and the loop takes its steps in groups of four
+//     whose position in the block — which lane and word hold the policy's draw, which word the
+//     planning lanes' pair, where the next evaluation falls — is fixed at compile time (env_step,
+//     PH = 0 .. 3); single generic steps (PH = -1) fill in wherever a group does not fit.
+//
+// Waves that work on the caller's Q table where it lies, in global memory (QG; `ng` of them; L2
+// resident while the instance is in flight: 16 KiB), exist only for COBEL_F_PWG_GLOBAL and forced
+// mixes (tests, experiments): next to ten LDS waves they cost more than they add
+// (cobel_tab_pwg_plan).  They take the generic step only, without a memory round trip per planning
+// round:
 //   * everything a step reads from Q is requested at the top of the step, after the previous
 //     step's stores have been acknowledged: Q[s], the rows of the four possible successors, and for
 //     the planning lanes the row Q[ns_j] and the cell Q[s_j][a_j] of the pair each will replay
@@ -25,9 +36,11 @@
 //   * the speculative rounds of k_tab_wpi (agent/dyna_q.py:327-330 applies the B updates one after
 //     another) run on those registers: lanes whose inputs were changed by an earlier lane of the
 //     round take the new values from the writers' registers (ds_bpermute over their exact conflict
-//     set) instead of re-reading the table.  Only changed cells are stored.
-// Same draws, same arithmetic, same order of effects as k_tab_wpi: identical tables, digests,
-// counters and monitors (tests/test_gpu_pwg.py compares the two kernels and the oracle).
+//     set, two 64-bucket tables of lane masks per wave) instead of re-reading the table.  Only
+//     changed cells are stored.
+// Same draws, same arithmetic, same order of effects as k_tab_wpi, whichever kind of wave and
+// whichever form of the step: identical tables, digests, counters and monitors
+// (tests/test_gpu_pwg.py and tests/test_gpu_pwg_phases.py compare the kernels and the oracle).
 //
 // Reference behaviour restated: agent/dyna_q.py:164-215 (train loop), :290-299 (TD), :327-330
 // (replay); memory/dyna_q.py:92-96 (store), :137-155 (retrieve_batch).
@@ -48,6 +61,11 @@ constexpr uint32_t kWholeSlice = 0xffu;   // slice number of an instance that ru
 // (COBEL_TAB_SCRATCH_ABORT_WORD in cobel_hip.h), and the polls (~1-2 us each) before it does
 constexpr uint32_t kAbortWord = COBEL_TAB_SCRATCH_ABORT_WORD;
 constexpr uint32_t kRingSpinLimit = 1u << 22;
+// the phase of a step as a type (env_step)
+template <int V>
+struct phase_c {
+  static constexpr int value = V;
+};
 struct pwg_args {
   const cobel_wrec* rec;
   const uint16_t* starts;
@@ -227,11 +245,16 @@ __device__ __forceinline__ void pwg_instance(const pwg_args& A, const int i, con
     const cobel_u4 b = cobel_philox(counter >> 2, (uint32_t)lane, g, COBEL_STREAM_MEMORY, seed_now());
     return cobel_word(b, counter & 3u);
   };
-  auto refresh_draws = [&](uint32_t pq) {
-    const uint32_t mi = (cm + 1u) >> 2;
+  auto refresh_draws = [&](uint32_t pq, uint32_t mi) {
     const bool p0 = lane == 62, p1 = lane == 63;
     blk = cobel_philox(p1 ? 2u * pq + 1u : (p0 ? 2u * pq : mi), (p0 || p1) ? 0u : (uint32_t)lane,
                        g, (p0 || p1) ? COBEL_STREAM_POLICY : COBEL_STREAM_MEMORY, seed_now());
+  };
+  // steps from the top of a step to the one that evaluates the next block: the policy's block runs
+  // out after the step with cp % 4 == 3, the memory's is needed by the step with (cm + 1) % 4 == 0
+  auto steps_to_refresh = [&]() -> int {
+    const int jp = 3 - (int)(cp & 3u), jm = 4 - (int)((cm + 1u) & 3u);
+    return jp < jm ? jp : jm;
   };
   auto enter_state = [&](int s) {
     const uint4 c = W4[s];
@@ -424,11 +447,8 @@ __device__ __forceinline__ void pwg_instance(const pwg_args& A, const int i, con
   bool live = true;
   if (iflags & 1u) enter_state(state);
   else live = begin_trial();
-  refresh_draws(cp >> 2);
-  {
-    const int jp = 3 - (int)(cp & 3u), jm = 4 - (int)((cm + 1u) & 3u);
-    refresh_in = jp < jm ? jp : jm;
-  }
+  refresh_draws(cp >> 2, (cm + 1u) >> 2);
+  refresh_in = steps_to_refresh();
   idx_cur = lane < B ? cobel_bounded(draw_m(cm), SA) : 0u;
   mg_cur = lane < B ? (uint32_t)Mg[idx_cur] : 0u;
   asm volatile("" ::"v"(warm));
@@ -466,21 +486,45 @@ __device__ __forceinline__ void pwg_instance(const pwg_args& A, const int i, con
   uint32_t batches = 0u;
   asm volatile("" : "+v"(batches));
 
-  while (live) {
-    if (budget == 0) break;
-    budget -= 1;
-
+  // ---- one step, from the draws to the planning batch; returns whether it ended the trial ----------
+  // One Philox evaluation serves four steps: lanes 62 / 63 hold the policy's blocks 2 q and 2 q + 1
+  // (two steps each: words x, y then z, w), lane j < B four words of its memory stream.  Which lane
+  // and which word a step takes follows from cp % 4 and (cm + 1) % 4.
+  //   PH = -1: both taken from the counters at run time; `refresh_in` counts down to the step that
+  //            evaluates the next blocks (steps_to_refresh).
+  //   PH >= 0: the caller guarantees that the step's counters are cp + PH and cm + PH with
+  //            cp % 4 == 0 and cm % 4 == 0 — it runs PH = 0, 1, 2, 3 in a row, and cp, cm and
+  //            `refresh_in` stay where they were at the group's first step until the caller
+  //            advances them.  In general, with (cp - cm) % 4 == 0, jp = 3 - cp % 4 and
+  //            jm = 4 - (cm + 1) % 4 of steps_to_refresh are equal at every step: the policy's and
+  //            the memory's blocks run out in the same step, PH == 3, and nowhere else.  So the
+  //            refresh is unconditional there, to blocks (cp + 4) / 4 and (cm + 4) / 4; the policy
+  //            draw is words x, y (PH even) or z, w (odd) of lane 62 (PH < 2) or 63; the memory word
+  //            is (PH + 1) % 4, for PH == 3 word 0 of the block just evaluated.  Both counters start
+  //            at zero and every training step advances both by one, so a run that only trains
+  //            keeps (cp - cm) % 4 == 0 for good; calls that draw from one stream alone (replay
+  //            between sessions, evaluation) may leave the counters apart, and such an instance
+  //            stays with PH = -1.
+  auto env_step = [&](auto ph) __attribute__((always_inline)) -> bool {
+    constexpr int PH = decltype(ph)::value;
     // ---- draws ----------------------------------------------------------------------------------
-    const int src_lane = 62 + (int)((cp >> 1) & 1u);
-    const uint32_t w0 = rl((cp & 1u) ? blk.z : blk.x, src_lane);
-    const uint32_t w1 = rl((cp & 1u) ? blk.w : blk.y, src_lane);
-    if (__builtin_expect(refresh_in == 0, 0)) {
-      refresh_draws((cp + 1u) >> 2);
-      const int jp = 4 - (int)((cp + 1u) & 3u), jm = 4 - (int)((cm + 1u) & 3u);
-      refresh_in = jp < jm ? jp : jm;
+    uint32_t w0, w1;
+    if constexpr (PH < 0) {
+      const int src_lane = 62 + (int)((cp >> 1) & 1u);
+      w0 = rl((cp & 1u) ? blk.z : blk.x, src_lane);
+      w1 = rl((cp & 1u) ? blk.w : blk.y, src_lane);
+      if (__builtin_expect(refresh_in == 0, 0)) {
+        refresh_draws((cp + 1u) >> 2, (cm + 1u) >> 2);
+        const int jp = 4 - (int)((cp + 1u) & 3u), jm = 4 - (int)((cm + 1u) & 3u);
+        refresh_in = jp < jm ? jp : jm;
+      }
+      refresh_in -= 1;
+      cp += 1u;
+    } else {
+      w0 = rl((PH & 1) ? blk.z : blk.x, 62 + (PH >> 1));
+      w1 = rl((PH & 1) ? blk.w : blk.y, 62 + (PH >> 1));
+      if constexpr (PH == 3) refresh_draws((cp + 4u) >> 2, (cm + 4u) >> 2);
     }
-    refresh_in -= 1;
-    cp += 1u;
 
     // ---- everything this step reads from Q ----------------------------------------------------------
     const uint32_t succ = succ_of(cw0, cw1);
@@ -529,12 +573,23 @@ __device__ __forceinline__ void pwg_instance(const pwg_args& A, const int i, con
     const uint32_t nw0 = rl(cand.x, a), nw1 = rl(cand.y, a);
     const uint32_t r_bits = rl(cand.z, a);
     const float r = __builtin_bit_cast(float, r_bits);
-    if (r_bits != 0u) iflags |= 2u;
+    // Rewarded steps only, a real branch (the empty asm keeps the compiler from turning it into an
+    // add and selects in every step).  The reward total: `trew` starts a trial at +0.0, and a sum
+    // rounded to nearest that starts there is never -0.0, so adding r = +0.0f changes nothing;
+    // -0.0f has bits and is added.
+    if (__builtin_expect(r_bits != 0u, 0)) {
+      iflags |= 2u;
+      trew += (double)r;
+      asm volatile("" : "+v"(trew));
+    }
     const uint32_t end = rl(cand.w, a);
     const float ns_max = __builtin_bit_cast(float, rl(fbits(smax), a));
     const uint32_t nt = 1u - end;
     const uint32_t sa = (uint32_t)state * 4u + (uint32_t)a;
-    const bool trial_over = end || (step + 1 >= A.r.steps_per_trial);
+    // (`step` is the same in every lane, but the compiler does not prove it: said here, because
+    //  the callers branch on this between the copies of the step, and a branch taken for divergent
+    //  runs the copies under exec masks)
+    const bool trial_over = end || ((int)rfl((uint32_t)step) + 1 >= A.r.steps_per_trial);
     // (everything the previous step requested is consumed BEFORE this step's requests go out: the
     //  wait for a register loaded across the loop edge is a wait for every load in flight)
     // The reward estimate of (state, a): +0.0f unless its digest entry is flagged — then, rarely
@@ -577,7 +632,6 @@ __device__ __forceinline__ void pwg_instance(const pwg_args& A, const int i, con
     __builtin_amdgcn_wave_barrier();
 
     // ---- bookkeeping ----------------------------------------------------------------------------------
-    trew += (double)r;
     const int s_prev = state;
     state = ns;
     cw0 = nw0;
@@ -585,12 +639,14 @@ __device__ __forceinline__ void pwg_instance(const pwg_args& A, const int i, con
 
     // ---- planning: next step's batch is drawn and its digest entries requested, then this batch runs -
     {
-      uint32_t idx_next = 0u, mg_next = 0u;
+      // (lanes >= B keep what they had: none of them reads idx_cur / mg_cur outside `lane < B`)
+      uint32_t idx_next = idx_cur, mg_next = mg_cur;
       const uint32_t m = (idx_cur == fresh_idx) ? fresh_m : mg_cur;
       if (lane < B) {
         float rj = 0.0f;
-        idx_next = POW2 ? cobel_word(blk, (cm + 1u) & 3u) >> SAv
-                        : cobel_bounded(cobel_word(blk, (cm + 1u) & 3u), SAv);
+        const uint32_t mword = PH < 0 ? cobel_word(blk, (cm + 1u) & 3u)
+                                      : cobel_word(blk, (uint32_t)(PH + 1) & 3u);
+        idx_next = POW2 ? mword >> SAv : cobel_bounded(mword, SAv);
         mg_next = (uint32_t)Mg[idx_next];
         if (iflags & 2u) {
           batches += 1u;
@@ -630,7 +686,52 @@ __device__ __forceinline__ void pwg_instance(const pwg_args& A, const int i, con
       idx_cur = idx_next;
       mg_cur = mg_next;
       mdig = mdig_next;
-      cm += 1u;
+      if constexpr (PH < 0) cm += 1u;
+    }
+    return trial_over;
+  };
+
+  // ---- the ticket's steps ---------------------------------------------------------------------------
+  // LDS waves take the steps in groups of four with the phase known at compile time — cp % 4 = 0,
+  // 1, 2, 3 back to back — whenever the counters are aligned at a multiple of four and four steps of
+  // budget remain; everything else (the head of a launch that starts inside a block, the up to
+  // three steps after a trial's end until cp % 4 == 0 again, the tail of the budget, instances
+  // whose counters are apart, global-memory waves) is the generic step.  A group is left at the
+  // first trial end; the counters and `refresh_in` are then what generic steps would have left, so
+  // the ONE trial-end block below and a generic step behind it go on exactly.
+  while (live) {
+    bool trial_over;
+    if (!QG && ((cp | cm) & 3u) == 0u && budget >= 4) {
+      // (`budget` step by step: a ticket that ends inside a group at trials_target reports the
+      //  steps it ran; the counters once per group)
+      uint32_t k = 1u;
+      budget -= 1;
+      trial_over = env_step(phase_c<0>());
+      if (!trial_over) {
+        step += 1;
+        budget -= 1;
+        k = 2u;
+        trial_over = env_step(phase_c<1>());
+        if (!trial_over) {
+          step += 1;
+          budget -= 1;
+          k = 3u;
+          trial_over = env_step(phase_c<2>());
+          if (!trial_over) {
+            step += 1;
+            budget -= 1;
+            k = 4u;
+            trial_over = env_step(phase_c<3>());
+          }
+        }
+      }
+      cp += k;
+      cm += k;
+      refresh_in = steps_to_refresh();
+    } else {
+      if (budget == 0) break;
+      budget -= 1;
+      trial_over = env_step(phase_c<-1>());
     }
 
     if (__builtin_expect(trial_over, 0)) {

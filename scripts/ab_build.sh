@@ -9,8 +9,8 @@ cd "$(dirname "$0")/../cobel-rl_amd/csrc"
 mkdir -p ../lib/obj_x
 F="-O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fPIC -fvisibility=hidden -munsafe-fp-atomics -Wall -Wno-unused-function"
 O=""
-for f in world tabular tabular_pwg tabular_nact sr sr_wave general sfma adam mlp mlp_fit dsr_targets dqn_act; do
-  [ "$f" = "$BASE" ] || O="$O ../lib/obj/$f.o"
+for o in ../lib/obj/*.o; do   # (every object of the regular build but the one replaced)
+  [ "$o" = "../lib/obj/$BASE.o" ] || O="$O $o"
 done
 git show HEAD:cobel-rl_amd/csrc/$SRC > ab_a.hip
 cp $SRC ab_b.hip
