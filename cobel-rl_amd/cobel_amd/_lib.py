@@ -67,10 +67,14 @@ class DQNReplay(C.Structure):
         ('is_float64', C.c_int32), ('ddqn', C.c_int32),
         ('gamma', C.c_double), ('lr', C.c_double), ('beta1', C.c_double), ('beta2', C.c_double),
         ('eps', C.c_double), ('weight_decay', C.c_double), ('tau', C.c_double),
-        ('batch_slots', C.c_void_p), ('ring_slots', C.c_int32), ('reserved_', C.c_int32),
+        ('batch_slots', C.c_void_p), ('ring_slots', C.c_int32), ('activation', C.c_int32),
         ('obs_index', C.c_void_p), ('obs_table', C.c_void_p), ('q_out', C.c_void_p),
         ('state_index', C.c_void_p), ('next_index', C.c_void_p),
     ]
+
+
+ACT_RELU, ACT_TANH = 0, 1          # cobel_dqn_replay_t.activation (COBEL_ACT_*)
+ACTIVATIONS = {'relu': ACT_RELU, 'tanh': ACT_TANH}
 
 
 class DQNAct(C.Structure):
@@ -428,6 +432,29 @@ class C2D(C.Structure):
     ]
 
 
+class DQNActC2D(C.Structure):
+    """``cobel_dqn_c2d_act_t``: ``cobel_dqn_act_t``'s policy, ring, bookkeeping and output fields
+    under the same names around a ``cobel_c2d_t`` held by value."""
+    _fields_ = [
+        ('arena', C2D),
+        ('q', C.c_void_p), ('policy_ctr', C.c_void_p), ('policy_stream', C.c_uint32),
+        ('is_float64', C.c_int32), ('epsilon', C.c_double),
+        ('ring_states', C.c_void_p), ('ring_next_states', C.c_void_p),
+        ('ring_actions', C.c_void_p), ('ring_rewards', C.c_void_p),
+        ('ring_nonterminal', C.c_void_p), ('ring_size', C.c_void_p), ('ring_head', C.c_void_p),
+        ('memory_ctr', C.c_void_p),
+        ('trial', C.c_void_p), ('step', C.c_void_p), ('trial_reward', C.c_void_p),
+        ('active', C.c_void_p), ('adam_steps', C.c_void_p),
+        ('lat_sum', C.c_void_p), ('lat_cnt', C.c_void_p), ('reward_sum', C.c_void_p),
+        ('stepped', C.c_void_p), ('batch_slots', C.c_void_p),
+        ('obs', C.c_void_p), ('reward_out', C.c_void_p), ('done_out', C.c_void_p),
+        ('wall_out', C.c_void_p), ('fallbacks', C.c_void_p),
+        ('slots', C.c_int32), ('batch', C.c_int32),
+        ('steps_per_trial', C.c_int32), ('trials_target', C.c_int32), ('trial_cap', C.c_int32),
+        ('mon_stripes', C.c_int32),
+    ]
+
+
 class SRRun(C.Structure):
     """``cobel_sr_run_t``."""
     _fields_ = [
@@ -547,6 +574,7 @@ _SIGNATURES['cobel_dsr_targets'] = (C.c_int, [C.POINTER(DSRTargets), _P])
 _SIGNATURES['cobel_c2d_plan'] = (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32 * 4)])
 _SIGNATURES['cobel_c2d_step'] = (C.c_int, [C.POINTER(C2D), _P, _P, _P, _P, _P])
 _SIGNATURES['cobel_c2d_reset'] = (C.c_int, [C.POINTER(C2D), _P, _P, _P])
+_SIGNATURES['cobel_dqn_act_c2d'] = (C.c_int, [C.POINTER(DQNActC2D), _P])
 EXPORTS = tuple(sorted(_SIGNATURES))
 
 _lib = None

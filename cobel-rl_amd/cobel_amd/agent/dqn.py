@@ -65,8 +65,8 @@ class DQN(Agent):
         # needed: True / False, or None = from 256 instances on (fixed-budget runs: only if True)
         self.use_graph = None
         self.graph_replays = 0     # lockstep steps executed from a graph so far
-        # two-kernel training step (cobel_dqn_act + cobel_dqn_replay) for 64-64 ReLU networks on a
-        # Topology: None = whenever the run qualifies (and use_graph is not forced), False = never
+        # two-kernel training step (cobel_dqn_act[_c2d] + cobel_dqn_replay) for 64-64 ReLU or tanh
+        # networks on a Topology or a Continuous2D: None = whenever the run qualifies (and use_graph is not forced), False = never
         self.fused_loop = None
         self.fused_steps = 0       # lockstep steps executed by the two-kernel loop so far
         self.fused_graph = True    # record 16 steps of the two-kernel loop into a HIP graph
@@ -196,7 +196,8 @@ class DQN(Agent):
     # -- the two-kernel training loop --------------------------------------------------------------
     def _fused_loop_ok(self, interface, pol, batch_size: int) -> bool:
         """The run is one the two fused kernels cover: a plain DQN (replay ring, blended target)
-        with a 64-64 ReLU network and an epsilon-greedy policy on a Topology."""
+        with a 64-64 ReLU or tanh network and an epsilon-greedy policy on a Topology or a
+        Continuous2D."""
         from ..interface.topology import Topology
         from ..policy.greedy import EpsilonGreedy
         net = self._online
@@ -206,12 +207,12 @@ class DQN(Agent):
                 or type(pol) is not EpsilonGreedy or not (self.target_update < 1.0) \
                 or getattr(self, '_no_replay', False) or not net.fused_mlp:
             return False
-        names = net._mlp3_names()
-        if names is None or self._target._mlp3_names() != names or not net._fused_adam_ok() \
+        kind = net._mlp3_activation()
+        if kind is None or self._target._mlp3_activation() != kind or not net._fused_adam_ok() \
                 or type(net.criterion) is not torch.nn.MSELoss \
                 or getattr(net.criterion, 'reduction', '') != 'none':
             return False
-        w = [net.params[k + '.weight'] for k in names]
+        w = [net.params[k + '.weight'] for k in kind[1]]
         if w[1].shape[2] != w[0].shape[1] or w[2].shape[2] != w[1].shape[1] \
                 or self.dtype not in (torch.float64, torch.float32):
             return False
@@ -222,12 +223,18 @@ class DQN(Agent):
     def _fused_setting_ok(self, interface) -> bool:
         """Agent class, environment and memory are the ones ``_fused_wire`` knows how to hand to
         the kernels."""
+        from ..interface.continuous import Continuous2D
         from ..interface.topology import Topology
-        return type(self) is DQN and isinstance(interface, Topology) and type(self.M) is DQNMemory
+        return type(self) is DQN and isinstance(interface, (Topology, Continuous2D)) \
+            and type(self.M) is DQNMemory
 
     def _fused_wire(self, interface, act, rep, batch_size: int):
         """Environment and memory side of the two launch descriptors; returns (world handle,
-        env state tensor, observation table, tensors to keep alive)."""
+        env state tensor, observation table, tensors to keep alive).  On a ``Continuous2D``
+        ``act`` is a ``cobel_dqn_c2d_act_t``: there is no world handle, the "table" is the ``[N, D]``
+        float64 observation buffer the act kernel writes, and the "state" the row of each instance
+        in it (0 .. N - 1) — which is how the replay kernel finds the observation for ``q_out``."""
+        from ..interface.continuous import Continuous2D
         M, n, dev = self.M, self.n_envs, self.device
         slots = torch.zeros((n, batch_size), dtype=torch.int32, device=dev)
         for run in (act, rep):
@@ -241,6 +248,17 @@ class DQN(Agent):
         act.memory_ctr, act.slots = _lib.ptr(M.counter), M.slots
         act.batch_slots = rep.batch_slots = _lib.ptr(slots)
         rep.ring_slots = M.slots
+        if isinstance(interface, Continuous2D):
+            # (the arena as it is after sync_world(), which _run has called: edges, rewards, state,
+            #  env_ctr, seed, instance_base and the scalar attributes as they are now)
+            act.arena = interface.descriptor()
+            obs = interface.observe().contiguous()
+            rows = torch.arange(n, dtype=torch.int32, device=dev)
+            act.obs = _lib.ptr(obs)
+            # the environment's own outputs, so that wall_hit and reset_fallbacks stay true
+            act.reward_out, act.done_out = _lib.ptr(interface._reward), _lib.ptr(interface._done)
+            act.wall_out, act.fallbacks = _lib.ptr(interface._wall), _lib.ptr(interface._fallbacks)
+            return None, rows, obs, [slots, rows, obs]
         act.env_ctr = _lib.ptr(interface.env_ctr)
         return interface.handle.ptr, interface.state, interface._pose_dev, [slots]
 
@@ -250,12 +268,19 @@ class DQN(Agent):
         ring store, trial bookkeeping, batch draw) and cobel_dqn_replay (the optimisation step,
         plus the Q-values of the next observation for the next cobel_dqn_act).  Same streams,
         counters and arithmetic as the PyTorch loop in ``_run``; instances that have run their
-        trials are skipped by both kernels, so the loop only looks at the device between chunks."""
+        trials are skipped by both kernels, so the loop only looks at the device between chunks.
+
+        On a ``Continuous2D`` the first launch is cobel_dqn_act_c2d.  Its descriptor carries the
+        arena's scalar attributes (``step_size``, ``body_radius``, ``wheel_distance``,
+        ``punish_wall``, ``lanes_per_instance``) by value: they are read once per ``train()`` call,
+        as the reward rows are; a change takes effect with the next call."""
         import ctypes as C
+        from ..interface.continuous import Continuous2D
         n, dev, net, M, mon = self.n_envs, self.device, self._online, self.M, self.monitors
         first = self.current_trial
         f64 = self.dtype == torch.float64
-        rep, act = _lib.DQNReplay(), _lib.DQNAct()
+        arena = isinstance(interface, Continuous2D)
+        rep, act = _lib.DQNReplay(), (_lib.DQNActC2D() if arena else _lib.DQNAct())
         world, state, table, keep = self._fused_wire(interface, act, rep, batch_size)
         q = self._q_values(interface.observe().to(self.dtype)).contiguous()
         step = torch.zeros(n, dtype=torch.int32, device=dev)
@@ -271,7 +296,8 @@ class DQN(Agent):
                     for st in opt.state.values()]
             counts = net._steps = torch.full((n,), max(seen, default=0.0), dtype=torch.float64,
                                              device=dev)
-        names = net._mlp3_names()
+        activation, names = net._mlp3_activation()
+        rep.activation = _lib.ACTIVATIONS[activation]
         for k, name in enumerate(names):
             for kind, dp, dt_, dm, dv in (('.weight', rep.w, rep.w_target, rep.m_w, rep.v_w),
                                           ('.bias', rep.b, rep.b_target, rep.m_b, rep.v_b)):
@@ -296,22 +322,27 @@ class DQN(Agent):
         rep.eps, rep.weight_decay = float(group['eps']), float(group['weight_decay'])
         rep.tau = float(self.target_update)
         rep.obs_index, rep.obs_table, rep.q_out = _lib.ptr(state), _lib.ptr(table), _lib.ptr(q)
-        act.state = _lib.ptr(state)
-        act.obs_table, act.q = _lib.ptr(table), _lib.ptr(q)
+        if not arena:
+            act.state, act.obs_table = _lib.ptr(state), _lib.ptr(table)
+            act.n, act.n_obs = n, table.shape[1]
+            act.instance_base, act.seed = interface.instance_base, interface.seed
+        act.q = _lib.ptr(q)
         act.policy_ctr, act.policy_stream = _lib.ptr(pol.counter), pol.stream
         act.is_float64, act.epsilon = int(f64), float(pol.epsilon)
         act.trial, act.step, act.trial_reward = _lib.ptr(self.trial), _lib.ptr(step), _lib.ptr(trew)
         act.active, act.adam_steps = _lib.ptr(active), _lib.ptr(counts)
         mon.fill(act)
         act.stepped = _lib.ptr(stepped)
-        act.n, act.n_obs, act.batch = n, table.shape[1], batch_size
+        act.batch = batch_size
         act.steps_per_trial, act.trials_target = steps, first + trials
-        act.instance_base, act.seed = interface.instance_base, interface.seed
         lib = _lib.lib()
 
         def pair() -> None:
             stream = _lib.current_stream(dev)        # (the capture stream while a graph records)
-            _lib.check(lib.cobel_dqn_act(world, C.byref(act), stream))
+            if arena:
+                _lib.check(lib.cobel_dqn_act_c2d(C.byref(act), stream))
+            else:
+                _lib.check(lib.cobel_dqn_act(world, C.byref(act), stream))
             _lib.check(lib.cobel_dqn_replay(C.byref(rep), stream))
 
         # The two launches of a step take all their state from device buffers whose addresses never

@@ -330,7 +330,7 @@ class StackedTorchNetwork:
                         active.view(self.n, *([1] * (v.dim() - 1))).to(v.dtype) * tau
                     v.lerp_(self.buffers[k], w)
 
-    # -- fused DQN replay step (libcobel_hip: cobel_dqn_replay) -----------------------------------
+    # -- fused DQN replay step (libcobel_hip: cobel_dqn_replay; ReLU or tanh hidden layers) --------
     fused_mlp = True       # False keeps the PyTorch forward / backward (tests compare the two)
 
     def _mlp3_names(self):
@@ -341,9 +341,36 @@ class StackedTorchNetwork:
         ``nn.Sequential``s — so the model must own exactly three Linear layers (all trainable,
         nothing else with parameters or buffers) whose shapes chain, and instance 0 must agree
         with the explicit formula on random probes."""
-        if hasattr(self, '_mlp3'):
-            return self._mlp3
-        self._mlp3 = None
+        if not hasattr(self, '_mlp3'):
+            # (both sides of the ReLUs seen: zeros and positive values among the hidden activations)
+            self._mlp3 = self._mlp3_probe(
+                nn.ReLU, torch.relu, lambda h: bool((h == 0).any()) and bool((h > 0).any()))
+        return self._mlp3
+
+    def _mlp3_activation(self):
+        """``('relu', names)`` where ``_mlp3_names()`` gives names, ``('tanh', names)`` if the model
+        computes Linear - tanh - Linear - tanh - Linear instead (the reference's Continuous2D demo,
+        demo/continuous/demo_2d.py: ``torch.tanh`` in a custom ``forward``; or ``nn.Tanh`` modules),
+        recognised the same way, else None (cached).  ``_mlp3_names()`` stays None for a tanh
+        network: the callers that route on it (cobel_mlp_fit / cobel_mlp_forward, ADQN, the Dyna
+        agents) are ReLU only.  On the probe at the weights as they are a hidden unit must leave
+        tanh's linear stretch (|h| > 0.25), where hardtanh, softsign and ``clamp(-1, 1)`` all give
+        another value; the scaled-up probe saturates every unit."""
+        if not hasattr(self, '_mlp3_act'):
+            names = self._mlp3_names()
+            if names is not None:
+                self._mlp3_act = ('relu', names)
+            else:
+                names = self._mlp3_probe(nn.Tanh, torch.tanh,
+                                         lambda h: bool((h.abs() > 0.25).any()))
+                self._mlp3_act = None if names is None else ('tanh', names)
+        return self._mlp3_act
+
+    def _mlp3_probe(self, act_module, act, hidden_used):
+        """The three Linear layers' names if the model is Linear - act - Linear - act - Linear by
+        structure (``act_module`` the only activation module allowed) and by behaviour (``act`` the
+        explicit formula; ``hidden_used(h)`` says whether the second hidden layer's values of a
+        probe can tell ``act`` from its look-alikes), else None."""
         lin = [(k, m) for k, m in self.base.named_modules() if type(m) is nn.Linear]
         want = [k + s for k, _ in lin for s in ('.weight', '.bias')]
         if len(lin) != 3 or self.buffers or sorted(want) != sorted(self.params) or \
@@ -356,16 +383,18 @@ class StackedTorchNetwork:
         # structure: besides the three Linear layers only modules that cannot change the function
         # (a saturating activation module such as ReLU6 / Hardtanh is refused outright)
         leaves = [m for m in self.base.modules() if not list(m.children())]
-        if not all(type(m) in (nn.Linear, nn.ReLU, nn.Flatten, nn.Identity) for m in leaves
+        if not all(type(m) in (nn.Linear, act_module, nn.Flatten, nn.Identity) for m in leaves
                    if m is not self.base or type(m) is nn.Linear):
             return None
+        found = None
         try:
             with torch.no_grad():
                 gen = torch.Generator(device='cpu').manual_seed(1234)
                 ok = True
                 # behaviour: at the weights as they are, and with inputs and weights scaled up so
                 # that hidden pre-activations reach ~1e5 — a clamp, ReLU6 or Hardtanh written
-                # inside a custom forward() equals ReLU on small activations only
+                # inside a custom forward() equals ReLU on small activations only (tanh: every unit
+                # saturates there; hidden_used holds its look-alikes apart on the first probe)
                 for x_scale, w_scale in ((1.0, 1.0), (1e3, 30.0)):
                     p0 = {k: v[0] * w_scale for k, v in self.params.items()}
                     x = ((torch.rand((16, w[0].shape[2]), generator=gen, dtype=torch.float64) * 4
@@ -373,19 +402,17 @@ class StackedTorchNetwork:
                     got = functional_call(self.base, (p0, {}), (x,))
                     h = x
                     for k in names[:2]:
-                        h = torch.relu(torch.nn.functional.linear(h, p0[k + '.weight'],
-                                                                  p0[k + '.bias']))
+                        h = act(torch.nn.functional.linear(h, p0[k + '.weight'], p0[k + '.bias']))
                     ref = torch.nn.functional.linear(h, p0[names[2] + '.weight'],
                                                      p0[names[2] + '.bias'])
                     tol = 1e-11 if w[0].dtype == torch.float64 else 1e-5
-                    hidden_used = bool((h == 0).any()) and bool((h > 0).any())  # both sides of
-                    ok = ok and got.shape == ref.shape and hidden_used and \
+                    ok = ok and got.shape == ref.shape and hidden_used(h) and \
                         torch.allclose(got, ref, rtol=tol, atol=tol * float(ref.abs().max() + 1))
-                if ok:                                                          # the ReLUs seen
-                    self._mlp3 = names
+                if ok:
+                    found = names
         except Exception:      # a forward that does not take one [B, D] batch: not this shape
-            self._mlp3 = None
-        return self._mlp3
+            found = None
+        return found
 
     def dqn_replay_fused(self, target: 'StackedTorchNetwork', states, actions, rewards, next_states,
                          nonterminal, gamma: float, ddqn: bool, tau: float, active=None) -> bool:
@@ -394,11 +421,12 @@ class StackedTorchNetwork:
         the network, loss, optimizer or batch is not of the shape ``cobel_dqn_replay`` covers; the
         caller then takes the PyTorch path."""
         from .. import _lib
-        names = self._mlp3_names() if self.fused_mlp else None
-        if names is None or not self._fused_adam_ok() or type(self.criterion) is not nn.MSELoss \
+        kind = self._mlp3_activation() if self.fused_mlp else None
+        if kind is None or not self._fused_adam_ok() or type(self.criterion) is not nn.MSELoss \
                 or getattr(self.criterion, 'reduction', '') != 'none' \
-                or target._mlp3_names() != names or states.dim() != 3:
+                or target._mlp3_activation() != kind or states.dim() != 3:
             return False
+        activation, names = kind
         w = [self.params[n + '.weight'] for n in names]
         dtype = w[0].dtype
         dims = (w[0].shape[2], w[0].shape[1], w[1].shape[1], w[2].shape[1])
@@ -450,6 +478,7 @@ class StackedTorchNetwork:
         run.n, run.batch = self.n, states.shape[1]
         run.n_inputs, run.n_hidden1, run.n_hidden2, run.n_actions = dims
         run.is_float64, run.ddqn = int(dtype == torch.float64), int(bool(ddqn))
+        run.activation = _lib.ACTIVATIONS[activation]
         run.gamma, run.lr = float(gamma), float(group['lr'])
         run.beta1, run.beta2 = (float(b) for b in group['betas'])
         run.eps, run.weight_decay, run.tau = float(group['eps']), float(group['weight_decay']), float(tau)

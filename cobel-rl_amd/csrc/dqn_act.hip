@@ -17,6 +17,7 @@
 // counter) on the memory stream — the same streams, counters and order as the stand-alone entry
 // points (cobel_rng_uniform, cobel_env_reset, cobel_rng_bounded_each) the PyTorch loop uses.
 #include "cobel_common.h"
+#include "cobel_dqn_batch.h"
 #include "cobel_policy.h"
 
 namespace {
@@ -172,26 +173,22 @@ template <typename T, bool DYNA>
 __global__ __launch_bounds__(256) void k_dqn_batch(const act_args A) {
   const cobel_dqn_act_t& R = A.r;
   const long long tid = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (!DYNA) {   // (the ring's draw: cobel_dqn_batch.h, shared with cobel_dqn_act_c2d)
+    cobel_dqn_ring_batch(R, tid, R.n, R.instance_base, R.seed);
+    return;
+  }
   const int i = (int)(tid / R.batch), j = (int)(tid - (long long)i * R.batch);
   if (i >= R.n || !R.stepped[i]) return;
   const uint32_t g = R.instance_base + (uint32_t)i;
   const uint32_t mc = R.memory_ctr[i] - 1u;
-  if (DYNA) {
-    const uint32_t pairs = (uint32_t)R.n_states * 4u;
-    const size_t base = (size_t)i * pairs, out = (size_t)i * R.batch + j;
-    const uint32_t idx = cobel_draw_bounded(mc, (uint32_t)j, g, COBEL_STREAM_MEMORY, R.seed, pairs);
-    R.batch_state_index[out] = (int32_t)(idx >> 2);
-    R.batch_next_index[out] = (int32_t)R.model_states[base + idx];
-    R.batch_actions[out] = (int64_t)(idx & 3u);
-    ((T*)R.batch_rewards)[out] = (T)R.model_rewards[base + idx];
-    ((T*)R.batch_nonterminal)[out] = (T)R.model_nonterminal[base + idx];
-  } else {
-    const int size = R.ring_size[i], slots = R.slots;
-    const long long head = R.ring_head[i];
-    const uint32_t idx = cobel_draw_bounded(mc, (uint32_t)j, g, COBEL_STREAM_MEMORY, R.seed,
-                                            (uint32_t)size);
-    R.batch_slots[(size_t)i * R.batch + j] = (int32_t)((head + (long long)idx) % slots);
-  }
+  const uint32_t pairs = (uint32_t)R.n_states * 4u;
+  const size_t base = (size_t)i * pairs, out = (size_t)i * R.batch + j;
+  const uint32_t idx = cobel_draw_bounded(mc, (uint32_t)j, g, COBEL_STREAM_MEMORY, R.seed, pairs);
+  R.batch_state_index[out] = (int32_t)(idx >> 2);
+  R.batch_next_index[out] = (int32_t)R.model_states[base + idx];
+  R.batch_actions[out] = (int64_t)(idx & 3u);
+  ((T*)R.batch_rewards)[out] = (T)R.model_rewards[base + idx];
+  ((T*)R.batch_nonterminal)[out] = (T)R.model_nonterminal[base + idx];
 }
 
 }  // namespace

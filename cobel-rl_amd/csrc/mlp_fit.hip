@@ -334,9 +334,27 @@ __device__ __forceinline__ weight_op<T, KS> weight_rows(const T* __restrict__ W,
   return w;
 }
 
-// One hidden layer for MT row tiles: out[m][n0 + li] = relu(bias + sum_k in[m][k] W[n0 + li][k]),
+// The hidden layers' activation, a compile-time choice (cobel_dqn_replay_t.activation): ACT 0 = ReLU,
+// 1 = tanh.  hidden_act is the forward pass; hidden_grad turns the gradient d arriving at a unit's
+// OUTPUT h into the gradient at its pre-activation: d where h > 0, or d * (1 - h * h) in exactly that
+// order (torch's tanh_backward; the library builds with -ffp-contract=off) — h is what the forward
+// pass left in LDS, so neither form stores anything extra.
+__device__ __forceinline__ float tanh_of(float x) { return tanhf(x); }
+__device__ __forceinline__ double tanh_of(double x) { return tanh(x); }
+template <int ACT, typename T>
+__device__ __forceinline__ T hidden_act(T pre) {
+  if (ACT == 1) return tanh_of(pre);
+  return pre > (T)0 ? pre : (T)0;
+}
+template <int ACT, typename T>
+__device__ __forceinline__ T hidden_grad(T h, T d) {
+  if (ACT == 1) return d * ((T)1 - h * h);
+  return h > (T)0 ? d : (T)0;
+}
+
+// One hidden layer for MT row tiles: out[m][n0 + li] = act(bias + sum_k in[m][k] W[n0 + li][k]),
 // K = 4 KS, `in` with row stride IS.
-template <typename T, int KS, int MT>
+template <typename T, int KS, int MT, int ACT = 0>
 __device__ __forceinline__ void dense_relu(const weight_op<T, KS>& w, const T* in, int IS, T* out,
                                            int m0, int n0, int lane) {
   typedef typename mfma_acc<T>::type acc_t;
@@ -349,8 +367,7 @@ __device__ __forceinline__ void dense_relu(const weight_op<T, KS>& w, const T* i
     for (int s = 0; s < KS; ++s) acc = mfma(ar[s], w.b[s], acc);
 #pragma unroll
     for (int v = 0; v < 4; ++v)
-      out[(m0 + 16 * i + mfma_acc<T>::row(lane, v)) * kRow + n0 + li] =
-          acc[v] > (T)0 ? acc[v] : (T)0;
+      out[(m0 + 16 * i + mfma_acc<T>::row(lane, v)) * kRow + n0 + li] = hidden_act<ACT>(acc[v]);
   }
 }
 
@@ -446,7 +463,7 @@ __global__ __launch_bounds__(256) void k_mlp_forward(const fwd_args A) {
 // first 16 by waves 0 .. 3), in two parts: `request` asks memory for the weight operands (ahead of
 // whatever fills L.x), `run` returns the output tile of the waves that own one (waves 0 .. 3: rows
 // 16 (w / 2) .., outputs 16 (w % 2) ..) and starts with a barrier (the rows are in LDS).
-template <typename T, bool ONE_TILE>
+template <typename T, bool ONE_TILE, int ACT = 0>
 struct forward_pass {
   weight_op<T, 8> o1;
   weight_op<T, 16> o2, o3;
@@ -469,9 +486,9 @@ struct forward_pass {
   }
   __device__ __forceinline__ typename mfma_acc<T>::type run(const act_lds<T>& L, int lane) {
     lds_barrier();
-    if (hidden) dense_relu<T, 8, 1>(o1, L.x, kXRow, L.h1, m0, n0, lane);
+    if (hidden) dense_relu<T, 8, 1, ACT>(o1, L.x, kXRow, L.h1, m0, n0, lane);
     lds_barrier();
-    if (hidden) dense_relu<T, 16, 1>(o2, L.h1, kRow, L.h2, m0, n0, lane);
+    if (hidden) dense_relu<T, 16, 1, ACT>(o2, L.h1, kRow, L.h2, m0, n0, lane);
     lds_barrier();
     typename mfma_acc<T>::type acc = splat<T>((T)0);
     if (has_out) acc = output_tile<T>(o3, L.h2, r3, lane);
@@ -498,7 +515,8 @@ __device__ __forceinline__ fit_kargs fit_kr() {
 
 // NAC: the DQN step's action count when it is known at compile time (4: every gridworld / linear
 // track; as a run-time value the loops over the actions cost the four-action step 13 %), 0 = A.n_actions.
-template <typename T, bool DQN, int NAC = 0>
+// ACT: the hidden layers' activation (hidden_act above; cobel_mlp_fit is ReLU only).
+template <typename T, bool DQN, int NAC = 0, int ACT = 0>
 __device__ __forceinline__ void mlp_fit_body(const fit_args& A) {
   constexpr int NT = kFitThreads;
   typedef typename mfma_acc<T>::type acc_t;
@@ -591,7 +609,7 @@ __device__ __forceinline__ void mlp_fit_body(const fit_args& A) {
 
     if (DQN) {
       // ---- Q_target(s') [and the online network's choice among the next actions] ---------------
-      forward_pass<T, false> tp;
+      forward_pass<T, false, ACT> tp;
       tp.request(tw1, tb1, tw2, tb2, tw3, tb3, D, O, wave, lane);
       if (t < kB) {
         const int sl = A.slots ? A.slots[(size_t)j * kB + t] : t;
@@ -618,7 +636,7 @@ __device__ __forceinline__ void mlp_fit_body(const fit_args& A) {
       stamp(1);
       if (R.debug_stage == 5) return;
       if (A.ddqn) {   // agent/dqn.py:352-355: the online network picks the action, the target rates it
-        forward_pass<T, false> op;
+        forward_pass<T, false, ACT> op;
         op.request(w1, b1, w2, b2, w3, b3, D, O, wave, lane);
         const acc_t acc = op.run(L, lane);
         if (has_out && li < NA) {
@@ -664,9 +682,9 @@ __device__ __forceinline__ void mlp_fit_body(const fit_args& A) {
     }
 
     // ---- forward --------------------------------------------------------------------------------
-    dense_relu<T, 8, 1>(o1, L.x, kXRow, L.h1, m0, n0, lane);
+    dense_relu<T, 8, 1, ACT>(o1, L.x, kXRow, L.h1, m0, n0, lane);
     lds_barrier();
-    dense_relu<T, 16, 1>(o2, L.h1, kRow, L.h2, m0, n0, lane);
+    dense_relu<T, 16, 1, ACT>(o2, L.h1, kRow, L.h2, m0, n0, lane);
     // Requested here, a barrier and a product ahead of their use: the targets of the output tile
     // (the mask and the targets, or the action, reward and terminal flag of the sample), the
     // weights behind delta2 (the column block W3[.][n0 ..], lane (li, lq) takes the outputs
@@ -800,7 +818,7 @@ __device__ __forceinline__ void mlp_fit_body(const fit_args& A) {
 #pragma unroll
       for (int v = 0; v < 4; ++v) {
         T* const h = L.h2 + (m0 + mfma_acc<T>::row(lane, v)) * kRow + n0 + li;
-        *h = *h > (T)0 ? d2[v] : (T)0;
+        *h = hidden_grad<ACT>(*h, d2[v]);
       }
       if (has_g) {
 #pragma unroll
@@ -856,7 +874,7 @@ __device__ __forceinline__ void mlp_fit_body(const fit_args& A) {
 #pragma unroll
       for (int v = 0; v < 4; ++v) {
         T* const h = L.h1 + (m0 + mfma_acc<T>::row(lane, v)) * kRow + n0 + li;
-        *h = *h > (T)0 ? d1[v] : (T)0;
+        *h = hidden_grad<ACT>(*h, d1[v]);
       }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -935,7 +953,7 @@ __device__ __forceinline__ void mlp_fit_body(const fit_args& A) {
   //  agent/dqn.py:174 -> retrieve_q)
   if (R.ep_out && R.ep_rows > 0) {
     __syncthreads();   // the new parameters are in memory; x / h1 / h2 are free
-    forward_pass<T, true> ep;
+    forward_pass<T, true, ACT> ep;
     w1 = mk_w(0, n1); b1 = mk_b(0, kH); w2 = mk_w(1, n2); b2 = mk_b(1, kH);   // REFRESH
     w3 = mk_w(2, n3); b3 = mk_b(2, (size_t)O);
     ep.request(w1, b1, w2, b2, w3, b3, D, O, wave, lane);
@@ -970,10 +988,10 @@ __global__ __launch_bounds__(kFitThreads) __attribute__((amdgpu_waves_per_eu(4, 
 void k_mlp_fit(const fit_args A) {
   mlp_fit_body<T, false>(A);
 }
-template <typename T, int NAC = kA>
+template <typename T, int NAC = kA, int ACT = 0>
 __global__ __launch_bounds__(kFitThreads) __attribute__((amdgpu_waves_per_eu(4, 4)))
 void k_dqn_replay(const fit_args A) {
-  mlp_fit_body<T, true, NAC>(A);
+  mlp_fit_body<T, true, NAC, ACT>(A);
 }
 
 int shape_ok(int32_t D, int32_t O, const char* who) {
@@ -1017,6 +1035,24 @@ int raise_lds(K kernel, int32_t lds) {
     COBEL_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   return COBEL_OK;
+}
+
+// The streaming form of the DQN step: one instantiation per dtype, action count (4 / run-time) and
+// activation.
+template <typename T, int NAC, int ACT>
+int launch_dqn_stream(const fit_args& A, int32_t lds, hipStream_t st) {
+  if (int rc = raise_lds(&k_dqn_replay<T, NAC, ACT>, lds)) return rc;   // (only a padded launch exceeds 64 KiB)
+  hipLaunchKernelGGL((k_dqn_replay<T, NAC, ACT>), dim3(A.r.n), dim3(kFitThreads), lds, st, A);
+  return COBEL_OK;
+}
+template <int ACT>
+int launch_dqn_stream(const fit_args& A, int32_t lds, hipStream_t st) {
+  const bool four = A.n_actions == kA;
+  if (A.r.is_float64)
+    return four ? launch_dqn_stream<double, kA, ACT>(A, lds, st)
+                : launch_dqn_stream<double, 0, ACT>(A, lds, st);
+  return four ? launch_dqn_stream<float, kA, ACT>(A, lds, st)
+              : launch_dqn_stream<float, 0, ACT>(A, lds, st);
 }
 
 }  // namespace
@@ -1116,7 +1152,12 @@ extern "C" int cobel_mlp_fit(const cobel_mlp_fit_t* run, void* stream) {
 // beyond that it is alone on its CU and the streaming form (k_dqn_replay here: 52 KB whatever the
 // inputs, two workgroups of eight waves per CU) wins: Dyna-DQN's 25 one-hot inputs in float64,
 // 1.34 -> 1.0 ms per step of 8 192 instances.  COBEL_DEBUG_DQN_KERNEL = lds | stream pins one
-// (experiments, tests).
+// (experiments, tests).  The staging form is ReLU only: a step with activation = COBEL_ACT_TANH takes
+// the streaming form at every width (cobel_dqn_replay), and pinning "lds" together with it is refused.
+static bool dqn_pinned_staged() {
+  const char* const v = cobel_debug_env("COBEL_DEBUG_DQN_KERNEL");
+  return v && !strcmp(v, "lds");
+}
 static bool dqn_staged(int32_t n_inputs, int32_t is_float64, int32_t n_actions) {
   if (n_actions != kA) return false;   // (the parameter-staging form is laid out for four actions)
   if (const char* v = cobel_debug_env("COBEL_DEBUG_DQN_KERNEL")) {   // exactly "lds" or "stream", else ignored
@@ -1171,9 +1212,17 @@ extern "C" int cobel_dqn_replay(const cobel_dqn_replay_t* run, void* stream) {
   COBEL_REQUIRE((((uintptr_t)r.w[1] | (uintptr_t)r.w[2] | (uintptr_t)r.w_target[1] |
                   (uintptr_t)r.w_target[2]) & 15u) == 0,
                 COBEL_E_ARG, "cobel_dqn_replay: the 64-wide weight matrices must be 16-byte aligned");
+  COBEL_REQUIRE(r.activation == COBEL_ACT_RELU || r.activation == COBEL_ACT_TANH, COBEL_E_ARG,
+                "cobel_dqn_replay: activation = %d (0 = ReLU, 1 = tanh)", r.activation);
+  const bool tanh_net = r.activation == COBEL_ACT_TANH;
+  COBEL_REQUIRE(!tanh_net || !dqn_pinned_staged(), COBEL_E_UNSUPPORTED,
+                "cobel_dqn_replay: the parameter-staging form (COBEL_DEBUG_DQN_KERNEL=lds) has no "
+                "tanh variant");
   if (r.n == 0) return COBEL_OK;
   hipStream_t st = (hipStream_t)stream;
-  if (dqn_staged(r.n_inputs, r.is_float64, r.n_actions))
+  if (tanh_net)
+    lds = (int32_t)(fit_lds_elems() * (r.is_float64 ? 8 : 4));
+  else if (dqn_staged(r.n_inputs, r.is_float64, r.n_actions))
     return cobel_dqn_replay_lds_launch(r, st, debug_trace_buffer());
   // the optimisation step of cobel_mlp_fit towards the Q-learning targets
   fit_args A;
@@ -1229,19 +1278,8 @@ extern "C" int cobel_dqn_replay(const cobel_dqn_replay_t* run, void* stream) {
   f.debug_stage = debug_stage_env();
   A.trace = debug_trace_buffer();
   lds += cobel_debug_lds_pad(lds, 160 * 1024);                                    // (occupancy)
-  const bool four = r.n_actions == kA;
-  const void* const kernel =
-      r.is_float64 ? (four ? reinterpret_cast<const void*>(&k_dqn_replay<double, kA>)
-                           : reinterpret_cast<const void*>(&k_dqn_replay<double, 0>))
-                   : (four ? reinterpret_cast<const void*>(&k_dqn_replay<float, kA>)
-                           : reinterpret_cast<const void*>(&k_dqn_replay<float, 0>));
-  if (lds > 64 * 1024) {
-    if (int rc = raise_lds(kernel, lds)) return rc;
-  }
-  if (r.is_float64 && four) hipLaunchKernelGGL((k_dqn_replay<double, kA>), dim3(r.n), dim3(kFitThreads), lds, st, A);
-  else if (r.is_float64) hipLaunchKernelGGL((k_dqn_replay<double, 0>), dim3(r.n), dim3(kFitThreads), lds, st, A);
-  else if (four) hipLaunchKernelGGL((k_dqn_replay<float, kA>), dim3(r.n), dim3(kFitThreads), lds, st, A);
-  else hipLaunchKernelGGL((k_dqn_replay<float, 0>), dim3(r.n), dim3(kFitThreads), lds, st, A);
+  if (int rc = tanh_net ? launch_dqn_stream<1>(A, lds, st) : launch_dqn_stream<0>(A, lds, st))
+    return rc;
   COBEL_HIP_TRY(hipGetLastError());
   return COBEL_OK;
 }

@@ -834,7 +834,9 @@ COBEL_API int cobel_adam_step(void* param /* [dev] [N][per_instance] */,
  * of the online network.  steps / active as for cobel_adam_step.  The batch is given gathered:
  * states / next_states [N][32][D], actions int64 [N][32], rewards and the non-terminal flags
  * (1 - end_trial, agent/dqn.py:191) [N][32] in the network's dtype.  All device memory, caller-owned.
+ * `activation` swaps both ReLUs for tanh.
  * ------------------------------------------------------------------------------------------ */
+enum { COBEL_ACT_RELU = 0, COBEL_ACT_TANH = 1 };
 typedef struct {
   void* w[3];
   void* b[3];
@@ -859,7 +861,12 @@ typedef struct {
      sample s of instance i is row batch_slots[i][s] (as written by cobel_dqn_act). */
   const int32_t* batch_slots; /* [N][batch] or NULL                                             */
   int32_t ring_slots;
-  int32_t reserved_;
+  /* the activation of both hidden layers: COBEL_ACT_RELU (0, what a zeroed struct asks for) or
+     COBEL_ACT_TANH — the network of the reference's Continuous2D demo (demo/continuous/demo_2d.py:
+     torch.tanh after both hidden layers).  Forward h = tanh(pre) in the network's dtype, backward
+     delta_l = (delta_{l+1} W_{l+1}) * (1 - h_l * h_l) in that order (torch's tanh_backward).  tanh
+     runs on the streaming form at every width; any other value is COBEL_E_ARG. */
+  int32_t activation;
   /* optional: Q-values of each instance's NEXT observation, computed with the updated online
      network at the end of the step (what the next action selection needs, agent/dqn.py:174):
      observation of instance i = row obs_index[i] of obs_table.  Instances outside `active` are
@@ -1560,6 +1567,69 @@ COBEL_API int cobel_c2d_step(const cobel_c2d_t* c2d, const uint8_t* action, doub
  * env_ctr += 2052 and *fallbacks += 1.  This bounds the reference's `while` loop (:282-283). */
 COBEL_API int cobel_c2d_reset(const cobel_c2d_t* c2d, const uint8_t* mask, int32_t* fallbacks,
                               void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * cobel_dqn_act on the arena: everything of one lockstep DQN training step that is not the
+ * network, for the agent the reference runs on Continuous2D (demo/continuous/demo_2d.py,
+ * agent/dqn.py:170-212).  Per instance, in this order:
+ *   epsilon-greedy on q (policy/greedy.py:40-88; four actions for the step robot, three for the
+ *     wheel robot), one double of the policy stream
+ *   Continuous2D.step (continuous.py:185-266), exactly cobel_c2d_step
+ *   append (observation, action, reward, observation after the step and BEFORE any reset,
+ *     1 - end_trial) to the replay ring in the network's dtype (memory/dqn.py:103-119); the
+ *     observation is (x, y) for the step robot and (x, y, orientation) for the wheel robot
+ *   trial bookkeeping and monitors (agent/dqn.py:186-212, monitor/behavior.py:82)
+ *   where the trial is over and the instance goes on: Continuous2D.reset (continuous.py:268-293),
+ *     exactly cobel_c2d_reset with a mask of that instance, env_ctr advanced as it advances it
+ *   obs = the observation the next selection looks at
+ *   the replay batch (memory/dqn.py:137), sub-streams 0 .. batch - 1 of one memory counter
+ * — the same streams, counters and order as cobel_rng_uniform + cobel_eps_greedy[_n][_f64],
+ * cobel_c2d_step, cobel_c2d_reset and cobel_rng_bounded_each, bit for bit, for every lane count.
+ * An instance whose `active` flag is 0 consumes no draw, has nothing of its own written and gets
+ * stepped = 0.  The fields shared with cobel_dqn_act_t carry its names and meanings.  arena.n,
+ * arena.seed and arena.instance_base count for the policy and memory streams as well; the scalar
+ * fields of the arena are read at the call (a recorded launch keeps them).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+  cobel_c2d_t arena;        /* state [n][3] and env_ctr [n] in/out                              */
+  /* policy */
+  const void* q;            /* [n][A] Q-values of the current observations, network dtype; A = 4
+                               (step robot) or 3 (wheel robot)                                  */
+  uint32_t* policy_ctr;     /* [n] next index on the policy stream                              */
+  uint32_t policy_stream;   /* COBEL_STREAM_POLICY or COBEL_STREAM_POLICY_TEST                  */
+  int32_t is_float64;       /* dtype of q and of the ring's floating-point arrays               */
+  double epsilon;
+  /* replay ring, [n][slots][..]; observations of n_obs = 2 (step robot) or 3 numbers            */
+  void* ring_states;
+  void* ring_next_states;
+  int64_t* ring_actions;
+  void* ring_rewards;
+  void* ring_nonterminal;
+  int32_t* ring_size;
+  int64_t* ring_head;
+  uint32_t* memory_ctr;
+  /* trial bookkeeping */
+  int32_t* trial;
+  int32_t* step;
+  double* trial_reward;
+  uint8_t* active;
+  double* adam_steps;       /* or NULL                                                          */
+  long long* lat_sum;       /* [mon_stripes][trial_cap], or NULL                                */
+  long long* lat_cnt;
+  double* reward_sum;
+  /* outputs */
+  uint8_t* stepped;         /* [n]                                                              */
+  int32_t* batch_slots;     /* [n][batch], or NULL: no batch is drawn                           */
+  double* obs;              /* [n][n_obs] float64: after the step and after any reset           */
+  double* reward_out;       /* [n] what cobel_c2d_step would have written, or NULL              */
+  uint8_t* done_out;        /* [n] or NULL                                                      */
+  uint8_t* wall_out;        /* [n] or NULL                                                      */
+  int32_t* fallbacks;       /* the counter cobel_c2d_reset adds into                            */
+  /* sizes and parameters */
+  int32_t slots, batch;
+  int32_t steps_per_trial, trials_target, trial_cap, mon_stripes;
+} cobel_dqn_c2d_act_t;
+COBEL_API int cobel_dqn_act_c2d(const cobel_dqn_c2d_act_t* run, void* stream);
 
 #ifdef __cplusplus
 }
