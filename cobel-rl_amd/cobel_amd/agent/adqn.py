@@ -25,12 +25,11 @@ steps.  Two paths, chosen as ``DQN._fused_loop_ok`` chooses:
 and the values of ``test()`` come from a forward pass of the same kernel (a fit call that trains
 nobody) or of the stack.  ``test()`` stores nothing and replays nothing.
 
-Launch and callback conventions are those of agent/rw.py and agent/anet.py: lockstep for
-``n_envs > 1`` with the trial hooks fired per session; for ``n_envs == 1`` with callbacks the
-reference's loop, one look at the device per step, with the reference's log keys
-(``trial_reward``, ``trial``, ``trial_session``, ``step``, ``steps`` and, from
-``logs.update(experience)``, ``state``, ``action``, ``reward``, ``next_state``,
-``terminal = 1 - end_trial``).  A session that would read past the last trial raises the
+Sessions and callbacks are ``SequenceAgent``'s (agent/agent.py), with no launch that covers one
+trial: lockstep for ``n_envs > 1`` with the trial hooks fired per session; for ``n_envs == 1`` with
+any callback the reference's loop, one look at the device per step, the logs also carrying, from
+``logs.update(experience)``, ``state``, ``action``, ``reward``, ``next_state`` and
+``terminal = 1 - end_trial``.  A session that would read past the last trial raises the
 reference's ``IndexError`` before anything is launched.  Per-trial traces ``trial_reward_trace`` and
 ``trial_steps_trace`` are device tensors ``[n_envs, trials]``; ``record_steps`` > 0 keeps value,
 reward, end flag and the drawn indices of that many steps per instance (``recorded_steps``,
@@ -50,11 +49,15 @@ import torch
 from .. import _lib
 from ..memory.adqn import ADQNMemory
 from ..spaces import Box
-from .agent import Agent
+from .agent import SequenceAgent
 from .dyna_dsr import DynaDSR
 
 
-class ADQN(Agent):
+class ADQN(SequenceAgent):
+    _who = 'ADQN'
+    _row_width = 3      # value, reward, end
+    one_trial_launch = False
+
     def __init__(self, observation_space, model, memory=None, custom_callbacks=None) -> None:
         if type(observation_space) is not Box:
             raise NotImplementedError(
@@ -72,14 +75,9 @@ class ADQN(Agent):
         self.memory = ADQNMemory(observation_space) if memory is None else memory
         assert isinstance(self.memory, ADQNMemory) and self.memory.dim == self.dim, \
             'ADQN takes an ADQNMemory over its own observation space'
-        self.current_trial = 0
-        self.stop = False
         self.fused_loop = None        # None: whenever the run qualifies; False: never
         self.fused_steps = 0          # lockstep steps whose replays ran in cobel_mlp_fit so far
-        self.record_steps = 0         # > 0: keep that many steps' (value, reward, end) and indices
-        self.n_envs = self.device = self._net = None
-        self.trial_reward_trace = self.trial_steps_trace = None
-        self._trace = self._idx_trace = self._trace_len = None
+        self._net = self._idx_trace = None      # (record_steps keeps the drawn indices as well)
         self._batch = 0
 
     @property
@@ -104,13 +102,8 @@ class ADQN(Agent):
         self._alive = torch.zeros(N, dtype=torch.uint8, device=dev)
         self._nobody = torch.zeros(N, dtype=torch.uint8, device=dev)
         self._done = torch.zeros(N, dtype=torch.int32, device=dev)
-        self._mid = torch.zeros(N, dtype=torch.int32, device=dev)
-        self._trew = torch.zeros(N, dtype=torch.float64, device=dev)
         self._step_rec = torch.zeros((N, 4), dtype=torch.float64, device=dev)
-        self._steps_done = torch.zeros(1, dtype=torch.int64, device=dev)
-
-    def env_steps(self) -> int:
-        return int(self._steps_done.item()) if self.n_envs is not None else 0
+        self._session_buffers()
 
     def _batch_buffers(self, B: int) -> None:
         if B == self._batch:
@@ -121,23 +114,8 @@ class ADQN(Agent):
         self._targets = torch.zeros((N, B), dtype=self.dtype, device=dev)
         self._batch = B
 
-    def _reserve(self, trials: int, B: int) -> None:
-        for name in ('trial_reward_trace', 'trial_steps_trace'):
-            old = getattr(self, name)
-            if old is not None and old.shape[1] >= trials:
-                continue
-            if name == 'trial_reward_trace':
-                new = torch.full((self.n_envs, trials), float('nan'), dtype=torch.float64,
-                                 device=self.device)
-            else:
-                new = torch.full((self.n_envs, trials), -1, dtype=torch.int32, device=self.device)
-            if old is not None:
-                new[:, :old.shape[1]] = old
-            setattr(self, name, new)
-        if self.record_steps and self._trace is None:
-            R = int(self.record_steps)
-            self._trace = torch.zeros((self.n_envs, R, 3), dtype=torch.float64, device=self.device)
-            self._trace_len = torch.zeros(self.n_envs, dtype=torch.int32, device=self.device)
+    def _reserve(self, trials: int, B: int = 0) -> None:
+        super()._reserve(trials)
         if self.record_steps and B and self._idx_trace is None:
             self._idx_trace = torch.full((self.n_envs, int(self.record_steps), B), -1,
                                          dtype=torch.int32, device=self.device)
@@ -146,8 +124,7 @@ class ADQN(Agent):
 
     def recorded_steps(self, instance: int = 0) -> np.ndarray:
         """Rows (value, reward, end) kept since ``record_steps`` was set."""
-        n = int(self._trace_len[instance].item())
-        return self._trace[instance, :n].cpu().numpy()
+        return super().recorded_steps(instance)
 
     def recorded_indices(self, instance: int = 0) -> np.ndarray:
         """The drawn indices ``[steps, batch_size]`` of the same steps (-1 in the rows of test())."""
@@ -208,60 +185,42 @@ class ADQN(Agent):
 
     # -- one session ------------------------------------------------------------------------------
     @staticmethod
-    def _session_steps(interface, trials: int, steps: int) -> np.ndarray:
-        """Steps every instance takes in a session: the schedule and the cap fix them."""
-        keys = np.stack([interface.schedule_of.astype(np.int64), interface._h_trial], axis=1)
-        uniq, inv = np.unique(keys, axis=0, return_inverse=True)
-        out = np.zeros(len(uniq), dtype=np.int64)
-        for u, (s, p) in enumerate(uniq):
-            for _ in range(trials):
-                length = int(interface._trial_len[s, p])
-                out[u] += min(length, steps)
-                p += int(length <= steps)
-        return out[inv.reshape(-1)]
-
-    @staticmethod
     def _experience(interface, step: int, value: float, reward: float, end: bool) -> dict:
         """The experience of step ``step`` of the trial instance 0 stands in (agent/adqn.py:138-144),
         the observations from the host's tables: the position depends on the schedule alone."""
         t = interface.tables
-        at = int(t['trial_off'][interface.schedule_of[0], interface._h_trial[0]]) + step
+        at = int(interface.step_at(0, step)[0])
         nxt = 0 if end else t['step_obs'][at + 1]      # (row 0 is the zero observation)
         shape = t['shape']
         return {'state': t['obs_table'][t['step_obs'][at]].reshape(shape).copy(), 'action': value,
                 'reward': reward, 'next_state': t['obs_table'][nxt].reshape(shape).copy(),
                 'terminal': 1 - int(end)}
 
-    def _session(self, interface, trials: int, steps: int, batch_size: int, nb_replays: int,
-                 learn: bool) -> None:
-        if not hasattr(interface, 'seq'):
-            raise NotImplementedError('ADQN runs on a Sequence')
-        assert interface.dim == self.dim, \
-            'the Sequence has observations of %d components, the agent %d' % (interface.dim, self.dim)
+    def _refuse(self, interface) -> None:
         if interface.has_array_rewards and not interface.overwrite:
             raise NotImplementedError(
                 'ADQN: the Sequence has array rewards and overwrite=False — the reference would '
                 'index the reward with int(value) (interface/sequence.py:165); this version serves '
                 'array rewards with overwrite=True only')
-        trials, steps, B, nb_replays = int(trials), int(steps), int(batch_size), int(nb_replays)
-        assert steps >= 1, 'steps must be at least 1'
-        assert not learn or (B > 0 and nb_replays > 0)
-        interface.plan_session(trials, steps)      # IndexError here, before any launch
-        interface._on_device()
-        self._bind_to(interface.n_envs, interface.device)
+
+    def _open(self, interface, trials: int, steps: int, learn: bool, batch_size: int = 0,
+              nb_replays: int = 0) -> None:
+        """Describe the whole session to ``cobel_adqn_step`` and compute the first value; what
+        ``_launch`` then runs is ``_one_step``, one lockstep step of all instances."""
+        B, nb_replays = int(batch_size), int(nb_replays)
         mem = self.memory
         mem._adopt(interface)
         self._adopt_user_weights()
         N, first = self.n_envs, self.current_trial
-        left = self._session_steps(interface, trials, steps)
+        self._left = left = interface.session_steps(trials, steps)
         mem.reserve(int((mem._h_count + (left if learn else 0)).max()) if learn or mem.cap else 1)
         fused = self._fused_ok(B if learn else 32)
         self._batch_buffers(B if learn else (self._batch or 32))
-        self._reserve(first + trials, B if learn else 0)
+        if learn:       # (the traces are reserved; the drawn indices need the batch size)
+            self._reserve(first + trials, B)
         self._done.zero_()
         table = interface._dev['obs_table']
-        t = interface.tables
-        rows = t['step_obs'][t['trial_off'][interface.schedule_of, interface._h_trial]]
+        rows = interface.tables['step_obs'][interface.step_at(slice(None))[0]]
         self._ep_index.copy_(torch.as_tensor(rows.astype(np.int32), device=self.device))
 
         m = mem._struct()
@@ -270,17 +229,11 @@ class ADQN(Agent):
         run.targets, run.idx = _lib.ptr(self._targets), _lib.ptr(self._idx)
         run.ep_index, run.active, run.alive = _lib.ptr(self._ep_index), _lib.ptr(self._active), \
             _lib.ptr(self._alive)
-        run.done, run.mid, run.trew = _lib.ptr(self._done), _lib.ptr(self._mid), _lib.ptr(self._trew)
-        run.trial_reward, run.trial_steps = _lib.ptr(self.trial_reward_trace), \
-            _lib.ptr(self.trial_steps_trace)
-        run.step_rec, run.steps_done = _lib.ptr(self._step_rec), _lib.ptr(self._steps_done)
-        if self._trace is not None:
-            run.trace, run.trace_len = _lib.ptr(self._trace), _lib.ptr(self._trace_len)
-            run.trace_cap = self._trace.shape[1]
-            run.idx_trace = _lib.ptr(self._idx_trace) if learn else None
+        run.done, run.step_rec = _lib.ptr(self._done), _lib.ptr(self._step_rec)
+        self._fill_session(run, first, trials, steps, 0)
+        run.idx_trace = _lib.ptr(self._idx_trace) if learn else None
         run.n, run.batch, run.is_float64 = N, self._batch, int(self.dtype == torch.float64)
-        run.trial_cap, run.flags = self.trial_reward_trace.shape[1], _lib.F_LEARN if learn else 0
-        run.trial_first, run.trials, run.steps_per_trial = first, trials, steps
+        run.flags = _lib.F_LEARN if learn else 0
         fit = self._fit_struct(table) if fused else None
         lib, seq, states = _lib.lib(), interface.seq, mem._arrays['states']
 
@@ -316,55 +269,30 @@ class ADQN(Agent):
             self._forward_rows(table)
 
         value_of_next()
-        hooks = self.callbacks
-        if not (N == 1 and hooks.has('on_trial_begin', 'on_trial_end', 'on_step_begin',
-                                     'on_step_end')):
-            for k in range(trials):
-                hooks.on_trial_begin({'trial_reward': 0.0, 'trial': first + k, 'trial_session': k})
-            for _ in range(int(left.max()) if N else 0):
-                one_step()
-            interface.commit_session(trials, steps)
-            self.current_trial = first + trials
-            self._net.write_back(self.model, 0)
-            if hooks.has('on_trial_end'):
-                rew = self.trial_reward_trace[:, first:first + trials].mean(dim=0).cpu().numpy()
-                lat = self.trial_steps_trace[:, first:first + trials].double().mean(dim=0).cpu().numpy()
-                for k in range(trials):
-                    hooks.on_trial_end({'trial_reward': float(rew[k]), 'trial': first + k,
-                                        'trial_session': k, 'steps': float(lat[k]), 'count': N})
-            return
-        for k in range(trials):
-            logs = hooks.on_trial_begin({'trial_reward': 0.0, 'trial': self.current_trial,
-                                         'trial_session': k})
-            step = 0
-            while True:
-                logs['step'] = step
-                logs = hooks.on_step_begin(logs)
-                one_step()
-                value, reward, end, _ = self._step_rec[0].cpu().numpy()
-                experience = self._experience(interface, step, float(value), float(reward),
-                                              bool(end))
-                logs['trial_reward'] += float(reward)
-                logs.update(experience)
-                logs = hooks.on_step_end(logs)
-                step += 1
-                if end or step >= steps:
-                    break
-            interface.commit_session(1, steps)
-            self.current_trial += 1
-            logs['step'] = logs['steps'] = step - 1
-            self._net.write_back(self.model, 0)
-            logs = hooks.on_trial_end(logs)
-            if self.stop:
-                break
+        self._one_step = one_step
+
+    def _launch(self, interface, pol, learn: bool, first: int, trials: int, steps: int,
+                budget: int) -> None:
+        for _ in range(1 if budget else int(self._left.max()) if self.n_envs else 0):
+            self._one_step()
+
+    def _step_logs(self, interface, step: int) -> tuple:
+        value, reward, end, _ = self._step_rec[0].cpu().numpy()
+        return self._experience(interface, step, float(value), float(reward), bool(end)), \
+            float(reward), end
+
+    def _after_trial(self, logs=None):
+        self._net.write_back(self.model, 0)
+        return logs
 
     # -- reference surface ------------------------------------------------------------------------
     def train(self, interface, trials: int, steps: int, batch_size: int = 32,
               nb_replays: int = 1) -> None:
-        self._session(interface, trials, steps, batch_size, nb_replays, True)
+        assert int(batch_size) > 0 and int(nb_replays) > 0
+        self._session(interface, trials, steps, True, batch_size=batch_size, nb_replays=nb_replays)
 
     def test(self, interface, trials: int, steps: int) -> None:
-        self._session(interface, trials, steps, 0, 0, False)
+        self._session(interface, trials, steps, False)
 
     def replay(self, batch_size: int = 32, nb_replays: int = 1) -> None:
         """agent/adqn.py:221-236: one batch from the memory, ``nb_replays`` optimisation steps."""

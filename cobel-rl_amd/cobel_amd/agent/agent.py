@@ -558,3 +558,210 @@ class FusedAgent(Agent):
                 if self.stop:
                     break
         self._session_end(pol, interface)
+
+
+class SequenceAgent(Agent):
+    """Plumbing common to the agents of a ``Sequence`` environment, which has no world handle for a
+    ``FusedAgent`` to be built around: the per-trial and per-step traces, the session half of a
+    launch struct (``_fill_session``) and the session driver.  Launches and callbacks follow the
+    module docstring: one launch per session for ``n_envs > 1``; for ``n_envs == 1`` with callbacks
+    one per trial, or per step where step callbacks are registered, with the reference's log keys
+    ``trial_reward``, ``trial``, ``trial_session``, ``step`` and ``steps`` and the agent's own.
+
+    A subclass gives ``_who``, ``_row_width`` (columns of a ``record_steps`` row), ``dim``,
+    ``_bind_to`` and ``_launch``, and the hooks below where their defaults do not fit."""
+
+    _who = 'SequenceAgent'
+    # False: no launch covers exactly one trial or hands one step back in ``_step_row``; any
+    # callback then means a launch per step, and the kernel keeps the ``record_steps`` trace itself
+    one_trial_launch = True
+
+    def __init__(self, observation_space, action_space, custom_callbacks=None) -> None:
+        super().__init__(observation_space, action_space, custom_callbacks)
+        self.policy = self.policy_test = None
+        self.record_steps = 0         # > 0: keep one row of that many steps per instance
+        self.n_envs = self.device = None
+        self.trial_reward_trace = self.trial_steps_trace = self.trial_action_trace = None
+        self._trace = self._trace_len = self._step_row = self._step_len = None
+        self._mid = self._trew = self._steps_done = None
+        self._sessions = 0
+
+    def _session_buffers(self) -> None:
+        """What the kernels keep between launches, allocated by ``_bind_to``."""
+        N, dev = self.n_envs, self.device
+        self._mid = torch.zeros(N, dtype=torch.int32, device=dev)
+        self._trew = torch.zeros(N, dtype=torch.float64, device=dev)
+        self._steps_done = torch.zeros(1, dtype=torch.int64, device=dev)
+        if self.one_trial_launch:
+            self._step_row = torch.zeros((N, 1, self._row_width), dtype=torch.float64, device=dev)
+            self._step_len = torch.zeros(N, dtype=torch.int32, device=dev)
+
+    def env_steps(self) -> int:
+        """Env steps executed by this agent's kernels so far."""
+        return int(self._steps_done.item()) if self.n_envs is not None else 0
+
+    def recorded_steps(self, instance: int = 0) -> np.ndarray:
+        """The rows kept since ``record_steps`` was set."""
+        n = int(self._trace_len[instance].item())
+        return self._trace[instance, :n].cpu().numpy()
+
+    def _trial_traces(self) -> tuple:
+        """The per-trial traces ``[n_envs, trials]`` this agent keeps."""
+        return ('trial_reward_trace', 'trial_steps_trace')
+
+    def _reserve(self, trials: int) -> None:
+        for name in self._trial_traces():
+            old = getattr(self, name)
+            if old is not None and old.shape[1] >= trials:
+                continue
+            fill, dtype = (float('nan'), torch.float64) if name == 'trial_reward_trace' \
+                else (-1, torch.int32)
+            new = torch.full((self.n_envs, trials), fill, dtype=dtype, device=self.device)
+            if old is not None:
+                new[:, :old.shape[1]] = old
+            setattr(self, name, new)
+        if self.record_steps and self._trace is None:
+            self._trace = torch.zeros((self.n_envs, int(self.record_steps), self._row_width),
+                                      dtype=torch.float64, device=self.device)
+            self._trace_len = torch.zeros(self.n_envs, dtype=torch.int32, device=self.device)
+
+    def _policy_in(self, pol, interface) -> None:
+        """Adopt the policy's stream and draw counters.  It is always ``policy`` and its stream
+        STREAM_POLICY: the reference selects with ``policy`` in ``test()`` too (agent/rw.py:359,
+        agent/anet.py:272); ``policy_test`` is stored only."""
+        if pol.seed is None:
+            pol.seed = interface.seed
+        assert pol.seed == interface.seed, 'all streams of an instance derive from the environment seed'
+        if pol.stream is None:
+            pol.stream = _lib.STREAM_POLICY
+        if pol.counter is None or pol.counter.numel() != self.n_envs or \
+                pol.counter.device != self.device:
+            pol.counter = torch.zeros(self.n_envs, dtype=torch.int32, device=self.device)
+
+    _SESSION_FIELDS = ('mid', 'trew', 'steps_done', 'trial_reward', 'trial_steps', 'trial_action',
+                       'trial_cap', 'trial_first', 'trials', 'steps_per_trial', 'step_budget')
+
+    def _fill_session(self, run, first: int, trials: int, steps: int, budget: int) -> None:
+        """What every launch struct says the same way, where ``run`` declares the field: the
+        bookkeeping between launches, the per-trial traces, the trials to run, and where the
+        steps are kept — with a launch per step, in a row of its own."""
+        ptr = _lib.ptr
+        values = {'mid': ptr(self._mid), 'trew': ptr(self._trew), 'steps_done': ptr(self._steps_done),
+                  'trial_reward': ptr(self.trial_reward_trace),
+                  'trial_steps': ptr(self.trial_steps_trace),
+                  'trial_action': ptr(self.trial_action_trace),
+                  'trial_cap': self.trial_reward_trace.shape[1], 'trial_first': first,
+                  'trials': trials, 'steps_per_trial': steps, 'step_budget': budget}
+        for name in _declared(type(run), self._SESSION_FIELDS):
+            setattr(run, name, values[name])
+        if budget == 1:
+            self._step_len.zero_()
+            run.trace, run.trace_len, run.trace_cap = ptr(self._step_row), ptr(self._step_len), 1
+        elif self._trace is not None:
+            run.trace, run.trace_len = ptr(self._trace), ptr(self._trace_len)
+            run.trace_cap = self._trace.shape[1]
+
+    # -- hooks ------------------------------------------------------------------------------------
+    def _refuse(self, interface) -> None:
+        """Raise for a Sequence this agent does not serve."""
+
+    def _open(self, interface, trials: int, steps: int, learn: bool) -> None:
+        """The session opens: bound, traces reserved, nothing launched yet."""
+
+    @abc.abstractmethod
+    def _bind_to(self, n_envs: int, device) -> None:
+        ...
+
+    @abc.abstractmethod
+    def _launch(self, interface, pol, learn: bool, first: int, trials: int, steps: int,
+                budget: int) -> None:
+        """Run ``trials`` trials from trial ``first`` on (budget 0), or one step (budget 1)."""
+
+    def _step_logs(self, interface, step: int) -> tuple:
+        """After a launch of one step: its log entries, its reward and its end flag."""
+        raise NotImplementedError
+
+    def _trial_logs(self, interface, at: int, last_step: int) -> dict:
+        """After a launch of the one trial ``at``: the agent's own log entries."""
+        return {}
+
+    def _after_trial(self, logs=None):
+        """After the launch(es) of one trial — of all trials, without logs, in a batched session —
+        and before ``on_trial_end``."""
+        return logs
+
+    # -- the shared session driver ----------------------------------------------------------------
+    def _session(self, interface, trials: int, steps: int, learn: bool, **how) -> None:
+        if not hasattr(interface, 'seq'):
+            raise NotImplementedError('%s runs on a Sequence' % self._who)
+        assert interface.dim == self.dim, \
+            'the Sequence has observations of %d components, the agent %d' % (interface.dim, self.dim)
+        self._refuse(interface)
+        trials, steps = int(trials), int(steps)
+        assert steps >= 1, 'steps must be at least 1'
+        interface.plan_session(trials, steps)      # IndexError here, before any launch
+        interface._on_device()
+        self._bind_to(interface.n_envs, interface.device)
+        pol = self.policy      # (in test() too, as the reference's: `policy_test` is stored only)
+        if pol is not None:
+            self._policy_in(pol, interface)
+        first = self.current_trial
+        self._reserve(first + trials)
+        self._open(interface, trials, steps, learn, **how)
+        self._sessions += 1
+        hooks = self.callbacks
+        per_trial = self.n_envs == 1 and hooks.has('on_trial_begin', 'on_trial_end',
+                                                   'on_step_begin', 'on_step_end')
+        per_step = per_trial and (not self.one_trial_launch
+                                  or hooks.has('on_step_begin', 'on_step_end'))
+        if not per_trial:
+            for t in range(trials):
+                hooks.on_trial_begin({'trial_reward': 0.0, 'trial': first + t, 'trial_session': t})
+            self._launch(interface, pol, learn, first, trials, steps, 0)
+            interface.commit_session(trials, steps)
+            self.current_trial = first + trials
+            self._after_trial()
+            if hooks.has('on_trial_end'):
+                rew = self.trial_reward_trace[:, first:first + trials].mean(dim=0).cpu().numpy()
+                lat = self.trial_steps_trace[:, first:first + trials].double().mean(dim=0).cpu().numpy()
+                for t in range(trials):
+                    hooks.on_trial_end({
+                        'trial_reward': float(rew[t]), 'trial': first + t, 'trial_session': t,
+                        'steps': float(lat[t]), 'count': self.n_envs})
+            return
+        for t in range(trials):
+            logs = hooks.on_trial_begin({'trial_reward': 0.0, 'trial': self.current_trial,
+                                         'trial_session': t})
+            at = self.current_trial
+            if per_step:
+                step = 0
+                while True:
+                    logs['step'] = step
+                    logs = hooks.on_step_begin(logs)
+                    self._launch(interface, pol, learn, at, 1, steps, 1)
+                    entries, reward, end = self._step_logs(interface, step)
+                    if self.one_trial_launch and self._trace is not None:
+                        # (the kernel wrote to the one-row buffer: the trace is kept here)
+                        n = int(self._trace_len[0].item())
+                        if n < self._trace.shape[1]:
+                            self._trace[0, n] = self._step_row[0, 0]
+                            self._trace_len[0] = n + 1
+                    logs['trial_reward'] += reward
+                    logs.update(entries)
+                    logs = hooks.on_step_end(logs)
+                    step += 1
+                    if end or step >= steps:
+                        break
+                logs['steps'] = step - 1
+                if not self.one_trial_launch:
+                    logs['step'] = step - 1
+            else:
+                self._launch(interface, pol, learn, at, 1, steps, 0)
+                logs['step'] = logs['steps'] = int(self.trial_steps_trace[0, at].item())
+                logs['trial_reward'] = float(self.trial_reward_trace[0, at].item())
+                logs.update(self._trial_logs(interface, at, logs['steps']))
+            interface.commit_session(1, steps)
+            self.current_trial += 1
+            logs = hooks.on_trial_end(self._after_trial(logs))
+            if self.stop:
+                break

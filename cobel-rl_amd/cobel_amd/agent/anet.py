@@ -11,12 +11,8 @@ the agent meets its environment and device tensors ``[n_envs, D, A - 1]`` from t
 array ``[n_envs, D, A - 1]``.  There are A - 1 outputs: the agent only ever chooses the actions
 0 ... A - 2, as the reference's does.
 
-The class derives from ``Agent``, not from ``FusedAgent``, for the reason agent/rw.py gives: that
-one's device state is built around a world handle, of which a Sequence has none.  The launch
-convention is the same: one launch per session for ``n_envs > 1``; for ``n_envs == 1`` with
-callbacks one per trial, or per step where step callbacks are registered, with the reference's log
-keys (``trial_reward``, ``trial``, ``trial_session``, ``step``, ``steps`` and, from
-``logs.update(experience)``, ``state``, ``action``, ``reward``, ``next_state``, ``terminal``).
+Sessions, launches and callbacks are ``SequenceAgent``'s (agent/agent.py); the logs also carry,
+from ``logs.update(experience)``, ``state``, ``action``, ``reward``, ``next_state``, ``terminal``.
 Per-trial traces ``trial_reward_trace``, ``trial_steps_trace`` and ``trial_action_trace`` are device
 tensors ``[n_envs, trials]``; ``record_steps`` > 0 keeps action, reward, end flag and the A - 1
 outputs of that many steps per instance (``recorded_steps``).
@@ -37,12 +33,14 @@ from .. import _lib
 from ..interface.gridworld import _as_seed
 from ..policy.greedy import EpsilonGreedy
 from ..spaces import Box, Discrete
-from .agent import Agent
+from .agent import SequenceAgent
 
 KEYS = ('excitatory', 'inhibitory')
 
 
-class AssociativeNetwork(Agent):
+class AssociativeNetwork(SequenceAgent):
+    _who = 'AssociativeNetwork'
+
     def __init__(self, observation_space, action_space, policy, policy_test=None, saturation=20.0,
                  learning_rate=0.01, noise=1.0, linear_update=False, custom_callbacks=None,
                  rng=None) -> None:
@@ -76,11 +74,7 @@ class AssociativeNetwork(Agent):
         self.noise_amplitude = noise
         self.alpha = 1.0
         self.d_alpha = 0.0
-        self.record_steps = 0         # > 0: keep that many steps' (action, reward, end, q ...)
-        self.n_envs = self.device = None
-        self.trial_reward_trace = self.trial_steps_trace = self.trial_action_trace = None
-        self._trace = self._trace_len = None
-        self._sessions = 0
+        self._row_width = 2 + self.n_actions      # action, reward, end, q[0] ... q[A - 2]
         self._seed = self._instance_ids = None
         self._instance_base = 0
         self._rows_key, self._rows_dev = {}, {}
@@ -109,11 +103,7 @@ class AssociativeNetwork(Agent):
                                               device=device)
         self.device = self.weights[KEYS[0]].device      # (with its index: 'cuda' is 'cuda:0')
         self._agent_ctr = torch.full((N,), drawn, dtype=torch.int32, device=device)
-        self._mid = torch.zeros(N, dtype=torch.int32, device=device)
-        self._trew = torch.zeros(N, dtype=torch.float64, device=device)
-        self._steps_done = torch.zeros(1, dtype=torch.int64, device=device)
-        self._step_row = torch.zeros((N, 1, 3 + NA), dtype=torch.float64, device=device)
-        self._step_len = torch.zeros(N, dtype=torch.int32, device=device)
+        self._session_buffers()
         self._rows_key, self._rows_dev = {}, {}
 
     def _bind_alone(self) -> None:
@@ -123,9 +113,6 @@ class AssociativeNetwork(Agent):
             self._bind_to(1, torch.device('cuda', torch.cuda.current_device()))
         if self._seed is None:
             self._seed = _as_seed(self.rng)
-
-    def env_steps(self) -> int:
-        return int(self._steps_done.item()) if self.n_envs is not None else 0
 
     # -- parameters -------------------------------------------------------------------------------
     def _weights(self, key: str):
@@ -192,28 +179,12 @@ class AssociativeNetwork(Agent):
         run.seed = self._seed
 
     # -- traces -----------------------------------------------------------------------------------
-    def _reserve(self, trials: int) -> None:
-        for name in ('trial_reward_trace', 'trial_steps_trace', 'trial_action_trace'):
-            old = getattr(self, name)
-            if old is not None and old.shape[1] >= trials:
-                continue
-            if name == 'trial_reward_trace':
-                new = torch.full((self.n_envs, trials), float('nan'), dtype=torch.float64,
-                                 device=self.device)
-            else:
-                new = torch.full((self.n_envs, trials), -1, dtype=torch.int32, device=self.device)
-            if old is not None:
-                new[:, :old.shape[1]] = old
-            setattr(self, name, new)
-        if self.record_steps and self._trace is None:
-            self._trace = torch.zeros((self.n_envs, int(self.record_steps), 2 + self.n_actions),
-                                      dtype=torch.float64, device=self.device)
-            self._trace_len = torch.zeros(self.n_envs, dtype=torch.int32, device=self.device)
+    def _trial_traces(self) -> tuple:
+        return super()._trial_traces() + ('trial_action_trace',)
 
     def recorded_steps(self, instance: int = 0) -> np.ndarray:
         """Rows (action, reward, end, q[0] ... q[A - 2]) kept since ``record_steps`` was set."""
-        n = int(self._trace_len[instance].item())
-        return self._trace[instance, :n].cpu().numpy()
+        return super().recorded_steps(instance)
 
     # -- launch -----------------------------------------------------------------------------------
     def _launch(self, interface, pol, learn: bool, first: int, trials: int, steps: int,
@@ -224,44 +195,16 @@ class AssociativeNetwork(Agent):
         run.eps = _lib.ptr(self._eps_rows(pol))
         run.eps_rows = self._rows_dev[('epsilon', '')].shape[0]
         run.pol_ctr, run.pol_stream = _lib.ptr(pol.counter), pol.stream
-        run.mid, run.trew, run.steps_done = _lib.ptr(self._mid), _lib.ptr(self._trew), \
-            _lib.ptr(self._steps_done)
-        run.trial_reward, run.trial_steps = _lib.ptr(self.trial_reward_trace), \
-            _lib.ptr(self.trial_steps_trace)
-        run.trial_action = _lib.ptr(self.trial_action_trace)
-        run.trial_cap = self.trial_reward_trace.shape[1]
-        if budget == 1:         # a launch per step: the step comes back in a row of its own
-            self._step_len.zero_()
-            run.trace, run.trace_len, run.trace_cap = _lib.ptr(self._step_row), \
-                _lib.ptr(self._step_len), 1
-        elif self._trace is not None:
-            run.trace, run.trace_len = _lib.ptr(self._trace), _lib.ptr(self._trace_len)
-            run.trace_cap = self._trace.shape[1]
-        run.trial_first, run.trials, run.steps_per_trial, run.step_budget = first, trials, steps, budget
+        self._fill_session(run, first, trials, steps, budget)
         _lib.check(_lib.lib().cobel_anet_run(C.byref(interface.seq), C.byref(run),
                                              _lib.current_stream(self.device)))
-
-    def _policy_in(self, pol, interface) -> None:
-        """Adopt the policy's stream and draw counters.  It is always ``policy`` and its stream
-        STREAM_POLICY: the reference selects with ``policy`` in ``test()`` too (agent/anet.py:272);
-        ``policy_test`` is stored only."""
-        if pol.seed is None:
-            pol.seed = interface.seed
-        assert pol.seed == interface.seed, 'all streams of an instance derive from the environment seed'
-        if pol.stream is None:
-            pol.stream = _lib.STREAM_POLICY
-        if pol.counter is None or pol.counter.numel() != self.n_envs or \
-                pol.counter.device != self.device:
-            pol.counter = torch.zeros(self.n_envs, dtype=torch.int32, device=self.device)
 
     @staticmethod
     def _experience(interface, step: int, action: int) -> dict:
         """The experience of step ``step`` of the trial instance 0 stands in (agent/anet.py:218-224),
         from the host's tables: the position depends on the schedule alone."""
         t = interface.tables
-        first = int(t['trial_off'][interface.schedule_of[0], interface._h_trial[0]])
-        length = int(interface._trial_len[interface.schedule_of[0], interface._h_trial[0]])
-        at = first + step
+        at, length = (int(v) for v in interface.step_at(0, step))
         end = step + 1 >= length
         if t['step_scalar'][at]:
             reward = float(t['step_reward'][at, 0])
@@ -273,83 +216,26 @@ class AssociativeNetwork(Agent):
         return {'state': t['obs_table'][t['step_obs'][at]].copy(), 'action': action,
                 'reward': reward, 'next_state': t['obs_table'][nxt].copy(), 'terminal': 1 - end}
 
-    def _session(self, interface, trials: int, steps: int, learn: bool) -> None:
-        if not hasattr(interface, 'seq'):
-            raise NotImplementedError('AssociativeNetwork runs on a Sequence')
-        assert interface.dim == self.dim, \
-            'the Sequence has observations of %d components, the agent %d' % (interface.dim, self.dim)
+    def _refuse(self, interface) -> None:
         A = int(interface.action_space.n)
         if interface.has_array_rewards and not interface.overwrite and self.n_actions - 1 > A:
             raise IndexError('index %d is out of bounds for axis 0 with size %d: the agent chooses '
                              'among %d actions, the array rewards of the Sequence have %d entries'
                              % (A, A, self.n_actions - 1, A))
-        trials, steps = int(trials), int(steps)
-        assert steps >= 1, 'steps must be at least 1'
-        interface.plan_session(trials, steps)      # IndexError here, before any launch
-        interface._on_device()
-        self._bind_to(interface.n_envs, interface.device)
+
+    def _open(self, interface, trials: int, steps: int, learn: bool) -> None:
         assert self._seed in (None, interface.seed) or self._sessions == 0, \
             'all streams of an instance derive from the environment seed'
         self._seed, self._instance_base = interface.seed, interface.instance_base
         self._instance_ids = interface.instance_ids
-        pol = self.policy
-        self._policy_in(pol, interface)
-        first = self.current_trial
-        self._reserve(first + trials)
-        self._sessions += 1
-        per_step = self.n_envs == 1 and self.callbacks.has('on_step_begin', 'on_step_end')
-        per_trial = self.n_envs == 1 and (per_step or self.callbacks.has('on_trial_begin',
-                                                                         'on_trial_end'))
-        if not per_trial:
-            for t in range(trials):
-                self.callbacks.on_trial_begin({'trial_reward': 0.0, 'trial': first + t,
-                                               'trial_session': t})
-            self._launch(interface, pol, learn, first, trials, steps, 0)
-            interface.commit_session(trials, steps)
-            self.current_trial = first + trials
-            if self.callbacks.has('on_trial_end'):
-                rew = self.trial_reward_trace[:, first:first + trials].mean(dim=0).cpu().numpy()
-                lat = self.trial_steps_trace[:, first:first + trials].double().mean(dim=0).cpu().numpy()
-                for t in range(trials):
-                    self.callbacks.on_trial_end({
-                        'trial_reward': float(rew[t]), 'trial': first + t, 'trial_session': t,
-                        'steps': float(lat[t]), 'count': self.n_envs})
-            return
-        for t in range(trials):
-            logs = self.callbacks.on_trial_begin({'trial_reward': 0.0, 'trial': self.current_trial,
-                                                  'trial_session': t})
-            at = self.current_trial
-            if per_step:
-                step = 0
-                while True:
-                    logs['step'] = step
-                    logs = self.callbacks.on_step_begin(logs)
-                    self._launch(interface, pol, learn, at, 1, steps, 1)
-                    row = self._step_row[0, 0].cpu().numpy()
-                    if self._trace is not None:
-                        n = int(self._trace_len[0].item())
-                        if n < self._trace.shape[1]:
-                            self._trace[0, n] = self._step_row[0, 0]
-                            self._trace_len[0] = n + 1
-                    experience = self._experience(interface, step, int(row[0]))
-                    logs['trial_reward'] += experience['reward']
-                    logs.update(experience)
-                    logs = self.callbacks.on_step_end(logs)
-                    step += 1
-                    if row[2] or step >= steps:
-                        break
-                logs['steps'] = step - 1
-            else:
-                self._launch(interface, pol, learn, at, 1, steps, 0)
-                logs['step'] = logs['steps'] = int(self.trial_steps_trace[0, at].item())
-                logs['trial_reward'] = float(self.trial_reward_trace[0, at].item())
-                logs.update(self._experience(interface, logs['steps'],
-                                             int(self.trial_action_trace[0, at].item())))
-            interface.commit_session(1, steps)
-            self.current_trial += 1
-            logs = self.callbacks.on_trial_end(logs)
-            if self.stop:
-                break
+
+    def _step_logs(self, interface, step: int) -> tuple:
+        row = self._step_row[0, 0].cpu().numpy()
+        experience = self._experience(interface, step, int(row[0]))
+        return experience, experience['reward'], row[2]
+
+    def _trial_logs(self, interface, at: int, last_step: int) -> dict:
+        return self._experience(interface, last_step, int(self.trial_action_trace[0, at].item()))
 
     # -- reference surface ------------------------------------------------------------------------
     def train(self, interface, trials: int, steps: int = 32) -> None:

@@ -8,12 +8,8 @@ attributes ``W``, ``learning_rate``, ``current_trial``, ``stop`` (and ``policy``
 float, a tuple of length D as in the reference, or an array ``[n_envs]`` or ``[n_envs, D]`` (an
 array of length D is the reference's tuple, also where ``n_envs == D``).
 
-The classes derive from ``Agent``, not from ``FusedAgent``: that one's device state is built around
-a world handle (states, action masks, start draws), of which a Sequence has none.  The launch
-convention is the same: one launch per session for ``n_envs > 1``; for ``n_envs == 1`` with
-callbacks one per trial, or per step where step callbacks are registered, with the reference's log
-keys (``trial_reward``, ``trial``, ``trial_session``, ``step``, ``steps`` and, for the binary agent,
-``action``).  Per-trial traces ``trial_reward_trace``, ``trial_steps_trace`` and (binary)
+Sessions, launches and callbacks are ``SequenceAgent``'s (agent/agent.py); the binary agent adds
+``action`` to the logs.  Per-trial traces ``trial_reward_trace``, ``trial_steps_trace`` and (binary)
 ``trial_action_trace`` are device tensors ``[n_envs, trials]``; ``record_steps`` > 0 keeps value,
 action, reward and end flag of that many steps per instance (``recorded_steps``).
 """
@@ -27,7 +23,7 @@ import torch
 from .. import _lib
 from ..policy.scalar import ScalarPolicy
 from ..spaces import Box, Discrete
-from .agent import Agent
+from .agent import SequenceAgent
 
 
 class Weights(torch.Tensor):
@@ -37,8 +33,9 @@ class Weights(torch.Tensor):
         self.fill_(value)
 
 
-class RescorlaWagner(Agent):
+class RescorlaWagner(SequenceAgent):
     _who = 'RescorlaWagner'
+    _row_width = 4      # value, action, reward, end
 
     def __init__(self, observation_space, learning_rate=0.9, custom_callbacks=None) -> None:
         assert type(observation_space) is Box, 'Wrong observation space!'
@@ -53,12 +50,6 @@ class RescorlaWagner(Agent):
             self.learning_rate = learning_rate
         else:
             self.learning_rate = np.array(learning_rate)
-        self.policy = self.policy_test = None
-        self.record_steps = 0         # > 0: keep that many steps' (value, action, reward, end)
-        self.n_envs = self.device = None
-        self.trial_reward_trace = self.trial_steps_trace = self.trial_action_trace = None
-        self._trace = self._trace_len = None
-        self._sessions = 0
         self._lr_key = self._lr_dev = None
         self._pol_key = self._pol_dev = None
 
@@ -90,15 +81,8 @@ class RescorlaWagner(Agent):
         rows = np.broadcast_to(w.reshape(-1, D), (N, D))
         self.n_envs, self.device = N, device
         self._W = torch.as_tensor(np.array(rows, dtype=np.float64, order='C'), device=device).as_subclass(Weights)
-        self._mid = torch.zeros(N, dtype=torch.int32, device=device)
-        self._trew = torch.zeros(N, dtype=torch.float64, device=device)
-        self._steps_done = torch.zeros(1, dtype=torch.int64, device=device)
-        self._step_row = torch.zeros((N, 1, 4), dtype=torch.float64, device=device)
-        self._step_len = torch.zeros(N, dtype=torch.int32, device=device)
+        self._session_buffers()
         self._lr_key = self._pol_key = None
-
-    def env_steps(self) -> int:
-        return int(self._steps_done.item()) if self.n_envs is not None else 0
 
     # -- parameters -------------------------------------------------------------------------------
     def _lr_rows(self):
@@ -137,31 +121,13 @@ class RescorlaWagner(Agent):
                 'serves array rewards with overwrite=True only')
 
     # -- traces -----------------------------------------------------------------------------------
-    def _reserve(self, trials: int) -> None:
-        names = ['trial_reward_trace', 'trial_steps_trace']
-        if self.policy is not None:
-            names.append('trial_action_trace')
-        for name in names:
-            old = getattr(self, name)
-            if old is not None and old.shape[1] >= trials:
-                continue
-            if name == 'trial_reward_trace':
-                new = torch.full((self.n_envs, trials), float('nan'), dtype=torch.float64,
-                                 device=self.device)
-            else:
-                new = torch.full((self.n_envs, trials), -1, dtype=torch.int32, device=self.device)
-            if old is not None:
-                new[:, :old.shape[1]] = old
-            setattr(self, name, new)
-        if self.record_steps and self._trace is None:
-            self._trace = torch.zeros((self.n_envs, int(self.record_steps), 4), dtype=torch.float64,
-                                      device=self.device)
-            self._trace_len = torch.zeros(self.n_envs, dtype=torch.int32, device=self.device)
+    def _trial_traces(self) -> tuple:
+        names = super()._trial_traces()
+        return names if self.policy is None else names + ('trial_action_trace',)
 
     def recorded_steps(self, instance: int = 0) -> np.ndarray:
         """Rows (value, action, reward, end) kept since ``record_steps`` was set."""
-        n = int(self._trace_len[instance].item())
-        return self._trace[instance, :n].cpu().numpy()
+        return super().recorded_steps(instance)
 
     # -- launch -----------------------------------------------------------------------------------
     def _launch(self, interface, pol, learn: bool, first: int, trials: int, steps: int,
@@ -172,115 +138,24 @@ class RescorlaWagner(Agent):
         run.n, run.flags = self.n_envs, _lib.F_LEARN if learn else 0
         run.instance_base, run.instance_ids = interface.instance_base, _lib.ptr(interface.instance_ids)
         run.seed = interface.seed
-        run.mid, run.trew, run.steps_done = _lib.ptr(self._mid), _lib.ptr(self._trew), \
-            _lib.ptr(self._steps_done)
-        run.trial_reward, run.trial_steps = _lib.ptr(self.trial_reward_trace), \
-            _lib.ptr(self.trial_steps_trace)
-        run.trial_action = _lib.ptr(self.trial_action_trace)
-        run.trial_cap = self.trial_reward_trace.shape[1]
-        if budget == 1:         # a launch per step: the step comes back in a row of its own
-            self._step_len.zero_()
-            run.trace, run.trace_len, run.trace_cap = _lib.ptr(self._step_row), \
-                _lib.ptr(self._step_len), 1
-        elif self._trace is not None:
-            run.trace, run.trace_len = _lib.ptr(self._trace), _lib.ptr(self._trace_len)
-            run.trace_cap = self._trace.shape[1]
+        self._fill_session(run, first, trials, steps, budget)
         run.policy = _lib.RW_POLICY_NONE
         if pol is not None:
             run.policy, run.code_reverse = pol.kind, int(bool(pol.code_reverse))
             run.pol = _lib.ptr(self._pol_rows(pol))
             run.pol_rows = self._pol_dev.shape[0]
             run.pol_ctr, run.pol_stream = _lib.ptr(pol.counter), pol.stream
-        run.trial_first, run.trials, run.steps_per_trial, run.step_budget = first, trials, steps, budget
         _lib.check(_lib.lib().cobel_rw_run(C.byref(interface.seq), C.byref(run),
                                            _lib.current_stream(self.device)))
 
-    def _policy_in(self, pol, interface) -> None:
-        """Adopt the policy's stream and draw counters.  It is always ``policy`` and its stream
-        STREAM_POLICY: the reference selects with ``policy`` in ``test()`` too (agent/rw.py:359);
-        ``policy_test`` is stored only."""
-        if pol.seed is None:
-            pol.seed = interface.seed
-        assert pol.seed == interface.seed, 'all streams of an instance derive from the environment seed'
-        if pol.stream is None:
-            pol.stream = _lib.STREAM_POLICY
-        if pol.counter is None or pol.counter.numel() != self.n_envs or \
-                pol.counter.device != self.device:
-            pol.counter = torch.zeros(self.n_envs, dtype=torch.int32, device=self.device)
+    def _step_logs(self, interface, step: int) -> tuple:
+        value, action, reward, end = self._step_row[0, 0].cpu().numpy()
+        return ({} if self.policy is None else {'action': int(action)}), float(reward), end
 
-    def _session(self, interface, trials: int, steps: int, learn: bool) -> None:
-        if not hasattr(interface, 'seq'):
-            raise NotImplementedError('%s runs on a Sequence' % self._who)
-        assert interface.dim == self.dim, \
-            'the Sequence has observations of %d components, the agent %d' % (interface.dim, self.dim)
-        self._refuse(interface)
-        trials, steps = int(trials), int(steps)
-        assert steps >= 1, 'steps must be at least 1'
-        interface.plan_session(trials, steps)      # IndexError here, before any launch
-        interface._on_device()
-        self._bind_to(interface.n_envs, interface.device)
-        # (the reference's BinaryRescorlaWagner.test selects with `policy`, not `policy_test`:
-        #  agent/rw.py:359 — kept; `policy_test` is stored as there)
-        pol = self.policy
-        if pol is not None:
-            self._policy_in(pol, interface)
-        first = self.current_trial
-        self._reserve(first + trials)
-        self._sessions += 1
-        binary = pol is not None
-        per_step = self.n_envs == 1 and self.callbacks.has('on_step_begin', 'on_step_end')
-        per_trial = self.n_envs == 1 and (per_step or self.callbacks.has('on_trial_begin',
-                                                                         'on_trial_end'))
-        if not per_trial:
-            for t in range(trials):
-                self.callbacks.on_trial_begin({'trial_reward': 0.0, 'trial': first + t,
-                                               'trial_session': t})
-            self._launch(interface, pol, learn, first, trials, steps, 0)
-            interface.commit_session(trials, steps)
-            self.current_trial = first + trials
-            if self.callbacks.has('on_trial_end'):
-                rew = self.trial_reward_trace[:, first:first + trials].mean(dim=0).cpu().numpy()
-                lat = self.trial_steps_trace[:, first:first + trials].double().mean(dim=0).cpu().numpy()
-                for t in range(trials):
-                    self.callbacks.on_trial_end({
-                        'trial_reward': float(rew[t]), 'trial': first + t, 'trial_session': t,
-                        'steps': float(lat[t]), 'count': self.n_envs})
-            return
-        for t in range(trials):
-            logs = self.callbacks.on_trial_begin({'trial_reward': 0.0, 'trial': self.current_trial,
-                                                  'trial_session': t})
-            at = self.current_trial
-            if per_step:
-                step = 0
-                while True:
-                    logs['step'] = step
-                    logs = self.callbacks.on_step_begin(logs)
-                    self._launch(interface, pol, learn, at, 1, steps, 1)
-                    value, action, reward, end = self._step_row[0, 0].cpu().numpy()
-                    if self._trace is not None:
-                        n = int(self._trace_len[0].item())
-                        if n < self._trace.shape[1]:
-                            self._trace[0, n] = self._step_row[0, 0]
-                            self._trace_len[0] = n + 1
-                    logs['trial_reward'] += float(reward)
-                    if binary:
-                        logs['action'] = int(action)
-                    logs = self.callbacks.on_step_end(logs)
-                    step += 1
-                    if end or step >= steps:
-                        break
-                logs['steps'] = step - 1
-            else:
-                self._launch(interface, pol, learn, at, 1, steps, 0)
-                logs['step'] = logs['steps'] = int(self.trial_steps_trace[0, at].item())
-                logs['trial_reward'] = float(self.trial_reward_trace[0, at].item())
-                if binary:
-                    logs['action'] = int(self.trial_action_trace[0, at].item())
-            interface.commit_session(1, steps)
-            self.current_trial += 1
-            logs = self.callbacks.on_trial_end(logs)
-            if self.stop:
-                break
+    def _trial_logs(self, interface, at: int, last_step: int) -> dict:
+        if self.policy is None:
+            return {}
+        return {'action': int(self.trial_action_trace[0, at].item())}
 
     # -- reference surface ------------------------------------------------------------------------
     def train(self, interface, trials: int, steps: int = 32) -> None:

@@ -160,30 +160,49 @@ class Sequence(Interface):
         return IndexError('list index out of range: %s of instance %d would read past the last of '
                           'the %d trials' % (what, instance, self.n_trials))
 
-    def plan_session(self, trials: int, steps: int):
-        """Where every instance stands after ``trials`` trials under the cap ``steps``:
-        (current_trial, current_step) as arrays.  ``IndexError`` if an instance would begin a
-        trial past its last one."""
+    def _walk(self, trials: int, steps: int):
+        """``trials`` trials under the cap ``steps``, walked once per (schedule, trial) the
+        instances stand in: per instance the trial it ends in, the step its last trial stopped at
+        (-1 for a session of no trials) and the steps it takes.  ``IndexError`` if an instance
+        would begin a trial past its last one."""
         keys = np.stack([self.schedule_of.astype(np.int64), self._h_trial], axis=1)
         uniq, inv = np.unique(keys, axis=0, return_inverse=True)
         inv = inv.reshape(-1)
-        out_t, out_s = np.empty(len(uniq), dtype=np.int64), np.empty(len(uniq), dtype=np.int64)
+        ends, stops, totals = (np.empty(len(uniq), dtype=np.int64) for _ in range(3))
         for u, (s, p) in enumerate(uniq):
-            step = None
+            step, total = -1, 0
             for _ in range(int(trials)):
                 if p >= self.n_trials:
                     raise self._past_the_end('a session of %d trials' % trials,
                                              int(np.flatnonzero(inv == u)[0]))
                 length = int(self._trial_len[s, p])
                 step = min(length, int(steps))
+                total += step
                 p += int(length <= steps)
-            out_t[u], out_s[u] = p, -1 if step is None else step
-        cur = np.where(out_s[inv] < 0, self._h_step, out_s[inv])
-        return out_t[inv], cur
+            ends[u], stops[u], totals[u] = p, step, total
+        return ends[inv], stops[inv], totals[inv]
+
+    def plan_session(self, trials: int, steps: int):
+        """Where every instance stands after ``trials`` trials under the cap ``steps``:
+        (current_trial, current_step) as arrays.  ``IndexError`` if an instance would begin a
+        trial past its last one."""
+        trial, step, _ = self._walk(trials, steps)
+        return trial, np.where(step < 0, self._h_step, step)
+
+    def session_steps(self, trials: int, steps: int) -> np.ndarray:
+        """Steps every instance takes in such a session: the schedule and the cap fix them."""
+        return self._walk(trials, steps)[2]
 
     def commit_session(self, trials: int, steps: int) -> None:
         """The mirror follows a session the device has run."""
         self._h_trial, self._h_step = self.plan_session(trials, steps)
+
+    def step_at(self, instance, step=0):
+        """(index into the step tables, length of the trial) of step ``step`` of the trial
+        ``instance`` stands in; ``instance`` is an index or whatever NumPy indexes with."""
+        s, p = self.schedule_of[instance], self._h_trial[instance]
+        return (self.tables['trial_off'][s, p] + step,
+                self._trial_len[s, np.minimum(p, self.n_trials - 1)])
 
     def _on_device(self) -> None:
         if self.device.type != 'cuda':
@@ -210,13 +229,12 @@ class Sequence(Interface):
     def step(self, action):
         self._on_device()
         N, A = self.n_envs, int(self.action_space.n)
-        length = self._trial_len[self.schedule_of, np.minimum(self._h_trial, self.n_trials - 1)]
+        at, length = self.step_at(slice(None), self._h_step)
         bad = (self._h_trial >= self.n_trials) | (self._h_step >= length)
         if bad.any():
             raise self._past_the_end('step()', int(np.flatnonzero(bad)[0]))
         # a step with an array reward indexes it with the action (sequence.py:165), unless it is
         # overwritten: out of range is the reference's IndexError, negative counts from the end
-        at = self.tables['trial_off'][self.schedule_of, self._h_trial] + self._h_step
         indexed = (self.tables['step_scalar'][at] == 0) & (not self.overwrite)
         if N == 1 and not torch.is_tensor(action):
             act = torch.full((1,), int(action), dtype=torch.int32, device=self.device)
