@@ -21,7 +21,11 @@
 //   * one Philox evaluation serves four steps, and the loop takes its steps in groups of four
 //     whose position in the block — which lane and word hold the policy's draw, which word the
 //     planning lanes' pair, where the next evaluation falls — is fixed at compile time (env_step,
-//     PH = 0 .. 3); single generic steps (PH = -1) fill in wherever a group does not fit.
+//     PH = 0 .. 3); single generic steps (PH = -1) fill in wherever a group does not fit;
+//   * where the NEXT trial starts is worked out when a trial begins and carried, inside a ticket,
+//     as three scalars (the state and its two world record words): a trial end sends the new
+//     trial's requests at once, reads its arguments in one scalar round trip, and waits neither
+//     for the start list nor for the monitor atomics (look for `begin_carried`).
 //
 // Waves that work on the caller's Q table where it lies, in global memory (QG; `ng` of them; L2
 // resident while the instance is in flight: 16 KiB), exist only for COBEL_F_PWG_GLOBAL and forced
@@ -114,8 +118,15 @@ __device__ __forceinline__ void pwg_stamp(uint32_t* stamps, uint32_t* prev, int 
   }
 }
 #define PWG_STAMP(k) pwg_stamp(stamps, stamp_prev, k, lane)
+// (a trial end: cycles and count in two words of the wave's own behind the eight of every wave)
+#define PWG_STAMP_TRIAL_END()                      \
+  do {                                             \
+    pwg_stamp(stamps_te, stamp_prev, 0, lane);     \
+    if (lane == 0) atomicAdd(stamps_te + 1, 1u);   \
+  } while (0)
 #else
 #define PWG_STAMP(k)
+#define PWG_STAMP_TRIAL_END()
 #endif
 
 // The kernel arguments as they lie in the kernarg segment, through a pointer the optimizer cannot
@@ -144,7 +155,7 @@ __device__ __forceinline__ void pwg_instance(const pwg_args& A, const int i, con
                                              unsigned char* const lds, const int lane,
                                              const uint64_t thr_mine, const uint32_t stripe
 #if defined(COBEL_PWG_STAMPS)
-                                             , uint32_t* stamps, uint32_t* stamp_prev
+                                             , uint32_t* stamps, uint32_t* stamp_prev, uint32_t* stamps_te
 #endif
                                              ) {
   const int S = A.S;
@@ -263,20 +274,63 @@ __device__ __forceinline__ void pwg_instance(const pwg_args& A, const int i, con
     cand = W4[succ_of(cw0, cw1)];   // (every lane: successor lane % 4; four distinct lines)
     mdig = *reinterpret_cast<const uint2*>(&Mg[(uint32_t)s * 4u]);
   };
-  auto begin_trial = [&]() -> bool {
+  // ---- the start of the NEXT trial, carried ahead ------------------------------------------------
+  // Where trial k + 1 starts depends on nothing trial k does: seed, instance, the ENV counter `ce`
+  // (which moves only when a trial begins) and the world's start list.  So it is worked out when
+  // trial k begins — the draw, starts[...], and that state's world record words — and carried as
+  // three wave-uniform scalars; a trial end takes state, cw0 and cw1 from them and sends the
+  // requests for `cand` and `mdig` at once, as after any other step.  The start list and the world
+  // record are read with SCALAR loads (lgkmcnt): no wait of this chain is a wait for the vector
+  // requests or the monitor atomics in flight (vmcnt).  Carried inside one ticket only: a ticket,
+  // a slice or a launch starts from the instance record and the world handle.  `ce` counts the
+  // trials BEGUN: a start carried and not used (trials_target) is drawn again by the next ticket.
+  typedef const __attribute__((address_space(4))) uint32_t* kwords;
+  uint32_t nx_state = 0u, nx_w0 = 0u, nx_w1 = 0u;
+  uint32_t start_lo, start_cnt;   // the world's part of the start list (the same for the whole ticket)
+  {
     const pwg_kargs R = rare_args();
-    if (trial >= R->r.trials_target) return false;
-    const int start_lo = R->start_off[world];
-    const uint32_t start_cnt = (uint32_t)(R->start_off[world + 1] - start_lo);
-    state = (int)R->starts[start_lo + (int)cobel_draw_bounded(ce, 0u, g, COBEL_STREAM_ENV, seed_now(),
-                                                              start_cnt)];
+    const kwords so = (kwords)R->start_off;
+    start_lo = so[world];
+    start_cnt = so[world + 1] - start_lo;
+  }
+  // One block of the ENV stream serves four trials (word ce & 3 of block ce >> 2): it is evaluated
+  // where a ticket starts and where ce enters a new block, and its four words are kept as scalars.
+  uint32_t eb0 = 0u, eb1 = 0u, eb2 = 0u, eb3 = 0u;
+  // entry of the start list at which the trial with ENV counter c starts (no memory access);
+  // `fresh`: the block kept is not c's (c is taken one after another inside a ticket)
+  auto start_entry = [&](uint32_t c, bool fresh) -> uint32_t {
+    if (fresh || (c & 3u) == 0u) {
+      const cobel_u4 b = cobel_philox(c >> 2, 0u, g, COBEL_STREAM_ENV, seed_now());
+      eb0 = rfl(b.x);
+      eb1 = rfl(b.y);
+      eb2 = rfl(b.z);
+      eb3 = rfl(b.w);
+    }
+    const uint32_t lo = (c & 1u) ? eb1 : eb0, hi = (c & 1u) ? eb3 : eb2;
+    return start_lo + cobel_bounded((c & 2u) ? hi : lo, start_cnt);
+  };
+  // (uint16 entry e of the list as half of an aligned word: there is no scalar load of 16 bits)
+  auto start_word = [&](const uint16_t* starts, uint32_t e) -> uint32_t {
+    return ((kwords)starts)[e >> 1];
+  };
+  auto carry_start = [&](uint32_t e, uint32_t w) {
+    nx_state = (e & 1u) ? w >> 16 : w & 0xffffu;
+    const kwords c = (kwords)(W4 + nx_state);
+    nx_w0 = c[0];
+    nx_w1 = c[1];
+  };
+  // the trial carried ahead begins: its requests go out first, nothing is waited for
+  auto begin_carried = [&]() {
+    state = (int)nx_state;
+    cw0 = nx_w0;
+    cw1 = nx_w1;
+    cand = W4[succ_of(cw0, cw1)];   // (every lane: successor lane % 4; four distinct lines)
+    mdig = *reinterpret_cast<const uint2*>(&Mg[nx_state * 4u]);
     ce += 1u;
     step = 0;
     trew = 0.0;
     asm volatile("" : "+v"(trew));
     iflags |= 1u;
-    enter_state(state);
-    return true;
   };
   // the float64 planning update (NumPy promotion of dyna_q.py:290-299 with a float32 table)
   auto plan_td = [&](float q, float m, float r, uint32_t nt) -> float {
@@ -445,8 +499,25 @@ __device__ __forceinline__ void pwg_instance(const pwg_args& A, const int i, con
     warm = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(Mg) + (off < last ? off : last));
   }
   bool live = true;
-  if (iflags & 1u) enter_state(state);
-  else live = begin_trial();
+  {
+    const pwg_kargs R = rare_args();
+    const uint16_t* const starts = R->starts;
+    bool fresh = true;
+    if (iflags & 1u) {
+      enter_state(state);
+    } else if (trial >= R->r.trials_target) {
+      live = false;
+    } else {
+      const uint32_t e = start_entry(ce, true);
+      carry_start(e, start_word(starts, e));
+      begin_carried();
+      fresh = false;
+    }
+    if (live) {
+      const uint32_t e = start_entry(ce, fresh);
+      carry_start(e, start_word(starts, e));
+    }
+  }
   refresh_draws(cp >> 2, (cm + 1u) >> 2);
   refresh_in = steps_to_refresh();
   idx_cur = lane < B ? cobel_bounded(draw_m(cm), SA) : 0u;
@@ -602,7 +673,7 @@ __device__ __forceinline__ void pwg_instance(const pwg_args& A, const int i, con
       R = __builtin_bit_cast(float, rfl(model32[2u * sa]));
     }
     __builtin_amdgcn_sched_barrier(0);
-    // (unconditional: at a trial's end the two requests are wasted — begin_trial asks again — but a
+    // (unconditional: at a trial's end the two requests are wasted — begin_carried asks again — but a
     //  request under a condition merges with the old value, and the merge is a copy behind a wait
     //  for the answer, a memory round trip per step of the global-memory waves: 25.7 -> 32 ms per
     //  launch of those alone in one build of round 6)
@@ -735,21 +806,45 @@ __device__ __forceinline__ void pwg_instance(const pwg_args& A, const int i, con
     }
 
     if (__builtin_expect(trial_over, 0)) {
+      PWG_STAMP(2);   // steps (up to this trial end)
       // agent/dyna_q.py:207-212: current_trial += 1; logs['steps'] = step (0-based)
+      // Everything the block reads through rare_args() is requested before the first of it is
+      // waited for (ONE scalar round trip); then the new trial's vector requests, then the monitor
+      // updates behind them — nothing in the block consumes a vector result, so nothing here waits
+      // for the atomics — and last the start of the trial after the new one (scalar loads).
       const pwg_kargs R = rare_args();
 #define rr (R->r)
-      if (lane == 0 && trial >= 0 && trial < rr.trial_cap) {
-        const size_t mo = (size_t)stripe * (size_t)rr.trial_cap + (size_t)trial;
-        if (rr.lat_sum) atomicAdd(rr.lat_sum + mo, (unsigned long long)step);
-        if (rr.lat_cnt) atomicAdd(rr.lat_cnt + mo, 1ull);
-        if (rr.reward_sum) atomicAdd(rr.reward_sum + mo, trew);
-        if (rr.resp_cnt && trew > 0.0) atomicAdd(rr.resp_cnt + mo, 1ull);
-        if (rr.lat_trace) rr.lat_trace[(size_t)i * rr.trial_cap + trial] = step;
-      }
+      const int trial_cap = rr.trial_cap, trials_target = rr.trials_target;
+      unsigned long long* const lat_sum = rr.lat_sum;
+      unsigned long long* const lat_cnt = rr.lat_cnt;
+      double* const reward_sum = rr.reward_sum;
+      unsigned long long* const resp_cnt = rr.resp_cnt;
+      int32_t* const lat_trace = rr.lat_trace;
+      const uint16_t* const starts = R->starts;
+      // (the entry of the trial after the new one, while the arguments travel: ce + 1 is the new
+      //  trial's counter once it has begun)
+      const uint32_t e_next = start_entry(ce + 1u, false);
+      asm volatile("" ::"s"(trial_cap), "s"(trials_target), "s"(lat_sum), "s"(lat_cnt), "s"(reward_sum),
+                   "s"(resp_cnt), "s"(lat_trace), "s"(starts), "s"(e_next));
+      const uint32_t w_next = start_word(starts, e_next);
 #undef rr
+      const int step_done = step, trial_done = trial;
+      const double trew_done = trew;
       trial += 1;
       iflags &= ~1u;
-      if (!begin_trial()) break;
+      const bool more = trial < trials_target;
+      if (more) begin_carried();
+      if (lane == 0 && trial_done >= 0 && trial_done < trial_cap) {
+        const size_t mo = (size_t)stripe * (size_t)trial_cap + (size_t)trial_done;
+        if (lat_sum) atomicAdd(lat_sum + mo, (unsigned long long)step_done);
+        if (lat_cnt) atomicAdd(lat_cnt + mo, 1ull);
+        if (reward_sum) atomicAdd(reward_sum + mo, trew_done);
+        if (resp_cnt && trew_done > 0.0) atomicAdd(resp_cnt + mo, 1ull);
+        if (lat_trace) lat_trace[(size_t)i * trial_cap + trial_done] = step_done;
+      }
+      if (!more) break;
+      carry_start(e_next, w_next);
+      PWG_STAMP_TRIAL_END();
     } else {
       step += 1;
     }
@@ -838,6 +933,8 @@ __global__ __launch_bounds__(1024) void k_tab_pwg(const pwg_args A) {
   //     CU drops its L1 (agent-scope acquire) before it reads.
 #if defined(COBEL_PWG_STAMPS)
   uint32_t* const stamps = A.ring + (size_t)8 * A.ring_stride + (size_t)wave_id * 8u;
+  uint32_t* const stamps_te = A.ring + (size_t)8 * A.ring_stride +
+                              (size_t)gridDim.x * (size_t)waves * 8u + (size_t)wave_id * 2u;
   uint32_t* const stamp_prev = reinterpret_cast<uint32_t*>(
       lds_raw + (size_t)A.nl * slice_l + (size_t)A.ng * kHashBytes + (size_t)wave * 8);
   if (lane == 0) {
@@ -970,8 +1067,8 @@ __global__ __launch_bounds__(1024) void k_tab_pwg(const pwg_args A) {
 #if defined(COBEL_PWG_STAMPS)
     PWG_STAMP(0);   // ticket
     if (lane == 0) atomicAdd(stamps + 4, 1u);
-    if (qg) pwg_instance<true, POW2>(A, i, budget, lds, lane, thr_mine, stripe, stamps, stamp_prev);
-    else pwg_instance<false, POW2>(A, i, budget, lds, lane, thr_mine, stripe, stamps, stamp_prev);
+    if (qg) pwg_instance<true, POW2>(A, i, budget, lds, lane, thr_mine, stripe, stamps, stamp_prev, stamps_te);
+    else pwg_instance<false, POW2>(A, i, budget, lds, lane, thr_mine, stripe, stamps, stamp_prev, stamps_te);
     PWG_STAMP(3);   // write-back issued
 #else
     if (qg) pwg_instance<true, POW2>(A, i, budget, lds, lane, thr_mine, stripe);
@@ -1186,7 +1283,10 @@ int cobel_tab_pwg_launch(const cobel_world* world, const cobel_tab_run_t& r,
   }
 #if defined(COBEL_PWG_STAMPS)
   lds += 1024;
-  COBEL_HIP_TRY(hipMemsetAsync(base, 0, (256 + (size_t)8 * A.ring_stride + (size_t)8 * grid * waves) * 4, st));
+  // (ten words per wave behind the rings: the timing build runs with a scratch area that holds them)
+  const size_t stamp_words = 256 + (size_t)8 * A.ring_stride + (size_t)10 * grid * waves;
+  if (!scratch || stamp_words * 4 > (size_t)r.scratch_bytes) return COBEL_E_ARG;
+  COBEL_HIP_TRY(hipMemsetAsync(base, 0, stamp_words * 4, st));
 #else
   // (the abort word — word 255 of a scratch area — is STICKY: no launch clears it, so a wave that
   //  gave up is reported by every later cobel_tab_scratch_check, whichever launches followed)

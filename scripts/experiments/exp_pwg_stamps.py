@@ -40,6 +40,19 @@ def main():
     off = 256 + 8 * ((n + 7) // 8) * (slices - 1)
     st = sc[off:off + grid * waves * 8].reshape(grid, waves, 8).astype(np.float64)
     nl = waves
+    # trial ends: cycles and count, two words per wave behind the eight of every wave (the `steps`
+    # figure below is then the steps WITHOUT their trial ends)
+    te = sc[off + grid * waves * 8:off + grid * waves * 10].reshape(grid, waves, 2).astype(np.float64)
+    if te[..., 1].sum():
+        tickets = st[..., 4].sum()
+        print('trial ends: %.2f per ticket, %.0f cycles each, %.0f cycles per ticket = %.2f %% of a ticket\'s '
+              'cycles (%.2f %% of its step loop)'
+              % (te[..., 1].sum() / tickets, te[..., 0].sum() / te[..., 1].sum(), te[..., 0].sum() / tickets,
+                 100 * te[..., 0].sum() / (st[..., :4].sum() + te[..., 0].sum()),
+                 100 * te[..., 0].sum() / (st[..., 2].sum() + te[..., 0].sum())))
+        with np.errstate(all='ignore'):
+            pw = te[..., 0].sum(axis=0) / te[..., 1].sum(axis=0)
+        print('cycles per trial end, by wave slot: ' + '  '.join('%d: %.0f' % (w, pw[w]) for w in range(waves)))
     print('launch %.3f ms, %d waves per workgroup' % (ms, waves))
     for name, sel in (('LDS waves', st[:, :nl]), ('global-memory waves', st[:, nl:])):
         if sel.size == 0:
