@@ -78,7 +78,8 @@ struct pwg_args {
   cobel_tab_run_t r;
   uint64_t thr[16][3];   // integer CDF thresholds of the epsilon-greedy tie patterns
   float alpha_f, gamma_f, model_lr_f;
-  int32_t nl, ng;        // waves per workgroup with Q in LDS / with Q in global memory
+  uint32_t store_always;   // 0, or 0x10000 (model_lr_f is not finite): every step stores its model record
+  int32_t nl, ng;       // waves per workgroup with Q in LDS / with Q in global memory
   // tickets (all counters zeroed before the launch)
   uint32_t* queue;       // eight heads, 32 B apart: word 0 = next (sliced) ticket of each queue, word 1 =
                          // next of its whole-instance tickets (sliced launches with `whole` > 0)
@@ -248,8 +249,8 @@ __device__ __forceinline__ void pwg_instance(const pwg_args& A, const int i, con
   cobel_u4 blk = {0, 0, 0, 0};
   int refresh_in = 0;
   uint2 mdig = {0u, 0u};   // the four digest entries of the current state (requested a step ahead)
-  uint32_t fix_sa = ~0u;
-  float fix_r = 0.0f;
+  uint32_t fix_sa = ~0u;   // the pair this ticket last stored to ...
+  float fix_r = 0.0f;      // ... and its reward estimate
   uint32_t idx_cur = 0, mg_cur = 0;
 
   auto draw_m = [&](uint32_t counter) -> uint32_t {
@@ -648,10 +649,12 @@ __device__ __forceinline__ void pwg_instance(const pwg_args& A, const int i, con
     // add and selects in every step).  The reward total: `trew` starts a trial at +0.0, and a sum
     // rounded to nearest that starts there is never -0.0, so adding r = +0.0f changes nothing;
     // -0.0f has bits and is added.
+    uint32_t never = A.store_always;   // (bit 16 where this step's model store cannot be skipped: below)
     if (__builtin_expect(r_bits != 0u, 0)) {
       iflags |= 2u;
       trew += (double)r;
       asm volatile("" : "+v"(trew));
+      never = 0x10000u;
     }
     const uint32_t end = rl(cand.w, a);
     const float ns_max = __builtin_bit_cast(float, rl(fbits(smax), a));
@@ -663,15 +666,36 @@ __device__ __forceinline__ void pwg_instance(const pwg_args& A, const int i, con
     const bool trial_over = end || ((int)rfl((uint32_t)step) + 1 >= A.r.steps_per_trial);
     // (everything the previous step requested is consumed BEFORE this step's requests go out: the
     //  wait for a register loaded across the loop edge is a wait for every load in flight)
-    // The reward estimate of (state, a): +0.0f unless its digest entry is flagged — then, rarely
-    // (pairs that lead into a rewarded state), it is fetched from the packed record.  The model
-    // records themselves are never read otherwise: their lines stay out of the L2.
+    // ---- model store (memory/dyna_q.py:92-96) ---------------------------------------------------------
+    // A step that relearns what the model holds stores nothing.  `m_skip` is the digest entry this
+    // step would write for a reward estimate of +0.0f; the pair's entry `dold` is in hand, a scalar.
+    // If they are equal and r = +0.0f, then R = +0.0f, d = +0.0f and Rn = R + mlr * d = +0.0f for
+    // every finite mlr: the record and the entry would be written with the bits memory has (the
+    // digest mirrors the record: k_model_index, rebuild_index()).  ONE compare decides it: bit 16
+    // of `m_skip`, which no entry has, is set where the step must store all the same —
+    //   * a reward with bits (`never`, set in the rewarded steps' block above);
+    //   * a model_lr that is not finite (`store_always`, from the launcher): inf * 0 is NaN —
+    // and a flagged entry (R != +0.0f) differs from every `m_skip` in bit 15.
+    // `dold` may be one store old: the step's requests go out in front of the store, so a store
+    // that leaves the state where it was (a bump) is passed by the request for that state's
+    // entries, and one into a terminal state whose trial restarts in the state just left has
+    // begin_carried's request right behind it.  No guard is needed.  Within a ticket the world
+    // does not change, so the same pair has the same `m_skip` again; the store in flight happened
+    // because the old entry differed from it (it still differs: the step stores) or because of
+    // bit 16 (set again: it stores).  A step that stores takes the estimate of the pair LAST
+    // STORED to, however long ago, from `fix_r` — its record may still be on its way, and a
+    // skipped step changes no record —, of a flagged pair from the packed record (never read
+    // otherwise: the records' lines stay out of the L2), and +0.0f else.  A skipped step leaves
+    // `fresh_m` = `dold` and `fresh_r` = +0.0f for the planning patches: what it would have written.
+    // The estimate and the new entry stay in vector registers, as where every step stored: as
+    // scalars (a v_readfirstlane behind the arithmetic) agents with fresh tables, which store in
+    // many steps, were slower than with a store in every step.
+    // (forms and measurements: scripts/experiments/pwg_model_store/)
+    const uint32_t m_new = (uint32_t)ns | (nt << 14);
+    uint32_t m_skip = m_new | never;
+    asm volatile("" : "+s"(m_skip));
     const uint32_t dpair = rfl((a & 2) ? mdig.y : mdig.x);
     const uint32_t dold = (a & 1) ? (dpair >> 16) : (dpair & 0xffffu);
-    float R = 0.0f;
-    if (__builtin_expect((dold & 0x8000u) != 0u, 0)) {
-      R = __builtin_bit_cast(float, rfl(model32[2u * sa]));
-    }
     __builtin_amdgcn_sched_barrier(0);
     // (unconditional: at a trial's end the two requests are wasted — begin_carried asks again — but a
     //  request under a condition merges with the old value, and the merge is a copy behind a wait
@@ -680,15 +704,27 @@ __device__ __forceinline__ void pwg_instance(const pwg_args& A, const int i, con
     cand = W4[succ_of(nw0, nw1)];
     const uint2 mdig_next = *reinterpret_cast<const uint2*>(&Mg[(uint32_t)ns * 4u]);
 
-    // ---- model store (memory/dyna_q.py:92-96) and online TD (agent/dyna_q.py:290-299), float32 ------
-    if (sa == fix_sa) R = fix_r;
-    const float d = r - R;
-    const float Rn = R + mlr_f * d;
     const uint32_t fresh_idx = sa;
-    const float fresh_r = Rn;
-    const uint32_t fresh_m = (uint32_t)ns | (nt << 14) | (fbits(Rn) ? 0x8000u : 0u);
-    fix_sa = sa;
-    fix_r = Rn;
+    uint32_t fresh_m = dold;   // (what a skipped step would have written: the planning patches select from them)
+    float fresh_r = 0.0f;
+    if (__builtin_expect(dold != m_skip, 0)) {
+      uint32_t Rb = 0u;
+      if ((dold & 0x8000u) != 0u) Rb = rfl(model32[2u * sa]);
+      float R = __builtin_bit_cast(float, Rb);
+      if (sa == fix_sa) R = fix_r;
+      const float d = r - R;
+      const float Rn = R + mlr_f * d;
+      fresh_r = Rn;
+      fresh_m = m_new | (fbits(Rn) ? 0x8000u : 0u);
+      if (lane == 0) {
+        NT_ST(cobel_model_pack(Rn, (uint32_t)ns, nt), &model[sa]);
+        Mg[sa] = (uint16_t)fresh_m;
+      }
+      fix_r = Rn;
+      fix_sa = sa;
+      asm volatile("" : "+v"(fresh_r));
+    }
+    // ---- online TD (agent/dyna_q.py:290-299), float32 ---------------------------------------------------
     const float q_sa = __builtin_bit_cast(float, rl(fbits(qc), a));
     const float gnt = nt ? gamma_f : 0.0f;
     float td = r + gnt * ns_max;
@@ -697,8 +733,6 @@ __device__ __forceinline__ void pwg_instance(const pwg_args& A, const int i, con
     if (lane == 0) {
       if (QG) Qgf[sa] = qn_online;
       else Qf[sa] = qn_online;
-      NT_ST(cobel_model_pack(fresh_r, (uint32_t)ns, nt), &model[sa]);
-      Mg[sa] = (uint16_t)fresh_m;
     }
     __builtin_amdgcn_wave_barrier();
 
@@ -1247,6 +1281,7 @@ int cobel_tab_pwg_launch(const cobel_world* world, const cobel_tab_run_t& r,
   A.alpha_f = (float)r.alpha;
   A.gamma_f = (float)r.gamma;
   A.model_lr_f = (float)r.model_lr;
+  A.store_always = (A.model_lr_f - A.model_lr_f == 0.0f) ? 0u : 0x10000u;   // (inf - inf and NaN - NaN are NaN)
   A.nl = nl;
   A.ng = ng;
   int n_cu = 0;
