@@ -138,6 +138,21 @@ class MLPFit(C.Structure):
     ]
 
 
+class MLPActivity(C.Structure):
+    """``cobel_mlp_activity_t``."""
+    _fields_ = [
+        ('w', C.c_void_p * 3), ('b', C.c_void_p * 3), ('probes', C.c_void_p),
+        ('units', C.c_void_p), ('out', C.c_void_p),
+        ('n', C.c_int32), ('n_probes', C.c_int32), ('n_inputs', C.c_int32),
+        ('n_outputs', C.c_int32), ('is_float64', C.c_int32),
+        ('layer', C.c_int32), ('hidden_activation', C.c_int32), ('apply', C.c_int32),
+        ('n_units', C.c_int32), ('probes_per_instance', C.c_int32),
+    ]
+
+
+APPLY_NONE, APPLY_RELU, APPLY_TANH = 0, 1, 2    # cobel_mlp_activity_t.apply (COBEL_APPLY_*)
+
+
 class DSRTargets(C.Structure):
     """``cobel_dsr_targets_t``."""
     _fields_ = [
@@ -570,6 +585,13 @@ _SIGNATURES['cobel_dqn_act'] = (C.c_int, [_P, C.POINTER(DQNAct), _P])
 _SIGNATURES['cobel_mlp_query'] = (C.c_int, [C.c_int32] * 6 + [C.POINTER(C.c_int32)])
 _SIGNATURES['cobel_mlp_forward'] = (C.c_int, [C.POINTER(MLPForward), _P])
 _SIGNATURES['cobel_mlp_fit'] = (C.c_int, [C.POINTER(MLPFit), _P])
+_SIGNATURES['cobel_mlp_activity'] = (C.c_int, [C.POINTER(MLPActivity), _P])
+_SIGNATURES['cobel_activity_process'] = (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32,
+                                                   C.c_double, _P])
+_SIGNATURES['cobel_place_fields_plan'] = (C.c_int, [C.c_int32, C.c_int32, C.c_int32,
+                                                    C.POINTER(C.c_int32 * 4)])
+_SIGNATURES['cobel_place_fields'] = (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                               C.c_double, C.c_double, _P, _P, _P, _P, _P, _P])
 _SIGNATURES['cobel_dsr_targets'] = (C.c_int, [C.POINTER(DSRTargets), _P])
 _SIGNATURES['cobel_c2d_plan'] = (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32 * 4)])
 _SIGNATURES['cobel_c2d_step'] = (C.c_int, [C.POINTER(C2D), _P, _P, _P, _P, _P])

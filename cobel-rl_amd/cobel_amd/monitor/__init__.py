@@ -1,2 +1,3 @@
 from .behavior import (EscapeLatencyMonitor, Monitor, QMonitor, ResponseMonitor,  # noqa: F401
                        RewardMonitor, TrajectoryMonitor)
+from .network import RepresentationMonitor  # noqa: F401

@@ -204,6 +204,7 @@ class StackedTorchNetwork:
                        for k, v in params.items()}
         self.buffers = {k: v.detach().expand(n, *v.shape[1:]).clone() for k, v in buffers.items()}
         self.criterion = copy.deepcopy(proto.criterion)
+        self.activations = copy.deepcopy(proto.activations)
         opt = proto.optimizer
         self.optimizer = type(opt)(list(self.params.values()), **{
             k: v for k, v in opt.defaults.items() if k not in ('foreach', 'fused', 'capturable',
@@ -484,6 +485,119 @@ class StackedTorchNetwork:
         run.eps, run.weight_decay, run.tau = float(group['eps']), float(group['weight_decay']), float(tau)
         _lib.check(_lib.lib().cobel_dqn_replay(C.byref(run), _lib.current_stream(self.device)))
         return True
+
+    # -- layer activity (libcobel_hip: cobel_mlp_activity) -----------------------------------------
+    def _activity_request(self, layer):
+        """``(key, fn)``: the child a ``get_layer_activity`` request names and the function the
+        reference would apply to its output, with the reference's rules and asserts
+        (network/network_torch.py:331-388) for ``activations`` as list or dict."""
+        children = list(self.base.named_children())
+        if isinstance(layer, str):
+            key = layer
+            index = next((i for i, (n, _) in enumerate(children) if n == layer), 10**10)
+        else:
+            key, index = children[int(layer)][0], int(layer)
+        if isinstance(self.activations, list):
+            assert len(self.activations) >= index, 'Index not in activation list!'
+            fn = self.activations[index]
+        else:
+            assert isinstance(self.activations, dict), \
+                'String layerkeys not compatible with activation lists!'
+            assert key in self.activations, 'Key not in activation dict!'
+            fn = self.activations[key]
+        return key, fn
+
+    def _activity_route(self, layer):
+        """``(k, apply, hidden)`` if the request is Linear ``k``'s output (0 .. 2) through ``apply``
+        (``_lib.APPLY_*``) of a network ``cobel_mlp_activity`` covers, ``hidden`` its own
+        activation; None if the PyTorch path has to serve it."""
+        from .. import _lib
+        key, fn = self._activity_request(layer)
+        kind = self._mlp3_activation() if self.fused_mlp else None
+        if kind is None:
+            return None
+        hidden, names = kind
+        w = [self.params[n + '.weight'] for n in names]
+        if _lib.lib().cobel_mlp_query(w[0].shape[2], w[0].shape[1], w[1].shape[1], w[2].shape[1],
+                                      32, int(w[0].dtype == torch.float64), None) != _lib.OK:
+            return None
+        functional = torch.nn.functional
+        if key in names:
+            if fn is None:
+                apply = _lib.APPLY_NONE
+            elif fn is torch.relu or fn is functional.relu or type(fn) is nn.ReLU:
+                apply = _lib.APPLY_RELU
+            elif fn is torch.tanh or fn is functional.tanh or type(fn) is nn.Tanh:
+                apply = _lib.APPLY_TANH
+            else:
+                return None
+            return names.index(key), apply, hidden
+        # the activation module right after a Linear layer of a Sequential: its output is the
+        # Linear layer's through that activation
+        children = list(self.base.named_children())
+        at = next((i for i, (n, _) in enumerate(children) if n == key), None)
+        if fn is None and at is not None and at > 0 and type(self.base) is nn.Sequential and \
+                children[at - 1][0] in names and type(children[at][1]) in (nn.ReLU, nn.Tanh):
+            apply = _lib.APPLY_RELU if type(children[at][1]) is nn.ReLU else _lib.APPLY_TANH
+            return names.index(children[at - 1][0]), apply, hidden
+        return None
+
+    def layer_activity_on_device(self, batch, layer, units=None) -> torch.Tensor:
+        """The activity ``[n, U, P]`` of one layer of every instance on the probe rows ``batch``
+        (``[P, D]`` shared by all instances, or ``[n, P, D]``), units-major as the reference's
+        ``get_layer_activity``; ``units`` (indices, any order, repeats allowed) selects rows.  One
+        kernel for the networks ``cobel_mlp_activity`` covers; anything else goes through a single
+        network per instance — the reference's exact semantics, slowly."""
+        from .. import _lib
+        route = self._activity_route(layer)
+        batch = torch.as_tensor(np.asarray(batch) if not torch.is_tensor(batch) else batch,
+                                device=self.device)
+        if route is not None:
+            k, apply, hidden = route
+            names = self._mlp3_activation()[1]
+            w = [self.params[n + '.weight'] for n in names]
+            D, O = int(w[0].shape[2]), int(w[2].shape[1])
+            if batch.dtype != w[0].dtype or batch.dim() not in (2, 3) or batch.shape[-1] != D or \
+                    batch.shape[-2] < 1 or (batch.dim() == 3 and batch.shape[0] != self.n):
+                route = None
+        if route is None:
+            return self._layer_activity_torch(batch, layer, units)
+        batch = batch.contiguous()
+        P = int(batch.shape[-2])
+        idx = None if units is None else torch.as_tensor(
+            np.asarray(units, dtype=np.int32).reshape(-1), device=self.device).contiguous()
+        rows = (O if k == 2 else int(w[0].shape[1])) if idx is None else int(idx.numel())
+        out = torch.empty((self.n, rows, P), dtype=w[0].dtype, device=self.device)
+        run = _lib.MLPActivity()
+        for i, n in enumerate(names):
+            run.w[i] = _lib.ptr(self.params[n + '.weight'].detach())
+            run.b[i] = _lib.ptr(self.params[n + '.bias'].detach())
+        run.probes, run.units, run.out = _lib.ptr(batch), _lib.ptr(idx), _lib.ptr(out)
+        run.n, run.n_probes, run.n_inputs, run.n_outputs = self.n, P, D, O
+        run.is_float64 = int(w[0].dtype == torch.float64)
+        run.layer, run.hidden_activation, run.apply = k, _lib.ACTIVATIONS[hidden], apply
+        run.n_units = 0 if idx is None else int(idx.numel())
+        run.probes_per_instance = int(batch.dim() == 3)
+        _lib.check(_lib.lib().cobel_mlp_activity(C.byref(run), _lib.current_stream(self.device)))
+        return out
+
+    def _layer_activity_torch(self, batch, layer, units) -> torch.Tensor:
+        if not hasattr(self, '_single'):
+            self._single = TorchNetwork(copy.deepcopy(self.base).to_empty(device=self.device),
+                                        activations=self.activations, device=str(self.device))
+        rows = []
+        for j in range(self.n):
+            self.write_back(self._single, j)
+            probes = batch if batch.dim() == 2 else batch[j]
+            rows.append(self._single.get_layer_activity(probes.cpu().numpy(), layer))
+        act = np.stack(rows)
+        if units is not None:
+            act = act[:, np.asarray(units).reshape(-1)]
+        return torch.as_tensor(act, device=self.device)
+
+    def get_layer_activity(self, batch, layer, units=None):
+        """``layer_activity_on_device`` as a NumPy array ``[n, U, P]``."""
+        return self.layer_activity_on_device(batch, layer, units).cpu().numpy()
 
     def make_capturable(self) -> None:
         """Prepare the optimizer for HIP-graph capture: its step counters move to the device

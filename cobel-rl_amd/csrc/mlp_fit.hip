@@ -1283,3 +1283,167 @@ extern "C" int cobel_dqn_replay(const cobel_dqn_replay_t* run, void* stream) {
   COBEL_HIP_TRY(hipGetLastError());
   return COBEL_OK;
 }
+
+// ---------------------------------------------------------------------------------------------
+// cobel_mlp_activity: the activity of ONE layer of every network of a stack on P probe rows
+// (TorchNetwork.get_layer_activity, network/network_torch.py:331-388), written units-major
+// [n][units][P].  One workgroup of four waves per network, as the forward kernel: wave w owns the
+// neurons 16 w .. of a hidden layer for both row tiles, and one of the (up to) four output tiles.
+// The probe rows go through in tiles of 32; the weight operands are requested once and stay in
+// registers across the tiles.  The chosen layer's Linear output goes through `apply` instead of the
+// network's own activation and stays in LDS ([32][66]: h1, h2, or the outputs where h1 was), from
+// where the tile's rows of the chosen units are written out, 32 consecutive probes per unit.
+namespace {
+
+struct activity_args {
+  cobel_mlp_activity_t r;
+  int32_t n_rows;   // rows of out per network: n_units, or the layer's width
+};
+
+template <typename T>
+__device__ __forceinline__ T activity_act(T pre, int act) {   // COBEL_APPLY_*
+  if (act == COBEL_APPLY_TANH) return hidden_act<1>(pre);
+  if (act == COBEL_APPLY_RELU) return hidden_act<0>(pre);
+  return pre;
+}
+
+// dense_relu for both row tiles with the activation chosen at run time (uniform)
+template <typename T, int KS>
+__device__ __forceinline__ void activity_dense(const weight_op<T, KS>& w, const T* in, int IS,
+                                               T* out, int n0, int lane, int act) {
+  typedef typename mfma_acc<T>::type acc_t;
+  const int li = lane & 15, lq = lane >> 4;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    acc_t acc = splat<T>(w.bias);
+    const T* const ar = in + (16 * i + li) * IS + lq * KS;
+#pragma unroll
+    for (int s = 0; s < KS; ++s) acc = mfma(ar[s], w.b[s], acc);
+#pragma unroll
+    for (int v = 0; v < 4; ++v)
+      out[(16 * i + mfma_acc<T>::row(lane, v)) * kRow + n0 + li] = activity_act(acc[v], act);
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_mlp_activity(const activity_args A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+  const cobel_mlp_activity_t& R = A.r;
+  const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int D = R.n_inputs, O = R.n_outputs, P = R.n_probes, layer = R.layer;
+  const size_t j = blockIdx.x;
+  T* const h1 = reinterpret_cast<T*>(lds_raw);   // [32][66]; layer 2: the outputs end up here
+  T* const h2 = h1 + kB * kRow;                  // [32][66]; before that the inputs x [32][33]
+  T* const x = h2;
+  const int hidden = R.hidden_activation == COBEL_ACT_TANH ? COBEL_APPLY_TANH : COBEL_APPLY_RELU;
+  const int m3 = 16 * (wave >> 1), n3 = 16 * (wave & 1);
+  const weight_op<T, 8> o1 = weight_rows<T, 8, false, true>(
+      (const T*)R.w[0] + j * (size_t)kH * D, (const T*)R.b[0] + j * kH, D, D, kH, 16 * wave, lane);
+  weight_op<T, 16> o2, o3;
+  if (layer >= 1)
+    o2 = weight_rows<T, 16, true, true>((const T*)R.w[1] + j * (size_t)kH * kH,
+                                        (const T*)R.b[1] + j * kH, kH, kH, kH, 16 * wave, lane);
+  if (layer == 2)
+    o3 = weight_rows<T, 16, true, true>((const T*)R.w[2] + j * (size_t)O * kH,
+                                        (const T*)R.b[2] + j * O, kH, kH, O, n3, lane);
+  const T* const probes = (const T*)R.probes + (R.probes_per_instance ? j * (size_t)P * D : 0);
+  const T* const src = layer == 1 ? h2 : h1;
+  const int K = A.n_rows;
+  T* const out = (T*)R.out + j * (size_t)K * (size_t)P;
+  for (int p0 = 0; p0 < P; p0 += kB) {
+    // the tile's rows into x [32][33], columns >= D zero; rows beyond P repeat the last one (they
+    // are computed and not written)
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int e = t + 256 * u, row = e >> 5, d = e & 31;
+      const int p = p0 + row < P ? p0 + row : P - 1;
+      const T v = probes[(size_t)p * D + (d < D ? d : D - 1)];
+      x[row * kXRow + d] = d < D ? v : (T)0;
+    }
+    lds_barrier();
+    activity_dense<T, 8>(o1, x, kXRow, h1, 16 * wave, lane, layer == 0 ? R.apply : hidden);
+    lds_barrier();   // (every read of x is done: h2 takes its place)
+    if (layer >= 1) {
+      activity_dense<T, 16>(o2, h1, kRow, h2, 16 * wave, lane, layer == 1 ? R.apply : hidden);
+      lds_barrier();   // (every read of h1 is done: the outputs take its place)
+    }
+    if (layer == 2) {
+      if (n3 < O) {
+        const typename mfma_acc<T>::type acc = output_tile<T>(o3, h2, m3, lane);
+        if (n3 + (lane & 15) < O) {
+#pragma unroll
+          for (int v = 0; v < 4; ++v)
+            h1[(m3 + mfma_acc<T>::row(lane, v)) * kRow + n3 + (lane & 15)] =
+                activity_act(acc[v], R.apply);
+        }
+      }
+      lds_barrier();
+    }
+    // rows of the chosen units: thread (k % 8, p) writes probe p0 + p of output row k
+    const int p = t & 31;
+    if (p0 + p < P) {
+      for (int k = t >> 5; k < K; k += 8) {
+        const int unit = R.units ? R.units[k] : k;
+        out[(size_t)k * (size_t)P + p0 + p] = src[p * kRow + unit];
+      }
+    }
+    lds_barrier();   // (the next tile's inputs go where h2 is; its first layer where h1 is)
+  }
+}
+
+}  // namespace
+
+extern "C" int cobel_mlp_activity(const cobel_mlp_activity_t* run, void* stream) {
+  COBEL_REQUIRE(run, COBEL_E_ARG, "cobel_mlp_activity: NULL run");
+  const cobel_mlp_activity_t& r = *run;
+  if (int rc = shape_ok(r.n_inputs, r.n_outputs, "cobel_mlp_activity")) return rc;
+  for (int l = 0; l < 3; ++l)
+    COBEL_REQUIRE(r.w[l] && r.b[l], COBEL_E_ARG, "cobel_mlp_activity: NULL parameters (layer %d)", l);
+  COBEL_REQUIRE(r.probes && r.out, COBEL_E_ARG, "cobel_mlp_activity: probes and out are required");
+  COBEL_REQUIRE(r.n >= 0 && r.n_probes >= 1, COBEL_E_RANGE,
+                "cobel_mlp_activity: bad sizes (n %d, %d probes)", r.n, r.n_probes);
+  COBEL_REQUIRE(r.layer >= 0 && r.layer <= 2, COBEL_E_RANGE,
+                "cobel_mlp_activity: layer = %d (0 .. 2)", r.layer);
+  COBEL_REQUIRE(r.apply == COBEL_APPLY_NONE || r.apply == COBEL_APPLY_RELU ||
+                    r.apply == COBEL_APPLY_TANH,
+                COBEL_E_RANGE, "cobel_mlp_activity: apply = %d (0 = none, 1 = ReLU, 2 = tanh)",
+                r.apply);
+  COBEL_REQUIRE(r.hidden_activation == COBEL_ACT_RELU || r.hidden_activation == COBEL_ACT_TANH,
+                COBEL_E_ARG, "cobel_mlp_activity: hidden_activation = %d (0 = ReLU, 1 = tanh)",
+                r.hidden_activation);
+  COBEL_REQUIRE(!r.units || r.n_units >= 1, COBEL_E_RANGE,
+                "cobel_mlp_activity: units given with n_units = %d", r.n_units);
+  COBEL_REQUIRE(((uintptr_t)r.w[1] & 15u) == 0 && ((uintptr_t)r.w[2] & 15u) == 0, COBEL_E_ARG,
+                "cobel_mlp_activity: the 64-wide weight matrices must be 16-byte aligned");
+  if (r.n == 0) return COBEL_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const int width = r.layer == 2 ? r.n_outputs : kH;
+  if (r.units) {
+    // the unit numbers index LDS in the kernel: looked at here, before anything is launched
+    int32_t* const host = (int32_t*)malloc((size_t)r.n_units * sizeof(int32_t));
+    COBEL_REQUIRE(host, COBEL_E_ARG, "cobel_mlp_activity: out of host memory");
+    hipError_t e = hipMemcpyAsync(host, r.units, (size_t)r.n_units * sizeof(int32_t),
+                                  hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    int bad = -1;
+    if (e == hipSuccess)
+      for (int k = 0; k < r.n_units && bad < 0; ++k)
+        if (host[k] < 0 || host[k] >= width) bad = k;
+    const int unit = bad >= 0 ? host[bad] : 0;
+    free(host);
+    COBEL_HIP_TRY(e);
+    COBEL_REQUIRE(bad < 0, COBEL_E_RANGE,
+                  "cobel_mlp_activity: units[%d] = %d, layer %d has %d units", bad, unit, r.layer,
+                  width);
+  }
+  activity_args A;
+  A.r = r;
+  A.n_rows = r.units ? r.n_units : width;
+  const int32_t lds = (int32_t)(fwd_lds_elems() * (r.is_float64 ? 8 : 4));
+  if (r.is_float64)
+    hipLaunchKernelGGL(k_mlp_activity<double>, dim3(r.n), dim3(256), lds, st, A);
+  else
+    hipLaunchKernelGGL(k_mlp_activity<float>, dim3(r.n), dim3(256), lds, st, A);
+  COBEL_HIP_TRY(hipGetLastError());
+  return COBEL_OK;
+}

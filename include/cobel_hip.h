@@ -960,6 +960,69 @@ COBEL_API int cobel_mlp_query(int32_t n_inputs, int32_t n_hidden1, int32_t n_hid
 COBEL_API int cobel_mlp_forward(const cobel_mlp_forward_t* run, void* stream);
 COBEL_API int cobel_mlp_fit(const cobel_mlp_fit_t* run, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * TorchNetwork.get_layer_activity (network/network_torch.py:331-388) for a STACK of the networks
+ * cobel_mlp_forward serves: the activity of one layer of every network on n_probes probe rows,
+ * written units-major, out[j][k][p] = apply(Linear_layer(...)(probe p))[units[k]] — the reference's
+ * (units, batch) orientation.  A forward hook on an nn.Linear sees the layer's pre-activation and
+ * the reference then applies activations[layer]: `apply` is that function (COBEL_APPLY_*), while
+ * `hidden_activation` (COBEL_ACT_*) is what the network itself applies between its layers.
+ * layer 0 / 1 have 64 units, layer 2 has n_outputs.  units NULL: all of them in order; else
+ * n_units numbers in any order, repeats allowed (they are read back and checked before the launch:
+ * the call then waits for the stream).  n_probes is any positive number: the rows go through in
+ * tiles of 32 with the network's weights held in registers.  probes_per_instance 0: one [P][D]
+ * block for every network; 1: [n][P][D].  ReLU is pre > 0 ? pre : 0, as in the other kernels: a NaN
+ * pre-activation gives 0 where torch.relu gives NaN.
+ * COBEL_E_UNSUPPORTED for other shapes than cobel_mlp_forward's, COBEL_E_ARG for NULL tensors, an
+ * unknown hidden_activation or misaligned 64-wide matrices, COBEL_E_RANGE for layer, apply, sizes
+ * or a unit number out of range.  n == 0 returns COBEL_OK.
+ * ------------------------------------------------------------------------------------------ */
+enum { COBEL_APPLY_NONE = 0, COBEL_APPLY_RELU = 1, COBEL_APPLY_TANH = 2 };
+typedef struct {
+  const void* w[3];        /* [n][out][in], network dtype                          */
+  const void* b[3];        /* [n][out]                                             */
+  const void* probes;      /* [P][D] or [n][P][D], network dtype                   */
+  const int32_t* units;    /* [dev] [n_units] or NULL                              */
+  void* out;               /* [n][n_units or U][P], network dtype                  */
+  int32_t n, n_probes, n_inputs, n_outputs, is_float64;
+  int32_t layer;           /* 0, 1 or 2: which Linear                              */
+  int32_t hidden_activation; /* COBEL_ACT_RELU / COBEL_ACT_TANH                    */
+  int32_t apply;           /* COBEL_APPLY_*: on the chosen layer's Linear output   */
+  int32_t n_units, probes_per_instance;
+} cobel_mlp_activity_t;
+COBEL_API int cobel_mlp_activity(const cobel_mlp_activity_t* run, void* stream);
+
+/* process_activity_maps (analysis/network_spatial.py:45-67) on rows [n_rows][n_cols] in place, in
+ * the rows' dtype: x -= min(x); x /= max(x); x[x < (T)threshold] = 0, each row equal to NumPy's bit
+ * for bit.  NaN as NumPy: a row that holds one becomes all NaN, a constant row too (0 / 0). */
+COBEL_API int cobel_activity_process(void* rows /* [dev] */, int64_t n_rows, int32_t n_cols,
+                                     int32_t is_float64, double threshold, void* stream);
+
+/* classify_place_field with sigma = 0 (analysis/network_spatial.py:70-144) for n_maps maps of
+ * height x width cells (height width <= 4096) in one launch, one wavefront per map:
+ *   thr = (T)cutoff * max(a) (NaN propagates);  field = a < thr ? 0 : a
+ *   4-connected components of field > 0, ordered by their first cell in row-major order
+ *   (scipy.ndimage.label's numbering); largest = the first component of maximal BOUNDING-BOX area
+ *   error = 1 without a component, else 2 with more than 4, else 3 if
+ *           (double)area[largest] > size_threshold * (double)(height * width), else 0
+ * has_field[m] = error == 0; features[m] = the number of components; largest_area[m] = the box
+ * area of the largest (height * width without a component); fields[m] = field where the cell
+ * belongs to the largest component, else 0 — without a component the thresholded field itself, as
+ * the reference returns it.  COBEL_E_ARG for NULL tensors or cutoff / size_threshold outside
+ * (0, 1) (the reference's asserts), COBEL_E_RANGE for sizes < 1, COBEL_E_UNSUPPORTED beyond 4096
+ * cells.  cobel_place_fields_plan: out = {LDS bytes per workgroup, maps per workgroup, LDS bytes
+ * per map, threads per workgroup}. */
+COBEL_API int cobel_place_fields_plan(int32_t height, int32_t width, int32_t is_float64,
+                                      int32_t out[4]);
+COBEL_API int cobel_place_fields(const void* maps /* [dev] [n_maps][height * width] */,
+                                 int64_t n_maps, int32_t height, int32_t width, int32_t is_float64,
+                                 double cutoff, double size_threshold,
+                                 uint8_t* has_field /* [dev] [n_maps] */,
+                                 int32_t* error /* [dev] [n_maps] */,
+                                 int32_t* features /* [dev] [n_maps] */,
+                                 int32_t* largest_area /* [dev] [n_maps] */,
+                                 void* fields /* [dev] [n_maps][height * width] */, void* stream);
+
 /* The regression targets of DynaDSR.replay (agent/dyna_q.py:1079-1131) for all samples of all
  * agents in ONE launch — what sits between the two forward passes and the two fits of a step:
  *   best[s]   = argmax_a value[a][s]   (first maximum)      | use_dr: the mean over the actions
