@@ -6,8 +6,12 @@ estimates, the buffers, the latencies and predict_on_batch.
 
     python scripts/fuzz_mfec.py [first seed] [count]
 
+Seeds from 10^6 on draw from the top of the documented ranges instead: random graphs of 100 to
+1 024 nodes with 5 to 8 neighbours, capacities of 64 to 2 048, k up to 32, and lattice, one-hot or
+random features given to the agent as its feature table (exact ties; tests/mfec_limits_common.py).
+
 A world in which two nodes' few random features are allclose is refused by the agent; such a seed is
-left out and listed in ``REFUSED``.  tests/test_gpu_fuzz_agents.py runs a fixed slice.
+left out and listed in ``REFUSED``.  tests/test_gpu_fuzz_agents.py runs a fixed slice of each range.
 """
 from __future__ import annotations
 
@@ -25,7 +29,28 @@ SEED = 0xC0BE1
 REFUSED: list = []      # seeds whose world the agent refused (allclose features)
 
 
+WIDE = 1_000_000        # first seed of the second range
+
+
+def draw_wide_case(seed: int) -> dict:
+    rng = np.random.default_rng(seed)
+    size = (int(rng.integers(100, 1025)), int(rng.integers(5, 9)))
+    capacity = int(rng.choice([64, 65, 128, 300, 2048]))
+    k = int(rng.choice([1, 2, 3, 5, 10, 32]))
+    eps = float(rng.choice([0.1, 0.3, 0.6]))
+    trials, steps = int(rng.integers(20, 90)), int(rng.integers(20, 80))
+    n = int(rng.choice([1, 2, 65]))
+    pick, base = int(rng.integers(n)), int(rng.integers(0, 1000))
+    features = str(rng.choice(['lattice', 'onehot', 'random']))
+    goals = int(rng.integers(size[0] // 60 + 1, size[0] // 25 + 2))
+    return dict(seed=seed, kind='graph', size=size, capacity=capacity, k=k, eps=eps, trials=trials,
+                steps=steps, n=n, pick=pick, base=base, D={'lattice': 2, 'onehot': size[0]}.get(features, 16),
+                features=features, goals=goals)
+
+
 def draw_case(seed: int) -> dict:
+    if seed >= WIDE:
+        return draw_wide_case(seed)
     rng = np.random.default_rng(seed)
     kind = str(rng.choice(['track', 'grid', 'hex']))
     if kind == 'track':
@@ -48,6 +73,9 @@ def draw_case(seed: int) -> dict:
 def world_of(c: dict):
     """(nodes, starting nodes) of a case."""
     from cobel_amd.misc import topology_tools as tt
+    if c['kind'] == 'graph':
+        import mfec_limits_common as ml
+        return ml.random_graph(c['size'][0], c['size'][1], c['seed'], goals=c['goals'])
     if c['kind'] == 'track':
         return tt.linear_track(c['size'][0], c['size'][1], 1.0, 20, 'right')
     if c['kind'] == 'grid':
@@ -68,7 +96,11 @@ def tables_of(nodes, starts) -> dict:
 
 def features_of(c: dict, S: int) -> np.ndarray:
     """The agent's feature table: one-hot observations times the projection its generator draws
-    first (agent/mfec.py: ``rng.random((S, projection_size))``) — the projection's rows."""
+    first (agent/mfec.py: ``rng.random((S, projection_size))``) — the projection's rows.  The second
+    range names its table (``feature_table`` is overridden with it)."""
+    if c['kind'] == 'graph':
+        import mfec_limits_common as ml
+        return ml.features(c['features'], S, c['seed'])
     return np.dot(np.eye(S), np.random.default_rng(c['seed']).random((S, c['D'])))
 
 
@@ -78,18 +110,24 @@ def run_reference(c: dict):
     nodes, starts = world_of(c)
     tab = tables_of(nodes, starts)
     F = features_of(c, len(nodes))
-    tables = mc.pair_tables(F)
+    more = {}
+    if c['kind'] == 'graph':    # (forms shown equal to the plain ones in tests/test_host_mfec.py)
+        import mfec_limits_common as ml
+        tables, more = ml.tables(c['features'], len(nodes), c['seed'])[1], {'query': ml.tree_query}
+    else:
+        tables = mc.pair_tables(F)
     if (tables[1] & ~np.eye(len(nodes), dtype=bool)).any():
         return None, None, tab
     ref, rag = mc.run_restatement(tab, F, [c['base'] + c['pick'], c['trials'], c['steps'],
                                            c['capacity'], c['k'], 0, round(c['eps'] * 1e6)], SEED,
-                                  tables=tables)
+                                  tables=tables, **more)
     return ref, rag, tab
 
 
 def describe(c: dict) -> str:
     return ('seed %(seed)d: %(kind)s %(size)s cap=%(capacity)d k=%(k)d eps=%(eps)g trials=%(trials)d '
-            'steps=%(steps)d n=%(n)d pick=%(pick)d base=%(base)d D=%(D)d' % c)
+            'steps=%(steps)d n=%(n)d pick=%(pick)d base=%(base)d D=%(D)d' % c
+            + (' %(features)s goals=%(goals)d' % c if c['kind'] == 'graph' else ''))
 
 
 def run_case(c: dict) -> list:
@@ -101,11 +139,16 @@ def run_case(c: dict) -> list:
     from cobel_amd.spaces import Box
     nodes, starts = world_of(c)
     S, n, pick = len(nodes), c['n'], c['pick']
-    obs = {tuple(nodes[key]['pose']): o for key, o in zip(nodes, np.eye(S))}
-    env = Topology(nodes, starts, OfflineSimulator(obs, Box(0.0, 1.0, (S,))), n_envs=n, seed=SEED,
-                   instance_base=c['base'])
+    if c['kind'] == 'graph':    # pose observations; the feature table is the case's own
+        env = Topology(nodes, starts, n_envs=n, seed=SEED, instance_base=c['base'])
+    else:
+        obs = {tuple(nodes[key]['pose']): o for key, o in zip(nodes, np.eye(S))}
+        env = Topology(nodes, starts, OfflineSimulator(obs, Box(0.0, 1.0, (S,))), n_envs=n, seed=SEED,
+                       instance_base=c['base'])
     ag = MFEC(env.observation_space, env.action_space, EpsilonGreedy(c['eps']), capacity=c['capacity'],
               k=c['k'], projection_size=c['D'], rng=np.random.default_rng(c['seed']))
+    if c['kind'] == 'graph':
+        ag.feature_table = lambda interface: np.ascontiguousarray(features_of(c, S))
     ag.record_steps, ag.track_instances = c['trials'] * c['steps'], True
     ref, rag, tab = run_reference(c)
     try:

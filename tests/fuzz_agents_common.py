@@ -27,6 +27,9 @@ C2D_FALLBACK_SEED = 279
 C2D_WHEEL_SEEDS = range(1_000_000, 1_000_006)
 MFEC_SEEDS = range(0, 30)
 MFEC_REFUSED_CAP = 3            # of the 30
+# the second range of scripts/fuzz_mfec.py: 100 to 1 024 nodes, 5 to 8 actions, capacity up to 2 048
+MFEC_WIDE_FIRSTS = (1_000_000, 1_000_004, 1_000_008)
+MFEC_WIDE_CHUNK = 4
 WHEEL_LEFT_OUT_CAP = 0.05       # of the instance-steps of the wheel slice
 
 

@@ -139,11 +139,12 @@ class RefQEC:
         self.buffers = tuple(RefActionBuffer(capacity) for _ in range(nb_actions))
         self.k = k
         self.evicted = 0       # entries of a full buffer replaced by a newer one
+        self.query = tree_query     # (tests/mfec_limits_common.py puts its faster, equal form here)
 
     def find_state(self, b, s):
         if not b.ids:
             return None
-        i = tree_query(self.R[s, b.ids], 1)[0]
+        i = self.query(self.R[s, b.ids], 1)[0]
         return i if self.same[s, b.ids[i]] else None
 
     def estimate(self, s, a):
@@ -154,7 +155,7 @@ class RefQEC:
         if len(b) <= self.k:
             return 0.0
         value = 0.0
-        for j in tree_query(self.R[s, b.ids], self.k):
+        for j in self.query(self.R[s, b.ids], self.k):
             value += b.values[j]
         return value / max(self.k, 1)
 
@@ -274,14 +275,16 @@ def tables_of(Z, name):
     return {k: Z['%s/tab_%s' % (name, k)] for k in ('next', 'reward', 'terminal', 'starts')}
 
 
-def run_restatement(tab, F, cfg, seed, tables=None):
+def run_restatement(tab, F, cfg, seed, tables=None, query=None):
     """One recorded case on the restatement.  cfg: instance, trials, steps, capacity, k,
-    test_trials, epsilon (x 1e6)."""
+    test_trials, epsilon (x 1e6).  ``query``: a form of ``tree_query`` shown equal to it."""
     inst, trials, steps, capacity, k, test_trials, eps6 = [int(x) for x in cfg]
     env = RefGridworld(tab, TapeRNG(seed, inst, STREAM_ENV))
     A = np.asarray(tab['next']).shape[1]
     pol = RefEpsilonGreedy(eps6 / 1e6, TapeRNG(seed, inst, STREAM_POLICY))
     ag = RefMFEC(F, A, pol, capacity=capacity, k=k, tables=tables)
+    if query is not None:
+        ag.Q.query = query
     tr = new_trace()
     ag.train(env, trials, steps, trace=tr)
     if test_trials:

@@ -95,3 +95,14 @@ def test_random_mfec_runs_match_the_restatement():
     print('MFEC sweep: %d of %d seeds refused (allclose): %s'
           % (len(fz.REFUSED), len(fa.MFEC_SEEDS), fz.REFUSED))
     assert len(fz.REFUSED) <= fa.MFEC_REFUSED_CAP
+
+
+@pytest.mark.parametrize('first', fa.MFEC_WIDE_FIRSTS)
+def test_random_mfec_runs_at_the_top_of_the_range_match_the_restatement(first):
+    """scripts/fuzz_mfec.py, seeds from 10^6 on: random graphs of 100 to 1 024 nodes with 5 to 8
+    actions, capacities of 64 to 2 048, k up to 32, lattice, one-hot or random features; none of the
+    slice is refused (tests/test_host_fuzz_agents.py says what it contains)."""
+    import fuzz_mfec as fz
+    del fz.REFUSED[:]
+    _sweep(fz, range(first, first + fa.MFEC_WIDE_CHUNK))
+    assert not fz.REFUSED

@@ -178,3 +178,28 @@ def test_mfec_slice():
     assert any(c['capacity'] > 64 for c in kept) and any(c['k'] == 32 for c in kept)
     assert evicting >= 1
     assert {c['kind'] for c in kept} == {'track', 'grid', 'hex'}
+
+
+def test_mfec_wide_slice():
+    """The slice of the second range: nothing refused by the restatement, and what it reaches."""
+    import fuzz_mfec as fz
+    seeds = [s for first in fa.MFEC_WIDE_FIRSTS for s in range(first, first + fa.MFEC_WIDE_CHUNK)]
+    cases, evicting, longest = [], 0, 0
+    for s in seeds:
+        c = fz.draw_case(s)
+        ref, rag, _ = fz.run_reference(c)
+        assert ref is not None, fz.describe(c)
+        cases.append(c)
+        evicting += rag.Q.evicted > 0
+        longest = max(longest, int(ref['buf_len'].max()))
+        assert ref['ended'].any()
+    print('MFEC wide slice: %d cases evict, longest buffer %d' % (evicting, longest))
+    assert len(seeds) == 12 and min(seeds) >= fz.WIDE and evicting >= 3 and longest > 128
+    assert {c['size'][1] for c in cases} == {5, 6, 7, 8}
+    assert max(c['size'][0] for c in cases) > 1000 and min(c['size'][0] for c in cases) >= 100
+    assert {c['features'] for c in cases} == {'lattice', 'onehot', 'random'}
+    assert {c['capacity'] for c in cases} >= {64, 128, 300, 2048} and any(c['k'] == 32 for c in cases)
+    assert {c['n'] for c in cases} == {1, 2, 65}
+    # the first range draws what it always drew
+    assert fz.draw_case(7) == {'seed': 7, 'kind': 'hex', 'size': (4,), 'capacity': 65, 'k': 32, 'eps': 0.3,
+                               'trials': 31, 'steps': 50, 'n': 2, 'pick': 0, 'base': 300, 'D': 2}

@@ -183,3 +183,115 @@ def test_feature_table_from_a_model_is_one_prediction_per_node():
     ag = MFEC(Box(0.0, 1.0, (6,)), Discrete(4), EpsilonGreedy(0.1), model=Model())
     F = ag.feature_table(g)
     assert Model.calls == 10 and np.array_equal(F, np.tanh(g.pose * 0.1) + 1.0)
+
+
+# -- the helpers of the tests at the limits (tests/mfec_limits_common.py) -----------------------------
+def _limits():
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    if here not in sys.path:
+        sys.path.insert(0, here)
+    import mfec_common as mc
+    import mfec_limits_common as ml
+    return mc, ml
+
+
+@pytest.mark.parametrize('D', [1, 16, 256])
+def test_vectorised_pair_tables_equal_the_plain_ones(D):
+    """The inputs of test_pair_tables_equal_the_sequential_sum (tests/test_gpu_mfec.py): a duplicate
+    row, an allclose one, one just outside; and the three feature tables of the limit tests."""
+    mc, ml = _limits()
+    S = 37
+    rng = np.random.default_rng(D)
+    F = rng.random((S, D))
+    F[5] = F[4]
+    F[7] = F[6] * (1 + 9e-5) + 5e-7
+    F[9] = F[8] * (1 + 2e-4)
+    R, same = mc.pair_tables(F)
+    r, s = ml.pair_tables(F)
+    assert r.dtype == R.dtype and s.dtype == same.dtype
+    assert np.array_equal(r, R) and np.array_equal(s, same)
+    assert same[4, 5] and same[6, 7] and not same[8, 9]
+    for kind in ('random', 'lattice', 'onehot'):
+        F = ml.features(kind, 40, seed=D)
+        for got, want in zip(ml.pair_tables(F), mc.pair_tables(F)):
+            assert np.array_equal(got, want), kind
+        assert np.array_equal(ml.pair_tables(F)[1], np.eye(40, dtype=bool)), kind
+
+
+def test_fast_tree_query_equals_the_plain_one():
+    """Random distances, all tied, few distinct values, descending (every entry enters the heap) and
+    lengths around the block: the same indices in the same order."""
+    mc, ml = _limits()
+    rng = np.random.default_rng(5)
+    cases = 0
+    for n in (1, 2, 3, 33, 127, 128, 129, 300, 700):
+        rows = [rng.random(n), np.full(n, 2.0), rng.integers(0, 4, n).astype(np.float64),
+                np.arange(n, 0, -1.0), np.where(rng.random(n) < 0.1, 0.0, 2.0),
+                np.full(n, np.inf)]
+        for dist in rows:
+            for k in (1, 2, 3, 4, 7, 32):
+                if k > n:
+                    continue
+                assert ml.tree_query(dist, k) == mc.tree_query(dist, k), (n, k)
+                assert ml.tree_query(dist, k, block=5) == mc.tree_query(dist, k), (n, k)
+                cases += 1
+    assert cases > 250
+
+
+def test_restatement_started_from_a_memory_continues_a_run():
+    """A run cut in two — the second half on a fresh RefMFEC loaded with the first half's buffers and
+    clock, the generators carried over — equals the uncut run; and the fast query changes nothing."""
+    mc, ml = _limits()
+    nodes, starts = ml.random_graph(50, 5, seed=3, goals=4)
+    tab = ml.tables_of(nodes, starts)
+    F = ml.features('lattice', 50)
+    tables = ml.pair_tables(F)
+    whole, env, pol = ml.restated(tab, F, tables, 5, 7, 11, 0.3, 9, 3)
+    whole.Q.query = mc.tree_query
+    tr = mc.new_trace()
+    whole.train(env, 30, 40, trace=tr)
+    assert whole.Q.evicted > 0 and max(len(b) for b in whole.Q.buffers) == 9
+    first, env, pol = ml.restated(tab, F, tables, 5, 7, 11, 0.3, 9, 3)
+    counts = ml.count_updates(first.Q)
+    tr2 = mc.new_trace()
+    first.train(env, 12, 40, trace=tr2)
+    second = mc.RefMFEC(F, 5, pol, capacity=9, k=3, tables=tables)
+    ml.load_memory(second, [(b.ids, b.values, b.times) for b in first.Q.buffers], first.clock)
+    counts2 = ml.count_updates(second.Q)
+    second.train(env, 18, 40, trace=tr2)
+    for key in ('sar', 'steps', 'ended', 'buf_len', 'buf_ids', 'buf_values', 'buf_times'):
+        assert tr[key] == tr2[key], key
+    assert all(np.array_equal(a, b) for a, b in zip(tr['q'], tr2['q']))
+    assert second.clock == whole.clock and env.rng.index == 1 + 30 and pol.rng.index == len(tr['sar'])
+    assert first.Q.evicted + second.Q.evicted == whole.Q.evicted == counts['replace'] + counts2['replace']
+    assert counts['append'] + counts2['append'] == sum(len(b) for b in whole.Q.buffers)
+    assert counts2['inplace'] > 0
+
+
+def test_built_buffers_hold_what_the_reference_can_produce():
+    mc, ml = _limits()
+    rng = np.random.default_rng(1)
+    for length, dups in ((1, None), (64, 0), (129, 40), (1000, 30), (2047, None), (2048, None)):
+        ids, values, times = ml.built_buffer(1024, length, rng, dups=dups)
+        assert len(ids) == len(values) == len(times) == length
+        rest = ids[ids != ids[0]]
+        assert len(np.unique(rest)) == len(rest) and ids.min() >= 0 and ids.max() < 1024
+        n_dup = int((ids == ids[0]).sum()) - 1
+        assert n_dup == (max(0, length - 1000) if dups is None else dups), (length, n_dup)
+
+
+def test_restated_environment_draws_successors_from_distribution_rows():
+    """One start integer per reset (sub-stream 0) and one double per step (sub-stream 1) of the same
+    ENV counter; the successor is the row's searchsorted(cdf, u, 'right')."""
+    mc, ml = _limits()
+    from oracle.philox import STREAM_ENV, draw_double
+    tab, sas = ml.drawn_world(40, 5, seed=2)
+    ag, env, pol = ml.restated(tab, ml.features('random', 40), None, 5, 3, 17, 0.5, 30, 3, drawn=True)
+    assert env.rng.index == 1
+    s = env.current_state
+    u = float(draw_double(17, 3, 1, 1, STREAM_ENV))
+    cdf = np.cumsum(sas[s, 2])
+    ns = env.step(2)[0]
+    assert ns == int(np.searchsorted(cdf / cdf[-1], u, side='right')) and env.rng.index == 2
+    assert (np.count_nonzero(sas, axis=2) > 1).sum() >= 40 and np.count_nonzero(sas, axis=2).max() == 3
