@@ -374,6 +374,30 @@ class RWRun(C.Structure):
     ]
 
 
+QSEQ_MAX_ACTIONS, QSEQ_MAX_KEYS, QSEQ_ROW = 8, 64, 6
+QSEQ_POLICY_SOFTMAX, QSEQ_POLICY_EPS_GREEDY = 0, 1
+
+
+class QSeqRun(C.Structure):
+    """``cobel_qseq_run_t``."""
+    _fields_ = [
+        ('Q', C.c_void_p), ('key_of_row', C.c_void_p), ('par', C.c_void_p), ('pol_ctr', C.c_void_p),
+        ('mem_ctr', C.c_void_p), ('log', C.c_void_p), ('log_len', C.c_void_p),
+        ('instance_ids', C.c_void_p), ('mid', C.c_void_p), ('trew', C.c_void_p),
+        ('trial_reward', C.c_void_p), ('trial_steps', C.c_void_p), ('trial_action', C.c_void_p),
+        ('trace', C.c_void_p), ('trace_len', C.c_void_p), ('last', C.c_void_p),
+        ('steps_done', C.c_void_p),
+        ('n', C.c_int32), ('n_keys', C.c_int32), ('n_actions', C.c_int32), ('log_cap', C.c_int32),
+        ('trial_cap', C.c_int32), ('trace_cap', C.c_int32), ('par_rows', C.c_int32),
+        ('policy', C.c_int32), ('batch_size', C.c_int32), ('reserved_', C.c_int32),
+        ('instance_base', C.c_uint32), ('flags', C.c_uint32),
+        ('pol_stream', C.c_uint32), ('reserved2_', C.c_uint32),
+        ('trial_first', C.c_int32), ('trials', C.c_int32), ('steps_per_trial', C.c_int32),
+        ('step_budget', C.c_int32),
+        ('seed', C.c_uint64),
+    ]
+
+
 ANET_MAX_ACTIONS = 9
 
 
@@ -567,6 +591,9 @@ _SIGNATURES = {
     'cobel_rw_predict': (C.c_int, [_P, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P]),
     'cobel_seq_step': (C.c_int, [C.POINTER(Seq), _P, _P, _P, _P, _P, _P]),
     'cobel_seq_reset': (C.c_int, [C.POINTER(Seq), _P, _P]),
+    'cobel_qseq_plan': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32 * 4)]),
+    'cobel_qseq_run': (C.c_int, [C.POINTER(Seq), C.POINTER(QSeqRun), _P]),
+    'cobel_softmax_n': (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P]),
     'cobel_anet_plan': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32 * 4)]),
     'cobel_anet_run': (C.c_int, [C.POINTER(Seq), C.POINTER(ANetRun), _P]),
     'cobel_anet_predict': (C.c_int, [C.POINTER(ANetRun), C.c_int32, _P, C.c_int32, _P, _P]),

@@ -665,6 +665,11 @@ class SequenceAgent(Agent):
     def _refuse(self, interface) -> None:
         """Raise for a Sequence this agent does not serve."""
 
+    def _acting_policy(self, learn: bool):
+        """The policy a session selects with: ``policy`` in test() too, as the reference's
+        Rescorla-Wagner and AssociativeNetwork agents (`policy_test` is stored only)."""
+        return self.policy
+
     def _open(self, interface, trials: int, steps: int, learn: bool) -> None:
         """The session opens: bound, traces reserved, nothing launched yet."""
 
@@ -702,7 +707,7 @@ class SequenceAgent(Agent):
         interface.plan_session(trials, steps)      # IndexError here, before any launch
         interface._on_device()
         self._bind_to(interface.n_envs, interface.device)
-        pol = self.policy      # (in test() too, as the reference's: `policy_test` is stored only)
+        pol = self._acting_policy(learn)
         if pol is not None:
             self._policy_in(pol, interface)
         first = self.current_trial

@@ -8,6 +8,14 @@ sized by each ``train`` call).  ``batch_size=0`` disables replay (demo/topology/
 experiences are logged all the same, as in the reference (``log_experiences = False`` skips that).
 Any action count up to 8 (a hexagonal ``Topology`` has six) and any ``batch_size``: runs outside
 what the wavefront kernels cover take the general kernel of ``cobel_tab_run``, same results.
+
+On a ``Sequence`` (Box observations) ``train`` / ``test`` run through ``QSequence`` (agent/q_seq.py)
+instead: Q keyed by the observation itself, float64, with a ``Softmax`` or an ``EpsilonGreedy``
+policy; ``learning_rate``, ``gamma`` and the policy's ``beta`` / ``epsilon`` may then be arrays of
+one value per instance.  ``Q_dict``, ``M``, ``predict_on_batch``, ``trial_reward_trace`` and
+``trial_steps_trace`` answer for that session; ``record_steps`` > 0 (set before the first session)
+keeps the rows (state key, action, reward, next key, non-terminal, td) of that many steps per
+instance for ``recorded_steps``.
 """
 from __future__ import annotations
 
@@ -45,6 +53,48 @@ class QAgent(TabularAgent):
         self.log_experiences = None
         self.log_budget_bytes = 4 << 30
         self._log_now = True
+        self._seq = None           # the QSequence helper, once a session ran on a Sequence
+        self.record_steps = 0
+
+    # -- on a Sequence ----------------------------------------------------------------------------
+    def _sequence(self):
+        if self._seq is None:
+            from .q_seq import QSequence
+            self._seq = QSequence(self)
+            self._seq.record_steps = self.record_steps
+        return self._seq
+
+    trial_reward_trace = property(
+        lambda self: None if self._seq is None else self._seq.trial_reward_trace)
+    trial_steps_trace = property(
+        lambda self: None if self._seq is None else self._seq.trial_steps_trace)
+
+    @property
+    def Q(self):
+        """On a Sequence the reference's dict for one instance (``Q_dict``), the device tensor
+        ``[n_envs, keys, A]`` when vectorised; else ``TabularAgent.Q``."""
+        seq = getattr(self, '_seq', None)
+        if seq is not None:
+            return seq.Q_dict if seq.n_envs == 1 else seq._q
+        return TabularAgent.Q.fget(self)
+
+    @Q.setter
+    def Q(self, value) -> None:
+        assert getattr(self, '_seq', None) is None, \
+            'Q of a QAgent on a Sequence is read through Q_dict'
+        TabularAgent.Q.fset(self, value)
+
+    def recorded_steps(self, instance: int = 0):
+        """The rows kept since ``record_steps`` was set (Sequence sessions)."""
+        return self._sequence().recorded_steps(instance)
+
+    def predict_on_batch(self, batch):
+        if self._seq is not None:
+            return self._seq.predict_on_batch(batch)
+        return super().predict_on_batch(batch)
+
+    def env_steps(self) -> int:
+        return self._seq.env_steps() if self._seq is not None else super().env_steps()
 
     def _log_words(self) -> int:
         """``COBEL_LOG_WORDS``: 64-bit words per logged experience (two where states and action
@@ -65,6 +115,8 @@ class QAgent(TabularAgent):
     @property
     def M(self):
         """Logged experiences of instance 0 as ``(state, action, reward, next_state, terminal)``."""
+        if self._seq is not None:     # (observation tuples as states, float64 rewards)
+            return self._seq.M
         if self._log is None:
             return []
         n = int(self.inst[0, _lib.I_LOG_LEN].item())
@@ -92,6 +144,8 @@ class QAgent(TabularAgent):
     @property
     def Q_dict(self) -> dict:
         """The reference's view of Q for instance 0: ``{observation tuple: float32[4]}``."""
+        if self._seq is not None:     # ({observation tuple: float64[A]}, keys as met)
+            return self._seq.Q_dict
         q = self._q[0].cpu().numpy() if self._q is not None else self._q_host
         if self._poses is not None:
             return {tuple(p.flatten()): q[i] for i, p in enumerate(self._poses)}
@@ -104,6 +158,8 @@ class QAgent(TabularAgent):
 
     def train(self, interface, trials: int, steps: int = 32, batch_size: int = 32) -> None:
         assert batch_size >= 0     # (above _lib.MAX_BATCH: passes of the wavefront kernels, any size)
+        if hasattr(interface, 'seq'):
+            return self._sequence().train(interface, trials, steps, batch_size)
         self._bind(interface)
         used = int(self.inst[:, _lib.I_LOG_LEN].max().item())
         need = (used + trials * steps) * 8 * self._log_words() * self.n_envs
@@ -122,4 +178,6 @@ class QAgent(TabularAgent):
         self._session(interface, trials, steps, batch_size, True)
 
     def test(self, interface, trials: int, steps: int = 32) -> None:
+        if hasattr(interface, 'seq'):
+            return self._sequence().test(interface, trials, steps)
         self._session(interface, trials, steps, 0, False)

@@ -1,3 +1,4 @@
 from .greedy import EpsilonGreedy  # noqa: F401
 from .policy import Policy  # noqa: F401
 from .scalar import Proportional, Sigmoid, Threshold  # noqa: F401
+from .softmax import Softmax  # noqa: F401

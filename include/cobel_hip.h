@@ -1563,6 +1563,95 @@ COBEL_API int cobel_adqn_step(const cobel_seq_t* seq, const cobel_adqn_mem_t* me
                               const cobel_adqn_step_t* run, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * QAgent (agent/q.py:26-354) on a Sequence, with a Softmax (policy/softmax.py:11-88) or an
+ * EpsilonGreedy policy.  Everything is float64, every operation rounded by itself.
+ *
+ * Keys.  The reference keys Q by tuple(observation.flatten()): observation rows of equal values
+ * share a Q row, and the zero observation a trial ends in (row 0 of obs_table) is a key too.  The
+ * host deduplicates the rows of obs_table by value into key_of_row [n_obs]; the kernel sees key
+ * indices only.  Q is [n][n_keys][n_actions].
+ *
+ * Log.  One 16-byte record per experience (QAgent.M): the reward and meta = state key |
+ * next key << 8 | action << 16 | non-terminal << 24.  log_len[i] persists between launches.
+ *
+ * Draws.  The policy takes one double per selection from pol_stream at pol_ctr[i]; a replay takes
+ * its batch_size indices as ONE integers(0, len(M), batch_size) of COBEL_STREAM_MEMORY at
+ * mem_ctr[i] (element j from sub-stream j; the counter moves by one per learning step, at
+ * batch_size 0 too, as TapeRNG.integers(size=0) does).
+ *
+ * Softmax selection (policy/softmax.py:77-86 and Generator.choice): e_a = exp((v_a - max v) beta),
+ * p_a = e_a / (((e_0 + e_1) + e_2) + ...), the cumulative sums in the same order, action =
+ * #{a < A - 1 : cum_a / cum_{A-1} <= u}.  Epsilon-greedy is cobel_eps_greedy_n_f64's.
+ *
+ * An instance takes a group of eight lanes, lane a holding the column of action a; its Q table
+ * stays in LDS for the launch.
+ * --------------------------------------------------------------------------------------------- */
+#define COBEL_QSEQ_MAX_ACTIONS 8
+#define COBEL_QSEQ_MAX_KEYS 64
+#define COBEL_QSEQ_POLICY_SOFTMAX 0     /* par[.][2] is beta                                      */
+#define COBEL_QSEQ_POLICY_EPS_GREEDY 1  /* par[.][2] is epsilon                                   */
+#define COBEL_QSEQ_ROW 6  /* doubles of a trace row: state key, action, reward, next key,
+                             non-terminal, td (0 without COBEL_F_LEARN; the td of the last update
+                             of the step's own experience, a replay in its batch included)        */
+
+typedef struct {
+  double reward;
+  uint32_t meta;              /* state key | next key << 8 | action << 16 | non-terminal << 24  */
+  uint32_t reserved_;
+} cobel_qseq_rec_t;
+
+typedef struct {
+  double* Q;                  /* [n][n_keys][n_actions]                                         */
+  const int32_t* key_of_row;  /* [seq->n_obs] key of every row of obs_table                     */
+  const double* par;          /* [par_rows][4] learning rate, gamma, beta or epsilon, unused    */
+  uint32_t* pol_ctr;          /* [n] draws taken from the policy's stream so far                */
+  uint32_t* mem_ctr;          /* [n] replay() calls so far (COBEL_STREAM_MEMORY); NULL allowed
+                                 without COBEL_F_LEARN                                          */
+  cobel_qseq_rec_t* log;      /* [n][log_cap]; NULL allowed without COBEL_F_LEARN               */
+  int32_t* log_len;           /* [n] records of the log; NULL iff log is                        */
+  const uint32_t* instance_ids; /* [n] stream instance numbers, or NULL: instance_base + i      */
+  int32_t* mid;               /* [n] 1: a trial is under way (step_budget ran out inside it)    */
+  double* trew;               /* [n] its reward so far                                          */
+  double* trial_reward;       /* [n][trial_cap] logs['trial_reward'] of every trial, or NULL    */
+  int32_t* trial_steps;       /* [n][trial_cap] logs['steps'] (index of its last step), or NULL */
+  int32_t* trial_action;      /* [n][trial_cap] its last action, or NULL                        */
+  double* trace;              /* [n][trace_cap][COBEL_QSEQ_ROW] every step, or NULL             */
+  int32_t* trace_len;         /* [n] rows of trace written so far (NULL iff trace is)           */
+  double* last;               /* [n][COBEL_QSEQ_ROW] the row of the launch's last step, or NULL */
+  unsigned long long* steps_done; /* env steps executed, added to; or NULL                      */
+  int32_t n, n_keys, n_actions, log_cap, trial_cap, trace_cap, par_rows, policy;
+  int32_t batch_size, reserved_;
+  uint32_t instance_base, flags;  /* COBEL_F_LEARN: train (update, log and replay)              */
+  uint32_t pol_stream, reserved2_;
+  int32_t trial_first;        /* row of the per-trial traces the session's first trial takes    */
+  int32_t trials;             /* trials to run                                                  */
+  int32_t steps_per_trial;    /* the cap of train(interface, trials, steps)                     */
+  int32_t step_budget;        /* > 0: stop after that many steps (launch per step)              */
+  uint64_t seed;
+} cobel_qseq_run_t;
+
+/* Launch shape of cobel_qseq_run: out = {lanes per instance, instances per wavefront, instances
+ * per workgroup, workgroups}.  COBEL_E_UNSUPPORTED outside 1 .. COBEL_QSEQ_MAX_ACTIONS actions or
+ * 1 .. COBEL_QSEQ_MAX_KEYS keys. */
+COBEL_API int cobel_qseq_plan(int32_t n_keys, int32_t n_actions, int32_t n, int32_t out[4]);
+/* QAgent.train (agent/q.py:160-228; COBEL_F_LEARN) or QAgent.test (:230-287) with Sequence.reset /
+ * step and the policy's select_action inside, `trials` trials in every instance in one launch.  Per
+ * step: select from Q[key(state)]; the Sequence step (under overwrite the forced action picks the
+ * reward, the experience keeps the agent's); append the experience (q.py:213); update_q
+ * (:304-313); replay(batch_size) (:344-354), the updates one after the other.  A trial cut by
+ * steps_per_trial is replayed from its first step.  The caller guarantees that no instance runs
+ * past its last trial and that the log has room (a full log takes no record).
+ * COBEL_E_UNSUPPORTED outside the limits above, before any launch. */
+COBEL_API int cobel_qseq_run(const cobel_seq_t* seq, const cobel_qseq_run_t* run, void* stream);
+/* Softmax.get_action_probs / select_action on N rows of n_actions float64 values with injected
+ * uniforms, in the arithmetic of cobel_qseq_run: values [dev] [N][n_actions], mask [dev] [N] bytes
+ * (bit a: action a allowed) or NULL, u [dev] [N], beta [dev] [beta_rows] (beta_rows 1 or N),
+ * action_out [dev] [N] or NULL, probs_out [dev] [N][n_actions] or NULL. */
+COBEL_API int cobel_softmax_n(const double* values, const uint8_t* mask, const double* u,
+                              const double* beta, int32_t beta_rows, uint8_t* action_out,
+                              double* probs_out, int32_t n, int32_t n_actions, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The continuous 2D arena (interface/continuous.py:21-438): a "step" robot that moves in the four
  * cardinal directions or a differential-wheel robot, inside one exterior ring with hole rings
  * (room, obstacles).  Everything is float64, every operation rounded by itself.
