@@ -668,7 +668,10 @@ __global__ __launch_bounds__(256) void k_sr_q(const float* __restrict__ sr,
     return;
   }
   for (int e = t; e < S; e += 256) L.rw[phys(e)] = rewards[(size_t)i * S + e];
-  if (t == 0) build_plan(L.plan, S, reinterpret_cast<int*>(L.rows + (size_t)4 * L.PS));
+  // (build_plan's 256-byte stack lies at the START of the rows, which are loaded behind the
+  //  barrier, as in k_sr.  Not behind the fourth row: the spare row there is 144 bytes at 25
+  //  states, and what follows it are the reward estimates staged above)
+  if (t == 0) build_plan(L.plan, S, reinterpret_cast<int*>(L.rows));
   __syncthreads();
   const int s = states[i];
   const int row = (int)trans[((size_t)i * S + s) * 4 + wave];
@@ -733,8 +736,10 @@ extern "C" int cobel_sr_run(const cobel_world_t* world, const cobel_sr_run_t* ru
   const cobel_sr_run_t& r = *run;
   COBEL_REQUIRE(r.sr && r.trans && r.rewards && r.inst, COBEL_E_ARG,
                 "cobel_sr_run: sr, trans, rewards and inst are required");
-  COBEL_REQUIRE(((uintptr_t)r.sr & 15u) == 0 && ((uintptr_t)r.inst & 7u) == 0, COBEL_E_ARG,
-                "cobel_sr_run: sr must be 16-byte and inst 8-byte aligned");
+  // (trans: both kernels read a state's four 16-bit successors as ONE 64-bit word)
+  COBEL_REQUIRE(((uintptr_t)r.sr & 15u) == 0 && ((uintptr_t)r.inst & 7u) == 0 &&
+                    ((uintptr_t)r.trans & 7u) == 0, COBEL_E_ARG,
+                "cobel_sr_run: sr must be 16-byte, inst and trans 8-byte aligned");
   COBEL_REQUIRE(r.n >= 0, COBEL_E_RANGE, "cobel_sr_run: n = %d", r.n);
   COBEL_REQUIRE(r.steps_per_trial > 0, COBEL_E_RANGE, "cobel_sr_run: steps_per_trial = %d",
                 r.steps_per_trial);

@@ -1232,6 +1232,11 @@ static int tab_plan(const cobel_world_t* world, const cobel_tab_run_t* run, cobe
   COBEL_REQUIRE(((uintptr_t)r.q & (world->n_actions == 4 ? 15u : 3u)) == 0 &&
                     ((uintptr_t)r.inst & 7u) == 0, COBEL_E_ARG,
                 "cobel_tab_run: q must be 16-byte and inst 8-byte aligned");
+  // (model_index: the persistent-workgroup kernel reads the four 16-bit digests of a state as ONE
+  //  64-bit word; model and replay_log hold 64-bit records)
+  COBEL_REQUIRE(((uintptr_t)r.model & 7u) == 0 && ((uintptr_t)r.model_index & 7u) == 0 &&
+                    ((uintptr_t)r.replay_log & 7u) == 0, COBEL_E_ARG,
+                "cobel_tab_run: model, model_index and replay_log must be 8-byte aligned");
   COBEL_REQUIRE(r.n >= 0, COBEL_E_RANGE, "cobel_tab_run: n = %d", r.n);
   COBEL_REQUIRE(r.agent == COBEL_AGENT_Q || r.agent == COBEL_AGENT_DYNAQ, COBEL_E_ARG,
                 "cobel_tab_run: unknown agent %d", r.agent);

@@ -340,7 +340,9 @@ typedef struct {
                             (next | nonterminal << 14 | (R != +0) << 15, cobel_model_index_build),
                             kept in sync by the kernel.  When present the planning kernel reads
                             it from HBM/L2 instead of holding a copy in LDS: nine instances per
-                            CU instead of six.                                                 */
+                            CU instead of six.  8-byte aligned, as `model` and `replay_log` are
+                            (a state's four entries are read as one 64-bit word): COBEL_E_ARG
+                            otherwise.                                                         */
   uint64_t* replay_log;  /* Q: [N][log_cap][COBEL_LOG_WORDS(actions, states)] experiences
                             (q.py:213), or NULL (needed for batch > 0).  Every learning step
                             appends one while there is room, also at batch 0 (the reference's
@@ -559,7 +561,8 @@ COBEL_API int cobel_model_store(uint64_t* model /* [dev] [N][S][4] */,
  * ------------------------------------------------------------------------------------------ */
 typedef struct {
   float* sr;          /* [N][S][S] */
-  uint16_t* trans;    /* [N][S][4] */
+  uint16_t* trans;    /* [N][S][4], 8-byte aligned (a state's row is read as one 64-bit word;
+                         COBEL_E_ARG otherwise; sr: 16-byte, inst: 8-byte aligned)            */
   float* rewards;     /* [N][S]    */
   int32_t* inst;      /* [N][COBEL_I_WORDS] */
   const uint8_t* action_mask;
