@@ -11,8 +11,12 @@ Same constructor, ``train(interface, trials, steps, batch_size=32, no_replay=Fal
 ``train`` runs trial by trial over all instances: ``cobel_pma_trial`` (reset, the start-of-trial
 replay, the steps with the 1-step update and the store), then ``M.update_sr()`` through the public
 method, then the end-of-trial replay with need from ``SR[last]``.  Instances whose trial timed out
-have no last state: their need is ``M.compute_need(None)`` on the host, so ``last`` [N] is read
-back once per trial.  Host callbacks fire at these boundaries: ``on_replay_end`` of the start
+have no last state: their need is ``M.compute_need(None)``.  With ``M.offline_need == 'host'`` (the
+default) that runs on the host, so ``last`` [N] is read back once per trial and T with it where a
+trial timed out.  With ``M.offline_need = 'device'`` the trial is four device calls —
+``cobel_pma_trial``, ``update_sr``, ``cobel_pma_stationary`` selecting by ``last``, ``cobel_pma_replay``
+with ``last`` and that need tensor — and nothing is read back unless a callback asks for host
+values.  Host callbacks fire at these boundaries: ``on_replay_end`` of the start
 replay after the trial's kernel, step callbacks not at all.  The head and the tail of a session
 are ``FusedAgent._session_begin`` / ``_session_end``; the loop between them is this agent's.
 """
@@ -163,10 +167,15 @@ class PMA(FusedAgent):
                 pol.counter.copy_(self.inst[:, _lib.I_CTR_POLICY])
             if replays:
                 logs = self._replay_logs(logs, self._start_records, batch)
-                last = self._last.cpu().numpy()
-                M.update_sr()
-                rec = M._replay_device(self._q, self._mask_dev, batch, last, M._need_rows(last),
-                                       None)
+                if M.offline_need == 'device':
+                    M.update_sr()
+                    rec = M._replay_device(self._q, self._mask_dev, batch, self._last,
+                                           M._need_device(self._last), None)
+                else:
+                    last = self._last.cpu().numpy()
+                    M.update_sr()
+                    rec = M._replay_device(self._q, self._mask_dev, batch, last,
+                                           M._need_rows(last), None)
                 if shared:
                     self.inst[:, _lib.I_CTR_POLICY] = pol.counter
             if self.callbacks.has('on_trial_end', 'on_replay_end'):

@@ -14,9 +14,28 @@ for one instance, and assigning uploads):
   ``T`` / ``SR``   float64 [S, S]        ``update_mask``             bool [A * S], index a * S + s
 
 The initial ``T`` and ``SR`` are the reference's NumPy expressions evaluated on the host, so until
-the first ``update_sr()`` the SR is the reference's bit for bit.  ``compute_need(None)`` — the
-stationary distribution, the left eigenvector of T for the eigenvalue nearest 1 — runs on the host
-with ``scipy.linalg.eig`` and reaches the kernel as a need vector: a slow path.
+the first ``update_sr()`` the SR is the reference's bit for bit.
+
+``compute_need(None)`` — |v| for the unit-2-norm left eigenvector v of T for the eigenvalue nearest
+1 — has two modes, chosen by the attribute ``offline_need``:
+
+  ``'host'``    (default) the reference's expression: T is downloaded, ``scipy.linalg.eig`` runs once
+                per instance and the vectors are uploaded as need rows.
+  ``'device'``  ``cobel_pma_stationary`` (csrc/pma_need.hip): T is row-stochastic, so v is its
+                stationary distribution divided by its 2-norm, and one float64 Gaussian elimination
+                with partial pivoting of ``(I - T + 1 1^T / S)^T x = 1 / S`` per instance gives it:
+                no transfer, no host work, the same bits from the same T.  ``replay`` hands the
+                states to the kernel as its selection and the need tensor straight on to
+                ``cobel_pma_replay``.  ``need_status`` [N] int32 is the status of the last call.
+
+The two agree to the accuracy either has (both are backward-stable solves; docs/MEASUREMENTS.md
+gives the errors against an 80-bit solution), not bit for bit, so a replay may break a near-tie of
+``gain * need`` differently.  Where the eigenvalue 1 of T is multiple (several closed classes) the
+reference returns whichever vector of the eigenspace LAPACK's iteration ends on; the device mode
+returns a defined one: the elimination meets a pivot that is exactly zero (or ends on values that
+are not finite), reports status 1 and returns ``1 / sqrt(S)`` in every component.  The device mode
+serves the default form only: with ``wide=True`` T and SR leave no room for an S x S workspace in
+LDS, and ``offline_need = 'device'`` raises ``NotImplementedError``.
 
 Draws: the memory's generator is stream ``STREAM_PMA_MEMORY`` of (seed, instance) at ``counter``;
 the extension actions come from the memory's own policy object — stream ``STREAM_PMA_POLICY`` at
@@ -94,6 +113,8 @@ class PMAMemory(_device.DeviceMemory):
         self.equal_gain = False
         self.ignore_barriers = True
         self.allow_loops = False
+        self._offline_need = 'host'
+        self.need_status = None
         # memory/pma.py:135-146, on the host
         states = np.zeros((S, A)).astype(int)
         T = np.sum(self.sas, axis=1) / A
@@ -118,6 +139,23 @@ class PMAMemory(_device.DeviceMemory):
                 'states and %d actions, the wide form up to %d states within 160 KiB of LDS (%s)'
                 % (S, A, _lib.PMA_MAX_STATES, _lib.PMA_MAX_ACTIONS, _lib.PMA_WIDE_MAX_STATES,
                    _lib.lib().cobel_last_error().decode('utf-8', 'replace')))
+
+    @property
+    def offline_need(self) -> str:
+        """Where ``compute_need(None)`` runs: ``'host'`` (``scipy.linalg.eig``, the default) or
+        ``'device'`` (``cobel_pma_stationary``)."""
+        return self._offline_need
+
+    @offline_need.setter
+    def offline_need(self, value) -> None:
+        if value not in ('host', 'device'):
+            raise ValueError("offline_need is 'host' or 'device', not %r" % (value,))
+        if value == 'device' and self.wide:
+            raise NotImplementedError(
+                "PMAMemory(wide=True): offline_need = 'device' serves the default form, worlds of "
+                "up to %d states; the wide form keeps compute_need(None) on the host"
+                % _lib.PMA_MAX_STATES)
+        self._offline_need = value
 
     rewards, states, terminals = _table('rewards'), _table('states'), _table('terminals')
     T, SR, update_mask = _table('T'), _table('SR'), _table('update_mask')
@@ -225,13 +263,16 @@ class PMAMemory(_device.DeviceMemory):
 
     def _replay_device(self, q, mask_bits, length: int, states, need_rows, force_first):
         """One replay per instance IN PLACE on the device tensor ``q`` [N, S, A]: ``states`` int32
-        [N] host array (-1: the instance's row of ``need_rows`` [N, S]) or None (all from
-        ``need_rows``).  Returns the records as a uint8 device tensor [N, length * 24]."""
+        [N] host array or device tensor (-1: the instance's row of ``need_rows`` [N, S], a host
+        array or a float64 device tensor) or None (all from ``need_rows``).  Returns the records
+        as a uint8 device tensor [N, length * 24]."""
         dev = self.device
         m = self._mem(q, mask_bits, length)
         st_d = None if states is None else torch.as_tensor(states, device=dev)
-        nd_d = None if need_rows is None else torch.as_tensor(
-            np.ascontiguousarray(need_rows, dtype=np.float64), device=dev)
+        if need_rows is None or torch.is_tensor(need_rows):
+            nd_d = need_rows
+        else:
+            nd_d = torch.as_tensor(np.ascontiguousarray(need_rows, dtype=np.float64), device=dev)
         ff_d = None if force_first is None else torch.as_tensor(force_first, device=dev)
         records = torch.zeros((self.n_envs, max(length, 1) * RECORD.itemsize), dtype=torch.uint8,
                               device=dev)
@@ -260,13 +301,41 @@ class PMAMemory(_device.DeviceMemory):
         rows[idx] = need.reshape(-1, self.nb_actions * S)[:, :S]
         return rows
 
+    def _need_device(self, select):
+        """``cobel_pma_stationary``: the need tensor [N, S] (float64, device) with the rows of the
+        instances whose entry of ``select`` (int32 [N] device tensor, or None: all) is negative
+        filled in, the others zero; ``need_status`` takes the call's status [N]."""
+        assert self._is_bound, _device.NOT_BOUND
+        dev = self.device
+        need = torch.zeros((self.n_envs, self.nb_states), dtype=torch.float64, device=dev)
+        self.need_status = torch.zeros(self.n_envs, dtype=torch.int32, device=dev)
+        m = self._mem()
+        _lib.check(_lib.lib().cobel_pma_stationary(
+            C.byref(m), _lib.ptr(select), _lib.ptr(need), _lib.ptr(self.need_status),
+            _lib.current_stream(dev)))
+        return need
+
+    def stationary(self, instances=None):
+        """The vectors of ``compute_need(None)`` by the device kernel, whatever ``offline_need``
+        says: a float64 device tensor [n, S], one row per entry of ``instances`` (default:
+        all).  ``need_status`` tells the degenerate ones."""
+        if instances is None:
+            return self._need_device(None)
+        idx = np.asarray(instances, dtype=np.int64).reshape(-1)
+        select = np.zeros(self.n_envs, dtype=np.int32)
+        select[idx] = -1
+        need = self._need_device(torch.as_tensor(select, device=self.device))
+        return need[torch.as_tensor(idx, device=self.device)]
+
     def replay(self, q_function, action_mask, replay_length: int, current_state,
                force_first=None):
         """memory/pma.py:168-267: one replay per instance on a copy of ``q_function`` ([S, A], or
         [N, S, A]).  Returns ``(updates, Q)``: the performed updates as a list of experience dicts
         and the updated copy as a NumPy array for one instance; one list per instance and the
         device tensor [N, S, A] for several.  ``current_state`` / ``force_first`` are scalars or
-        [N] arrays; ``current_state=None`` takes ``compute_need(None)`` (host, slow)."""
+        [N] arrays; ``current_state=None`` (or an entry None / < 0) takes ``compute_need(None)``:
+        with ``offline_need = 'host'`` through the host, with ``'device'`` by
+        ``cobel_pma_stationary`` without leaving the device."""
         assert self._is_bound, _device.NOT_BOUND
         n, S, A = self.n_envs, self.nb_states, self.nb_actions
         if torch.is_tensor(q_function):
@@ -277,7 +346,13 @@ class PMAMemory(_device.DeviceMemory):
         states = (None if current_state is None
                   else self._per_instance(current_state, 'current_state', S))
         ff = None if force_first is None else self._per_instance(force_first, 'force_first', S)
-        rows = self._need_rows(states)
+        if self._offline_need == 'device':
+            rows = None
+            if states is None or (states < 0).any():
+                states = None if states is None else torch.as_tensor(states, device=self.device)
+                rows = self._need_device(states)
+        else:
+            rows = self._need_rows(states)
         length = int(replay_length)
         records = self._replay_device(q, self._mask_bits(action_mask), length, states, rows, ff)
         ups = self.experiences(records, length)
@@ -286,9 +361,13 @@ class PMAMemory(_device.DeviceMemory):
         return ups, q
 
     def compute_need(self, current_state=None, instances=None):
-        """memory/pma.py:388-411.  ``None``: the stationary distribution of T by
-        ``scipy.linalg.eig`` on the host, of ``instances`` (default: all)."""
+        """memory/pma.py:388-411.  ``None``: the unit-2-norm stationary vector of T of
+        ``instances`` (default: all), tiled ``nb_actions`` times, as NumPy: by
+        ``scipy.linalg.eig`` on the host, or with ``offline_need = 'device'`` by the kernel."""
         S, A = self.nb_states, self.nb_actions
+        if current_state is None and self._offline_need == 'device':
+            out = np.tile(self.stationary(instances).cpu().numpy(), (1, A))
+            return out[0] if (instances is None and len(out) == 1) else out
         if current_state is None:
             from scipy import linalg
             T = np.asarray(self.T, dtype=np.float64).reshape(-1, S, S)

@@ -1241,6 +1241,29 @@ COBEL_API int cobel_pma_store(const cobel_pma_mem_t* mem, const cobel_pma_exp_t*
  * to COBEL_PMA_MAX_STATES states, beyond (wide form) blocked over panels of 32 pivots on the SR
  * block in global memory, the same operations per element in the same order. */
 COBEL_API int cobel_pma_update_sr(const cobel_pma_mem_t* mem, void* stream);
+/* PMAMemory.compute_need(None) (memory/pma.py:403-408) per instance: |v| for the unit-2-norm
+ * left eigenvector v of mem->T for the eigenvalue 1, i.e. the stationary distribution of T
+ * divided by its 2-norm.  select [dev][N] or NULL: an instance whose entry is >= 0 is skipped
+ * (its row of need and its status are not written); NULL selects all.  need [dev][N][S] out,
+ * status [dev][N] out (0 ok, 1 degenerate).  Reads mem->T, n, n_states (and the form in flags)
+ * only.  So cobel_pma_replay's current_state serves as select, and need as its need.
+ * Method: T is row-stochastic, so the vector solves (I - T + (1/S) 1 1^T)^T x = (1/S) 1; one
+ * float64 Gaussian elimination with partial pivoting per instance in LDS (one workgroup each),
+ * |x| divided by its 2-norm, every operation in a fixed order — no iteration, and the same bits
+ * from the same T whatever the batch.  Every T with a simple eigenvalue 1 is served, transient
+ * states included.  Degenerate (status 1): a pivot is exactly zero or the result is not finite;
+ * need is then 1 / sqrt(S) in every component.  With a multiple eigenvalue 1 the reference
+ * returns whichever vector of the eigenspace LAPACK's iteration ends on; this call returns that
+ * defined one, or, where rounding hides the singularity, some finite vector with status 0.
+ * COBEL_E_UNSUPPORTED beyond COBEL_PMA_MAX_STATES states and for the wide form (COBEL_PMA_WIDE:
+ * T and SR leave no S x S workspace; its compute_need(None) stays on the host);
+ * COBEL_E_RANGE for n < 1. */
+COBEL_API int cobel_pma_stationary(const cobel_pma_mem_t* mem, const int32_t* select,
+                                   double* need, int32_t* status, void* stream);
+/* Launch shape of cobel_pma_stationary: out = {LDS bytes of a workgroup (one per instance): the
+ * S x (S + 1) augmented matrix at a row stride of the next odd count past S, the multipliers,
+ * pivots and solution; its threads}.  COBEL_E_UNSUPPORTED beyond COBEL_PMA_MAX_STATES. */
+COBEL_API int cobel_pma_plan_need(int32_t n_states, int32_t out[2]);
 
 /* ---------------------------------------------------------------------------------------------
  * Model-Free Episodic Control (Blundell et al. 2016).  Replaces ActionBuffer / QEC
