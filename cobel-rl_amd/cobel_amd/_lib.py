@@ -585,6 +585,8 @@ _SIGNATURES = {
     'cobel_pma_update_sr': (C.c_int, [C.POINTER(PMAMem), _P]),
     'cobel_pma_stationary': (C.c_int, [C.POINTER(PMAMem), _P, _P, _P, _P]),
     'cobel_pma_plan_need': (C.c_int, [C.c_int32, C.POINTER(C.c_int32 * 2)]),
+    'cobel_pma_stationary_wide': (C.c_int, [C.POINTER(PMAMem), _P, _P, _P, _P, C.c_int64, _P]),
+    'cobel_pma_plan_need_wide': (C.c_int, [C.c_int32, C.POINTER(C.c_int64 * 4)]),
     'cobel_mfec_pairs': (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P]),
     'cobel_mfec_run': (C.c_int, [_P, C.POINTER(MFECMem), C.POINTER(MFECRun), _P]),
     'cobel_mfec_estimate': (C.c_int, [C.POINTER(MFECMem), _P, C.c_int32, _P, _P]),

@@ -16,7 +16,8 @@ default) that runs on the host, so ``last`` [N] is read back once per trial and 
 trial timed out.  With ``M.offline_need = 'device'`` the trial is four device calls —
 ``cobel_pma_trial``, ``update_sr``, ``cobel_pma_stationary`` selecting by ``last``, ``cobel_pma_replay``
 with ``last`` and that need tensor — and nothing is read back unless a callback asks for host
-values.  Host callbacks fire at these boundaries: ``on_replay_end`` of the start
+values.  A wide memory built with a ``need_workspace`` takes ``cobel_pma_stationary_wide`` in that
+place (the elimination on a workspace in device memory), with the same effect.  Host callbacks fire at these boundaries: ``on_replay_end`` of the start
 replay after the trial's kernel, step callbacks not at all.  The head and the tail of a session
 are ``FusedAgent._session_begin`` / ``_session_end``; the loop between them is this agent's.
 """

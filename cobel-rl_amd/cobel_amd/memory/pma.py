@@ -33,9 +33,14 @@ gives the errors against an 80-bit solution), not bit for bit, so a replay may b
 ``gain * need`` differently.  Where the eigenvalue 1 of T is multiple (several closed classes) the
 reference returns whichever vector of the eigenspace LAPACK's iteration ends on; the device mode
 returns a defined one: the elimination meets a pivot that is exactly zero (or ends on values that
-are not finite), reports status 1 and returns ``1 / sqrt(S)`` in every component.  The device mode
-serves the default form only: with ``wide=True`` T and SR leave no room for an S x S workspace in
-LDS, and ``offline_need = 'device'`` raises ``NotImplementedError``.
+are not finite), reports status 1 and returns ``1 / sqrt(S)`` in every component.  In the default
+form the elimination runs in LDS.  With ``wide=True`` T and SR leave no room for an S x S workspace
+there: ``PMAMemory(..., wide=True, need_workspace=k)`` keeps the elimination workspaces of k
+instances in device memory (about 8 * S * S bytes each, 8 MiB at 1 024 states; clipped to the
+instance count at bind) and ``cobel_pma_stationary_wide`` (csrc/pma_need_wide.hip) does the same
+solve on them, the same operations in the same order, k instances at a time.  Without a workspace
+(``need_workspace=0``, the default) ``offline_need = 'device'`` raises ``NotImplementedError`` on a
+wide memory.
 
 Draws: the memory's generator is stream ``STREAM_PMA_MEMORY`` of (seed, instance) at ``counter``;
 the extension actions come from the memory's own policy object — stream ``STREAM_PMA_POLICY`` at
@@ -89,9 +94,16 @@ def _table(name: str):
 
 class PMAMemory(_device.DeviceMemory):
     def __init__(self, sas, policy, learning_rate: float = 0.9, learning_rate_q: float = 0.9,
-                 gamma: float = 0.9, gamma_q: float = 0.9, rng=None, wide: bool = False) -> None:
+                 gamma: float = 0.9, gamma_q: float = 0.9, rng=None, wide: bool = False,
+                 need_workspace: int = 0) -> None:
         self.rng = rng
         self.wide = bool(wide)
+        self.need_workspace = int(need_workspace)
+        if self.need_workspace < 0 or (self.need_workspace and not self.wide):
+            raise ValueError(
+                'PMAMemory: need_workspace = %d — the number of instances whose elimination '
+                'workspaces the wide form (wide=True) holds in device memory; the default form '
+                'solves in LDS and takes none' % self.need_workspace)
         self.sas = np.asarray(sas)
         self.policy = policy
         self.learning_rate = learning_rate
@@ -125,6 +137,7 @@ class PMAMemory(_device.DeviceMemory):
             'update_mask': states.flatten(order='F') != np.tile(np.arange(S), A),
         }
         self._dev = None
+        self._need_work = None
         self.counter = None
         self.seed, self.instance_base = 0, 0
         self._pows = None
@@ -140,21 +153,28 @@ class PMAMemory(_device.DeviceMemory):
                 % (S, A, _lib.PMA_MAX_STATES, _lib.PMA_MAX_ACTIONS, _lib.PMA_WIDE_MAX_STATES,
                    _lib.lib().cobel_last_error().decode('utf-8', 'replace')))
 
+    def _need_work_bytes(self) -> int:
+        """Bytes of one instance's elimination workspace (``cobel_pma_plan_need_wide``)."""
+        out = (C.c_int64 * 4)()
+        _lib.check(_lib.lib().cobel_pma_plan_need_wide(self.nb_states, C.byref(out)))
+        return int(out[0])
+
     @property
     def offline_need(self) -> str:
         """Where ``compute_need(None)`` runs: ``'host'`` (``scipy.linalg.eig``, the default) or
-        ``'device'`` (``cobel_pma_stationary``)."""
+        ``'device'`` (``cobel_pma_stationary``; on a wide memory with a ``need_workspace``,
+        ``cobel_pma_stationary_wide``)."""
         return self._offline_need
 
     @offline_need.setter
     def offline_need(self, value) -> None:
         if value not in ('host', 'device'):
             raise ValueError("offline_need is 'host' or 'device', not %r" % (value,))
-        if value == 'device' and self.wide:
+        if value == 'device' and self.wide and not self.need_workspace:
             raise NotImplementedError(
                 "PMAMemory(wide=True): offline_need = 'device' serves the default form, worlds of "
-                "up to %d states; the wide form keeps compute_need(None) on the host"
-                % _lib.PMA_MAX_STATES)
+                "up to %d states; the wide form keeps compute_need(None) on the host unless it "
+                "was built with a need_workspace" % _lib.PMA_MAX_STATES)
         self._offline_need = value
 
     rewards, states, terminals = _table('rewards'), _table('states'), _table('terminals')
@@ -165,20 +185,23 @@ class PMAMemory(_device.DeviceMemory):
         if self._dev is not None:
             assert self.n_envs == n_envs, 'a memory stays bound to the instance count it first saw'
             return
+        held = min(self.need_workspace, n_envs)
+        work = held * self._need_work_bytes() if held else 0
         if self.wide and torch.device(device).type == 'cuda':
-            need = n_envs * self.nb_states ** 2 * 16
+            need = n_envs * self.nb_states ** 2 * 16 + work
             free = torch.cuda.mem_get_info(device)[0]
             if need > free:
                 raise MemoryError(
-                    'PMAMemory(wide=True): T and SR of %d instances of %d states take %d bytes '
-                    '(%.1f GiB), %d bytes of device memory are free'
-                    % (n_envs, self.nb_states, need, need / 2.0 ** 30, free))
+                    'PMAMemory(wide=True): T and SR of %d instances of %d states and the need '
+                    'workspaces of %d take %d bytes (%.1f GiB), %d bytes of device memory are free'
+                    % (n_envs, self.nb_states, held, need, need / 2.0 ** 30, free))
         dev = {}
         for name, (tdt, _) in _TABLES.items():
             h = np.ascontiguousarray(self._host[name])
             t = torch.as_tensor(h, device=device).to(tdt)
             dev[name] = t.unsqueeze(0).expand((n_envs,) + tuple(t.shape)).contiguous()
         self._dev = dev
+        self._need_work = torch.empty(work, dtype=torch.uint8, device=device) if work else None
         self.n_envs = n_envs
         self.counter = torch.zeros(n_envs, dtype=torch.int32, device=device)
 
@@ -302,17 +325,27 @@ class PMAMemory(_device.DeviceMemory):
         return rows
 
     def _need_device(self, select):
-        """``cobel_pma_stationary``: the need tensor [N, S] (float64, device) with the rows of the
-        instances whose entry of ``select`` (int32 [N] device tensor, or None: all) is negative
-        filled in, the others zero; ``need_status`` takes the call's status [N]."""
+        """``cobel_pma_stationary`` (a wide memory: ``cobel_pma_stationary_wide`` on its
+        workspace): the need tensor [N, S] (float64, device) with the rows of the instances whose
+        entry of ``select`` (int32 [N] device tensor, or None: all) is negative filled in, the
+        others zero; ``need_status`` takes the call's status [N]."""
         assert self._is_bound, _device.NOT_BOUND
         dev = self.device
         need = torch.zeros((self.n_envs, self.nb_states), dtype=torch.float64, device=dev)
         self.need_status = torch.zeros(self.n_envs, dtype=torch.int32, device=dev)
         m = self._mem()
-        _lib.check(_lib.lib().cobel_pma_stationary(
-            C.byref(m), _lib.ptr(select), _lib.ptr(need), _lib.ptr(self.need_status),
-            _lib.current_stream(dev)))
+        if self.wide:
+            if self._need_work is None:
+                raise NotImplementedError(
+                    'PMAMemory(wide=True): the stationary distribution on the device takes a '
+                    'workspace — build the memory with need_workspace >= 1')
+            _lib.check(_lib.lib().cobel_pma_stationary_wide(
+                C.byref(m), _lib.ptr(select), _lib.ptr(need), _lib.ptr(self.need_status),
+                _lib.ptr(self._need_work), self._need_work.numel(), _lib.current_stream(dev)))
+        else:
+            _lib.check(_lib.lib().cobel_pma_stationary(
+                C.byref(m), _lib.ptr(select), _lib.ptr(need), _lib.ptr(self.need_status),
+                _lib.current_stream(dev)))
         return need
 
     def stationary(self, instances=None):

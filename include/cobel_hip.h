@@ -1256,7 +1256,7 @@ COBEL_API int cobel_pma_update_sr(const cobel_pma_mem_t* mem, void* stream);
  * returns whichever vector of the eigenspace LAPACK's iteration ends on; this call returns that
  * defined one, or, where rounding hides the singularity, some finite vector with status 0.
  * COBEL_E_UNSUPPORTED beyond COBEL_PMA_MAX_STATES states and for the wide form (COBEL_PMA_WIDE:
- * T and SR leave no S x S workspace; its compute_need(None) stays on the host);
+ * T and SR leave no S x S workspace in LDS; cobel_pma_stationary_wide below serves it);
  * COBEL_E_RANGE for n < 1. */
 COBEL_API int cobel_pma_stationary(const cobel_pma_mem_t* mem, const int32_t* select,
                                    double* need, int32_t* status, void* stream);
@@ -1264,6 +1264,34 @@ COBEL_API int cobel_pma_stationary(const cobel_pma_mem_t* mem, const int32_t* se
  * S x (S + 1) augmented matrix at a row stride of the next odd count past S, the multipliers,
  * pivots and solution; its threads}.  COBEL_E_UNSUPPORTED beyond COBEL_PMA_MAX_STATES. */
 COBEL_API int cobel_pma_plan_need(int32_t n_states, int32_t out[2]);
+/* The same vectors beyond the LDS: 1 .. COBEL_PMA_WIDE_MAX_STATES states, the elimination on a
+ * caller-owned workspace in device memory.  select, need and status as in cobel_pma_stationary;
+ * reads mem->T, n and n_states only (COBEL_PMA_WIDE in flags is not looked at).  The same
+ * operations per element in the same order as the LDS kernel, so the same bits wherever both run.
+ * Workspace per instance, in bytes (cobel_pma_plan_need_wide's out[0]):
+ *     8 * S * (S + 1) + 4 * (S + 1), rounded up to a multiple of 16
+ * — the augmented matrix, the pivot rows and one mark word; 8 MiB at 1 024 states.  work [dev],
+ * 8-byte aligned, holds work_bytes / that many instances (at least one); the n instances are taken
+ * in groups of that size, one group after the other in the stream, and the result does not depend
+ * on the group size.  The workspace holds nothing of value between calls.
+ * Method: a right-looking LU with partial pivoting, blocked over panels of 16 pivots; per panel
+ * three launches ordered by the stream — the panel with pivoting (one workgroup per instance, the
+ * whole remaining height in LDS), the panel's swaps and its rows of U in the columns to the right,
+ * the rank-16 update of the rest over 64 x 64 tiles (one instance uses the whole chip) — then one
+ * workgroup per instance for the back substitution and the norm.  No kernel waits for another
+ * workgroup and nothing is read back; a degenerate instance is marked in its workspace and skipped
+ * by the later launches.
+ * COBEL_E_ARG: NULL mem, T, need, status or work, a misaligned pointer, or a workspace smaller
+ * than one instance's (the message names the bytes needed); COBEL_E_RANGE: n < 1;
+ * COBEL_E_UNSUPPORTED: n_states outside 1 .. COBEL_PMA_WIDE_MAX_STATES.  Every refusal comes before
+ * any launch. */
+COBEL_API int cobel_pma_stationary_wide(const cobel_pma_mem_t* mem, const int32_t* select,
+                                        double* need, int32_t* status, void* work,
+                                        int64_t work_bytes, void* stream);
+/* out = {workspace bytes per instance, LDS bytes of the largest workgroup (the panel kernel's
+ * S x 17 doubles from 241 states on, the back substitution's below), its threads, the panel width}.
+ * COBEL_E_UNSUPPORTED outside 1 .. COBEL_PMA_WIDE_MAX_STATES, with out zeroed. */
+COBEL_API int cobel_pma_plan_need_wide(int32_t n_states, int64_t out[4]);
 
 /* ---------------------------------------------------------------------------------------------
  * Model-Free Episodic Control (Blundell et al. 2016).  Replaces ActionBuffer / QEC
