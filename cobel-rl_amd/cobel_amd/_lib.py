@@ -308,6 +308,17 @@ class PMARun(C.Structure):
     ]
 
 
+METRIC_MAX_STATES, METRIC_MAX_RANK, METRIC_MAX_WORLDS = 16383, 128, 65535
+
+
+def metric_work_bytes(n_worlds: int, n_states: int, max_rank: int) -> int:
+    """Bytes of the workspace ``cobel_metric_dr`` takes (include/cobel_hip.h)."""
+    W, S, k = int(n_worlds), int(n_states), int(max_rank)
+    head = (4 * W * (1 + k) + 15) // 16 * 16
+    world = ((36 * k + 7) // 8 * 8 + 8 * (9 * k + k * k + 2 * k * S) + 15) // 16 * 16
+    return head + W * world
+
+
 MFEC_MAX_STATES, MFEC_MAX_ACTIONS, MFEC_MAX_CAPACITY, MFEC_MAX_K = 1024, 8, 2048, 32
 MFEC_MAX_FEATURES = 65536
 
@@ -587,6 +598,10 @@ _SIGNATURES = {
     'cobel_pma_plan_need': (C.c_int, [C.c_int32, C.POINTER(C.c_int32 * 2)]),
     'cobel_pma_stationary_wide': (C.c_int, [C.POINTER(PMAMem), _P, _P, _P, _P, C.c_int64, _P]),
     'cobel_pma_plan_need_wide': (C.c_int, [C.c_int32, C.POINTER(C.c_int64 * 4)]),
+    'cobel_metric_sr': (C.c_int, [_P, C.c_int32, C.c_int32, C.c_double, _P, _P]),
+    'cobel_metric_dr': (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_double,
+                                  _P, _P, C.c_int64, _P]),
+    'cobel_metric_plan': (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int64 * 4)]),
     'cobel_mfec_pairs': (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P]),
     'cobel_mfec_run': (C.c_int, [_P, C.POINTER(MFECMem), C.POINTER(MFECRun), _P]),
     'cobel_mfec_estimate': (C.c_int, [C.POINTER(MFECMem), _P, C.c_int32, _P, _P]),

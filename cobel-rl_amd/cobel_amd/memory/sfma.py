@@ -63,7 +63,7 @@ class SFMAMemory(_device.DeviceMemory, _device.PackedModel):
         self.blend = 0.1
         self.interpolation_fwd, self.interpolation_rev = 0.5, 0.5
         self.table = self.strength = self.stamp = self.state = self.counter = None
-        self._metric_dev = self._metric_src = None
+        self._metric_dev = self._metric_src = self._metric_version = None
         self._recency = None
         # the session the host-called methods draw in: seed, instance base, worlds of the metric
         self.seed, self.instance_base, self._n_worlds = 0, 0, 1
@@ -87,18 +87,41 @@ class SFMAMemory(_device.DeviceMemory, _device.PackedModel):
         self.counter = torch.zeros(n_envs, dtype=torch.int32, device=device)
 
     def _metric_on(self, device, n_worlds: int):
-        """metric.D on the device, [n_worlds, S, S]: one matrix shared by all worlds, or a stack."""
-        D = np.asarray(self.metric.D if hasattr(self.metric, 'D') else self.metric,
-                       dtype=np.float64)
-        if self._metric_dev is None or self._metric_src is not D:
-            S = self.nb_states
+        """metric.D on the device, [n_worlds, S, S]: one matrix shared by all worlds, or a stack.
+        A float64 contiguous tensor on ``device`` (a metric with ``compute='device'``) is used where
+        it lies, without a copy: what ``update_transitions()`` writes into it in stream order is
+        what the next launch reads.  One [S, S] matrix for several worlds is expanded into a stack of
+        the memory's own, again after each ``update_transitions()`` of the metric."""
+        src = self.metric.D if hasattr(self.metric, 'D') else self.metric
+        S, dev = self.nb_states, torch.device(device)
+        version = getattr(self.metric, 'version', None)     # (device metrics count their updates)
+        if isinstance(src, torch.Tensor) and src.is_cuda and dev.type == 'cuda' \
+                and dev.index in (None, src.device.index):
+            assert src.dtype == torch.float64 and src.is_contiguous(), \
+                'a device metric is a contiguous float64 tensor'
+            if src.dim() == 3 or n_worlds == 1:
+                assert tuple(src.shape) in ((S, S), (n_worlds, S, S)), \
+                    'metric.D must be [S, S] or [n_worlds, S, S]'
+                return src
+            assert tuple(src.shape) == (S, S), 'metric.D must be [S, S] or [n_worlds, S, S]'
+            if self._metric_dev is None or self._metric_src is not src \
+                    or self._metric_version != version:
+                if self._metric_dev is None or self._metric_src is not src:
+                    self._metric_dev = torch.empty((n_worlds, S, S), dtype=torch.float64,
+                                                   device=src.device)
+                self._metric_dev.copy_(src.expand(n_worlds, S, S))
+                self._metric_src, self._metric_version = src, version
+            return self._metric_dev
+        if self._metric_dev is None or self._metric_src is not src:
+            D = np.asarray(src.cpu().numpy() if isinstance(src, torch.Tensor) else src,
+                           dtype=np.float64)
             if D.ndim == 2:
                 D3 = np.broadcast_to(D, (n_worlds, S, S))
             else:
                 D3 = D
             assert D3.shape == (n_worlds, S, S), 'metric.D must be [S, S] or [n_worlds, S, S]'
             self._metric_dev = torch.as_tensor(np.array(D3, dtype=np.float64, order='C'), device=device)
-            self._metric_src = D
+            self._metric_src = src
         return self._metric_dev
 
     def _recency_table(self, device):

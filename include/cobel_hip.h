@@ -1294,6 +1294,66 @@ COBEL_API int cobel_pma_stationary_wide(const cobel_pma_mem_t* mem, const int32_
 COBEL_API int cobel_pma_plan_need_wide(int32_t n_states, int64_t out[4]);
 
 /* ---------------------------------------------------------------------------------------------
+ * The similarity metrics of SFMA (memory/utils/metrics.py:66-268) for stacks of four-action worlds
+ * given by their compact successor tables: SR.D = inv(I - gamma T) (:66-105) and DR.D, the same
+ * inverse of the default world corrected by the Woodbury identity (:107-268).  Everything is
+ * float64, one rounding per operation, every sum in ascending index order (no MFMA), so a matrix
+ * depends on its own world alone and equals the NumPy restatement of tests/metric_common.py bit
+ * for bit.  Neither call has a status word; every refusal comes before any launch.
+ * --------------------------------------------------------------------------------------------- */
+#define COBEL_METRIC_MAX_STATES 16383  /* what cobel_sfma_run serves                              */
+#define COBEL_METRIC_MAX_RANK 128      /* affected states per world: the k x k block of the
+                                        * Woodbury correction at a row stride of k + 1 doubles and
+                                        * its bookkeeping (pivots, the rows of delta, the pivot
+                                        * search) take 152 064 of a workgroup's 163 840 bytes of LDS */
+#define COBEL_METRIC_MAX_WORLDS 65535  /* worlds of one call (the grid's z axis)                  */
+/* SR(sas, gamma).D (metrics.py:66-105) of n_worlds worlds: next [dev] [n_worlds][S][4] successor
+ * of (state, action); D [dev] [n_worlds][S][S] out.  L = I - gamma T is written straight from the
+ * table (T[s][c] = count / 4; 1.0 - gamma t on the diagonal, 0.0 - gamma t elsewhere; no dense T is
+ * formed), then inverted in place by Gauss-Jordan without pivoting (L is strictly diagonally
+ * dominant by rows for gamma < 1): pivots ascending, the pivot row scaled by 1 / pivot (the pivot's
+ * place takes 1 / pivot), every other element M - col[r] * row[c] (0 - col[r] * row[k] in column
+ * k); blocked over panels of 32 pivots as cobel_pma_update_sr's wide form, 1 + 3 ceil(S / 32)
+ * launches ordered by the stream.
+ * COBEL_E_ARG: a NULL or misaligned pointer, n_worlds < 1, gamma outside [0, 1);
+ * COBEL_E_UNSUPPORTED: n_states outside 1 .. COBEL_METRIC_MAX_STATES, more than
+ * COBEL_METRIC_MAX_WORLDS worlds. */
+COBEL_API int cobel_metric_sr(const int32_t* next, int32_t n_worlds, int32_t n_states, double gamma,
+                              double* D, void* stream);
+/* DR.update_transitions (metrics.py:107-268): D_w = D0 - (D0[:, J_w] alpha_w) (delta_w D0) per
+ * world.  D0 [dev] [S][S] is the metric of the default world, shared by all worlds (cobel_metric_sr
+ * on next_default); next [dev] [n_worlds][S][4]; next_default [dev] [S][4]; J [HOST]
+ * [n_worlds][max_rank], row w holding rank[w] affected states in strictly ascending order
+ * (np.unique of the first members of invalid_transitions); rank [HOST] [n_worlds]; D [dev]
+ * [n_worlds][S][S] out, not D0.  J and rank are copied into the workspace in stream order; they
+ * must stay valid until the stream has passed the call.
+ *   delta  rows (I - gamma T_new)[J] - (I - gamma T_default)[J], those very expressions on the at
+ *          most nine columns where either table has an entry (the state, four successors each)
+ *   A      I_k + delta D0[:, J]
+ *   alpha  A^-1 by in-place Gauss-Jordan with partial pivoting in LDS, one workgroup per world
+ *          (pivot: largest magnitude in the column, lowest row on ties)
+ *   D      X = delta D0, Y = D0[:, J] alpha, D = D0 - Y X over 64 x 64 tiles (D0 and D touched
+ *          once); terms of delta that are exactly zero are skipped (they change no bit)
+ * A world of rank 0 gets a copy of D0.  Four launches (one with max_rank 0).
+ * work [dev], 16-byte aligned, of at least
+ *     (4 * n_worlds * (1 + max_rank), rounded up to 16) + n_worlds * cobel_metric_plan's out[3]
+ * bytes for (n_states, max_rank); it holds nothing of value between calls.
+ * COBEL_E_ARG: a NULL or misaligned pointer, D == D0, n_worlds < 1, gamma outside [0, 1), a rank
+ * outside 0 .. max_rank, J unsorted or out of range, a workspace too small (the message names the
+ * bytes); COBEL_E_UNSUPPORTED: n_states outside 1 .. COBEL_METRIC_MAX_STATES, a rank above
+ * COBEL_METRIC_MAX_RANK, more than COBEL_METRIC_MAX_WORLDS worlds. */
+COBEL_API int cobel_metric_dr(const double* D0, const int32_t* next, const int32_t* next_default,
+                              const int32_t* J, const int32_t* rank, int32_t max_rank,
+                              int32_t n_worlds, int32_t n_states, double gamma, double* D,
+                              void* work, int64_t work_bytes, void* stream);
+/* out = {form of cobel_metric_sr (0: the matrix is one diagonal block, up to 32 states; 1:
+ * blocked), LDS bytes of the largest workgroup of cobel_metric_sr and — rank > 0 — cobel_metric_dr
+ * at that rank, its threads, workspace bytes per world of cobel_metric_dr at max_rank = rank}.
+ * COBEL_E_UNSUPPORTED outside 1 .. COBEL_METRIC_MAX_STATES states or 0 .. COBEL_METRIC_MAX_RANK,
+ * with out zeroed. */
+COBEL_API int cobel_metric_plan(int32_t n_states, int32_t rank, int64_t out[4]);
+
+/* ---------------------------------------------------------------------------------------------
  * Model-Free Episodic Control (Blundell et al. 2016).  Replaces ActionBuffer / QEC
  * (agent/mfec.py:28-237: find_state, find_neighbors, add, replace, estimate, update,
  * update_episode) and the trial loops of MFEC.train / MFEC.test / predict_on_batch
