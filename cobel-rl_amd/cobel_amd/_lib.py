@@ -190,6 +190,20 @@ class TabRun(C.Structure):
     ]
 
 
+ROLLOUT_ELEMENT_STORES = 1       # cobel_tab_rollout_t.record_flags (COBEL_ROLLOUT_*)
+
+
+class TabRollout(C.Structure):
+    """``cobel_tab_rollout_t``: a ``cobel_tab_run_t`` held by value and the trajectory record."""
+    _fields_ = [
+        ('run', TabRun),
+        ('start', C.c_void_p), ('states', C.c_void_p), ('actions', C.c_void_p),
+        ('length', C.c_void_p),
+        ('trials', C.c_int32), ('steps', C.c_int32), ('record_flags', C.c_uint32),
+        ('reserved_', C.c_int32),
+    ]
+
+
 class TabExp(C.Structure):
     """``cobel_tab_exp_t`` (24 bytes)."""
     _fields_ = [
@@ -570,6 +584,10 @@ _SIGNATURES = {
                                           C.POINTER(C.c_int32 * 4)]),
     'cobel_dynaq_update': (C.c_int, [_P, C.POINTER(TabRun), _P, C.c_uint32, _P, _P]),
     'cobel_model_store': (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, C.c_double, _P]),
+    'cobel_tab_rollout': (C.c_int, [_P, C.POINTER(TabRollout), _P]),
+    'cobel_tab_rollout_plan': (C.c_int, [_P, C.POINTER(TabRollout), C.POINTER(C.c_int32 * 4)]),
+    'cobel_rollout_visits': (C.c_int, [_P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_uint32,
+                                       _P, _P]),
     'cobel_pack_model': (C.c_uint64, [C.c_float, C.c_uint16, C.c_uint8]),
     'cobel_unpack_model': (None, [C.c_uint64, C.POINTER(C.c_float), C.POINTER(C.c_uint16),
                                   C.POINTER(C.c_uint8)]),

@@ -503,6 +503,23 @@ class FusedAgent(Agent):
         if check is not None:
             check()
 
+    def _one_launch_session(self, first: int, trials: int, launch) -> None:
+        """The trials ``first .. first + trials - 1`` as ONE launch: ``on_trial_begin`` for each,
+        ``launch()``, then ``on_trial_end`` for each with the means over instances."""
+        for t in range(trials):
+            self.callbacks.on_trial_begin({'trial_reward': 0.0, 'trial': first + t,
+                                           'trial_session': t})
+        launch()
+        self.current_trial = first + trials
+        if self.callbacks.has('on_trial_end'):
+            lat, rew = self.monitors.mean_latency(), self.monitors.mean_reward()
+            cnt = self.monitors.lat_cnt.cpu().numpy()
+            for t in range(trials):
+                self.callbacks.on_trial_end({
+                    'trial_reward': float(rew[first + t]), 'trial': first + t,
+                    'trial_session': t, 'steps': float(lat[first + t]),
+                    'count': int(cnt[first + t])})
+
     def _session(self, interface, trials: int, steps: int, batch: int, learn: bool,
                  extra_flags: int = 0, pol=None) -> None:
         pol, flags, first = self._session_begin(interface, trials, learn, extra_flags, pol)
@@ -510,19 +527,8 @@ class FusedAgent(Agent):
         per_trial = self.n_envs == 1 and (per_step or self.callbacks.has('on_trial_begin',
                                                                          'on_trial_end'))
         if not per_trial:
-            for t in range(trials):
-                self.callbacks.on_trial_begin({'trial_reward': 0.0, 'trial': first + t,
-                                               'trial_session': t})
-            self._launch(interface, pol, flags, first + trials, steps, 0, batch)
-            self.current_trial = first + trials
-            if self.callbacks.has('on_trial_end'):
-                lat, rew = self.monitors.mean_latency(), self.monitors.mean_reward()
-                cnt = self.monitors.lat_cnt.cpu().numpy()
-                for t in range(trials):
-                    self.callbacks.on_trial_end({
-                        'trial_reward': float(rew[first + t]), 'trial': first + t,
-                        'trial_session': t, 'steps': float(lat[first + t]),
-                        'count': int(cnt[first + t])})
+            self._one_launch_session(first, trials, lambda: self._launch(
+                interface, pol, flags, first + trials, steps, 0, batch))
         else:
             for t in range(trials):
                 logs = self.callbacks.on_trial_begin(self._trial_logs(

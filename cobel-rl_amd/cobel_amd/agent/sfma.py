@@ -208,6 +208,12 @@ class SFMA(TabularAgent):
             'M.replay_batch); Q is updated from replays inside train() only — call train() for '
             'replays with TD updates')
 
+    def rollout(self, interface, trials: int, steps: int):
+        """Not served: SFMA's test loop selects with ``policy`` and runs in ``cobel_sfma_run``."""
+        raise NotImplementedError(
+            'rollout() records the test sessions of QAgent and DynaQ (cobel_tab_rollout); SFMA\'s '
+            'sessions run in its own kernel, which keeps no trajectory record')
+
     def test(self, interface, trials: int, steps: int) -> None:
         # agent/sfma.py:369: the test loop selects with self.policy
         self._session(interface, trials, steps, 0, False, pol=self.policy,

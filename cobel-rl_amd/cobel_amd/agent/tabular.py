@@ -94,7 +94,7 @@ class TabularAgent(FusedAgent):
         return 0.9
 
     def _launch(self, interface, pol, flags, trials_target, steps, budget, batch,
-                describe=None) -> None:
+                describe=None, record=None) -> None:
         run = _lib.TabRun()
         self._fill_run(run, interface, flags, trials_target, steps, budget)
         run.q = _lib.ptr(self._q)
@@ -117,12 +117,54 @@ class TabularAgent(FusedAgent):
             pair = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             pair[0].record()
         # (the entry point SURVEY.md section 8b names for this agent: cobel_tab_run with the kind checked)
-        entry = (_lib.lib().cobel_dynaq_run if self.agent_kind == _lib.AGENT_DYNAQ
-                 else _lib.lib().cobel_q_run)
-        _lib.check(entry(interface.handle.ptr, C.byref(run), _lib.current_stream(self.device)))
+        if record is not None:      # rollout(): the same run struct around a trajectory record
+            ro = self._rollout_struct(run, record, interface.handle.ptr)
+            _lib.check(_lib.lib().cobel_tab_rollout(interface.handle.ptr, C.byref(ro),
+                                                    _lib.current_stream(self.device)))
+        else:
+            entry = (_lib.lib().cobel_dynaq_run if self.agent_kind == _lib.AGENT_DYNAQ
+                     else _lib.lib().cobel_q_run)
+            _lib.check(entry(interface.handle.ptr, C.byref(run), _lib.current_stream(self.device)))
         if pair is not None:
             pair[1].record()
             ev.append(pair)
+
+    # -- a test session that records ----------------------------------------------------------------
+    rollout_element_stores = False   # True: one store per record entry (tests, A/B comparisons)
+
+    def _rollout_struct(self, run: _lib.TabRun, record, world) -> _lib.TabRollout:
+        ro = _lib.TabRollout()
+        ro.run = run
+        ro.start, ro.states = _lib.ptr(record.start), _lib.ptr(record.states)
+        ro.actions, ro.length = _lib.ptr(record.actions), _lib.ptr(record.length)
+        ro.trials, ro.steps = record.trials, record.steps
+        ro.record_flags = _lib.ROLLOUT_ELEMENT_STORES if self.rollout_element_stores else 0
+        out = (C.c_int32 * 4)()
+        _lib.check(_lib.lib().cobel_tab_rollout_plan(world, C.byref(ro), out))
+        self.rollout_plan = {'lds_bytes': int(out[0]), 'threads_per_workgroup': int(out[1]),
+                             'instances_per_workgroup': int(out[2]), 'workgroups': int(out[3])}
+        return ro
+
+    def rollout(self, interface, trials: int, steps: int):
+        """``test(interface, trials, steps)`` that also returns what every instance did, as a
+        ``monitor.TrajectoryRecord`` on the device: the same draws, monitors, counters and final
+        state, one launch (``cobel_tab_rollout``) whatever the instance count, ``Q`` untouched.
+        Trial callbacks fire as in a vectorised session — ``on_trial_begin`` for every trial before
+        the launch, ``on_trial_end`` after it with the means over instances; step callbacks do not
+        fire: the record holds what they would have seen (``record.trajectory(i, t)``,
+        ``TrajectoryMonitor.update_from_device(record)``)."""
+        from ..monitor.trajectory import TrajectoryRecord
+        trials, steps = int(trials), int(steps)
+        if hasattr(interface, 'seq'):
+            raise NotImplementedError('rollout records sessions on a Gridworld or a Topology')
+        if trials < 1 or steps < 1:
+            raise IndexError('rollout: trials = %d, steps = %d (both at least 1)' % (trials, steps))
+        pol, flags, first = self._session_begin(interface, trials, False)
+        record = TrajectoryRecord(interface, self.n_envs, trials, steps, self.device, first)
+        self._one_launch_session(first, trials, lambda: self._launch(
+            interface, pol, flags, first + trials, steps, 0, 0, record=record))
+        self._session_end(pol, interface)
+        return record
 
     def check_launches(self) -> None:
         """Waits for this agent's launches and raises ``CobelHipError`` if a sliced launch of the

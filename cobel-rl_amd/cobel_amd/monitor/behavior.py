@@ -121,6 +121,12 @@ class TrajectoryMonitor(Monitor):
             self.trajectory_trace.append([])
         self.trajectory_trace[-1].append(self.env.get_position())
 
+    def update_from_device(self, record, instances=None) -> None:
+        """Append what ``update`` would have collected over the session of a ``TrajectoryRecord``
+        (``agent.rollout``): one list of positions per trial and instance, instance-major — all
+        trials of the first instance, then the second's — for ``instances`` (all when None)."""
+        self.trajectory_trace.extend(record.trajectories(instances))
+
     def get_trace(self):
         return self.trajectory_trace
 

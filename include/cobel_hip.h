@@ -553,6 +553,58 @@ COBEL_API int cobel_model_store(uint64_t* model /* [dev] [N][S][4] */,
                                 double model_lr, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * A test session that records.  The reference's TrajectoryMonitor (monitor/behavior.py:304-385)
+ * appends env.get_position() at every on_step_end; step hooks cannot fire inside a launch, so
+ * vectorised test runs report sums only.  cobel_tab_rollout is the test session of cobel_tab_run
+ * (COBEL_F_LEARN clear: select with the test policy, step, count — agent/dyna_q.py:217-273,
+ * agent/q.py:230-287) for QAgent and Dyna-Q on worlds of 1..32 actions, with every draw, counter,
+ * monitor and inst word as cobel_tab_run leaves them, that also keeps what each instance did:
+ * for instance i and session trial t (t = trial index - (run.trials_target - trials)),
+ *   start  [i][t]      the state after the reset
+ *   states [i][t][k]   the state entered by step k
+ *   actions[i][t][k]   the action of step k
+ *   length [i][t]      steps executed (logs['steps'] + 1)
+ * and 0xffff / 0xff (-1 / 255) in states / actions at k >= length: the call fills both arrays
+ * with 0xff bytes in stream order before its one kernel launch.  Q is read, never written; model,
+ * replay_log, scratch, last_exp, batch and batches_done of the run are ignored.  Every instance
+ * is expected at a trial boundary (inst[COBEL_I_FLAGS] bit 0 clear) of trial trials_target -
+ * trials; a trial outside the session's range runs and counts but leaves no record.
+ * One lane per instance (k_tab_rollout, rollout.hip), Q rows read from device memory.
+ * ------------------------------------------------------------------------------------------ */
+#define COBEL_ROLLOUT_ELEMENT_STORES 1u /* record_flags: store every record entry on its own (2- and
+                                           1-byte stores) instead of four steps at a time as one 8-byte
+                                           and one 4-byte store (testing, A/B measurements)          */
+typedef struct {
+  cobel_tab_run_t run;   /* the session, as cobel_tab_run takes it                              */
+  int16_t* start;        /* [N][trials]          2-byte aligned                                 */
+  int16_t* states;       /* [N][trials][steps]   8-byte aligned                                 */
+  uint8_t* actions;      /* [N][trials][steps]   4-byte aligned                                 */
+  int32_t* length;       /* [N][trials]          4-byte aligned                                 */
+  int32_t trials;        /* trials of this session (>= 1)                                       */
+  int32_t steps;         /* steps per trial (>= 1): run.steps_per_trial must equal it           */
+  uint32_t record_flags; /* COBEL_ROLLOUT_*                                                     */
+  int32_t reserved_;
+} cobel_tab_rollout_t;
+/* COBEL_E_ARG: a NULL argument, record array or q; COBEL_F_LEARN set; step_budget != 0; a
+ * misaligned q (16 bytes in four-action worlds, else 4), inst or record array; steps_per_trial !=
+ * steps.  COBEL_E_RANGE: trials < 1, steps < 1, n < 0, trials_target < trials, trial_cap <
+ * trials_target.  COBEL_E_UNSUPPORTED: more than COBEL_MAX_ACTIONS actions.  All before any launch. */
+COBEL_API int cobel_tab_rollout(const cobel_world_t* world, const cobel_tab_rollout_t* rollout,
+                                void* stream);
+/* The same checks without a launch: out = {LDS bytes per workgroup (0), threads per workgroup,
+ * instances per workgroup, workgroups}; all zero for n = 0. */
+COBEL_API int cobel_tab_rollout_plan(const cobel_world_t* world,
+                                     const cobel_tab_rollout_t* rollout, int32_t out[4]);
+/* Visit counts of a record: counts[w][s] += entries of `states` equal to s among the instances of
+ * world w = (instance_base + i) % n_worlds (what cobel_tab_run adds to `occupancy` over the same
+ * session).  Entries outside 0 .. n_states - 1 (the padding) are skipped. */
+COBEL_API int cobel_rollout_visits(const int16_t* states /* [dev] [N][per_instance] */, int32_t n,
+                                   int64_t per_instance, int32_t n_states, int32_t n_worlds,
+                                   uint32_t instance_base,
+                                   unsigned long long* counts /* [dev] [n_worlds][n_states] */,
+                                   void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Successor-representation agent.  Replaces SR.train / SR.update / SR.retrieve_q
  * (agent/sr.py:142-197, :255-286, :288-308).  Tables: SR f32 [N][S][S] (= eye at init),
  * agent transition table T u16 [N][S][4] (= s at init, sr.py:131-135), reward estimate
