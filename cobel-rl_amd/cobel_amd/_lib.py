@@ -285,6 +285,7 @@ class SFMAMem(C.Structure):
 
 PMA_MAX_STATES, PMA_MAX_ACTIONS = 128, 8
 PMA_WIDE_MAX_STATES = 1024
+PMA_MAX_SEQ = 256
 (PMA_EQUAL_NEED, PMA_EQUAL_GAIN, PMA_IGNORE_BARRIERS, PMA_ALLOW_LOOPS, PMA_GAIN_ORIGINAL,
  PMA_SHARED_POLICY, PMA_WIDE) = (1 << k for k in range(7))
 
@@ -616,6 +617,12 @@ _SIGNATURES = {
     'cobel_pma_plan_need': (C.c_int, [C.c_int32, C.POINTER(C.c_int32 * 2)]),
     'cobel_pma_stationary_wide': (C.c_int, [C.POINTER(PMAMem), _P, _P, _P, _P, C.c_int64, _P]),
     'cobel_pma_plan_need_wide': (C.c_int, [C.c_int32, C.POINTER(C.c_int64 * 4)]),
+    'cobel_pma_gain_batch': (C.c_int, [C.POINTER(PMAMem), _P, C.c_int64, _P, _P]),
+    'cobel_pma_gain_seq': (C.c_int, [C.POINTER(PMAMem), _P, C.c_int64, _P, _P, C.c_int32,
+                                     C.c_int32, C.c_int64, _P, _P]),
+    'cobel_pma_action_probs': (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_double, _P, _P]),
+    'cobel_pma_update_q': (C.c_int, [C.POINTER(PMAMem), _P, _P, _P, C.c_int32, C.c_int64,
+                                     C.c_double, _P, C.c_int32, _P]),
     'cobel_metric_sr': (C.c_int, [_P, C.c_int32, C.c_int32, C.c_double, _P, _P]),
     'cobel_metric_dr': (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_double,
                                   _P, _P, C.c_int64, _P]),

@@ -101,8 +101,15 @@ class PMA(FusedAgent):
 
     def update_q(self, update: list) -> None:
         """agent/pma.py:319-353 for a given n-step list of experiences, applied to every instance:
-        a host call for use between sessions (inside ``train`` the 1-step update is part of the
-        trial kernel)."""
+        for use between sessions (inside ``train`` the 1-step update is part of the trial
+        kernel).  Once the agent has device tables it is one device call, ``cobel_pma_update_q``
+        with the agent's learning rate and ``gamma ** k``, the same bits as the host loop below,
+        which serves the agent that has not run yet."""
+        if self._q is not None:
+            pows = torch.as_tensor(np.array([self.gamma ** k for k in range(len(update) + 1)],
+                                            dtype=np.float64), device=self.device)
+            self.M._update_q_device(self._q, update, self.learning_rate, pows)
+            return
         q = np.array(self.Q.cpu().numpy() if torch.is_tensor(self.Q) else self.Q)
         for Q in q.reshape(-1, self.n_states, self.n_actions):
             future_value = np.amax(Q[update[-1]['next_state']]) * update[-1]['terminal']

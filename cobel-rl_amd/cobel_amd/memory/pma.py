@@ -7,6 +7,21 @@ kernel (``cobel_pma_trial``).  A memory is bound to a device by the agent's firs
 without an agent, by ``bind``.  Every table is float64, as the reference's are.  The host
 plumbing shared with ``SFMAMemory`` (``bind``, argument checks, records) is memory/_device.py's.
 
+The observables of the model are device calls of their own (csrc/pma_gain.hip), the expressions the
+replay kernel evaluates every round, bit for bit, on tables read in place — so one form serves
+the default and the wide memory, up to 1 024 states:
+
+  ``compute_gain_batch(q_function, action_mask)``   the gain of every one-step backup, [A * S]
+  ``compute_gain(q_function, action_mask, updates)``   the gain of given n-step updates, of up to
+                                                    ``_lib.PMA_MAX_SEQ`` steps each
+  ``action_probs_batch(q_function, action_mask=None)``   normalised epsilon-greedy rows of any table
+  ``update_q(q_function, update)``                  the n-step update, in place
+
+``q_function`` is one [S, A] table for every instance or [N, S, A]; results are NumPy for a memory
+of one instance and device tensors with a leading instance axis for several.  None of them draws a
+number or moves a counter.  ``equal_gain`` does not touch them: the reference applies it in
+``replay``.
+
 Tables (one leading instance axis on the device; the attributes return NumPy snapshots, squeezed
 for one instance, and assigning uploads):
 
@@ -392,6 +407,155 @@ class PMAMemory(_device.DeviceMemory):
         if n == 1:
             return ups[0], q[0].cpu().numpy()
         return ups, q
+
+    # -- the observables: gain maps, n-step gains, action probabilities, update_q -----------------
+    def _q_tables(self, q_function, who: str):
+        """``q_function`` [S, A] (one table for every instance) or [N, S, A], NumPy or tensor ->
+        (float64 device tensor, the ``q_stride`` of the C calls)."""
+        S, A = self.nb_states, self.nb_actions
+        if torch.is_tensor(q_function):
+            q = q_function.to(device=self.device, dtype=torch.float64)
+        else:
+            q = torch.as_tensor(np.asarray(q_function, dtype=np.float64), device=self.device)
+        if tuple(q.shape) == (S, A):
+            return q.contiguous(), 0
+        if tuple(q.shape) == (self.n_envs, S, A):
+            return q.contiguous(), S * A
+        raise ValueError('%s: q_function of shape %s — [%d, %d] or [%d, %d, %d] is expected'
+                         % (who, tuple(q.shape), S, A, self.n_envs, S, A))
+
+    def _sequences(self, updates: list, who: str):
+        """A list of n-step updates (lists of experience dicts of scalars or [N] arrays) as the
+        record tensor [rows, len(updates), max_len] — rows = 1 where every value is a scalar, N
+        otherwise — with the lengths int32 [rows, len(updates)] (host) and ``max_len``.  An
+        instance whose ``state`` entry is None or negative from some step on has a shorter
+        sequence."""
+        n, S = self.n_envs, self.nb_states
+        for update in updates:
+            if len(update) == 0:
+                raise IndexError('%s: an update without steps (update[-1] of an empty list)' % who)
+        max_len = max([len(u) for u in updates], default=1)
+        if max_len > _lib.PMA_MAX_SEQ:
+            raise NotImplementedError('%s: an update of %d steps — this version serves sequences '
+                                      'of up to %d steps' % (who, max_len, _lib.PMA_MAX_SEQ))
+        per = any(np.ndim(v) > 0 for u in updates for step in u for v in step.values())
+        rows = n if per else 1
+        rec = np.zeros((rows, len(updates), max_len), dtype=RECORD)
+        lengths = np.zeros((rows, len(updates)), dtype=np.int32)
+        limits = {'state': S, 'action': self.nb_actions, 'next_state': S}
+        for k, update in enumerate(updates):
+            for j, step in enumerate(update):
+                rec[:, k, j] = _device.records(step, rows, RECORD, limits, none_as=-1)
+            valid = rec['state'][:, k, :len(update)] >= 0
+            lengths[:, k] = valid.sum(axis=1)
+            if (lengths[:, k] < 1).any() or \
+                    (valid != (np.arange(len(update))[None, :] < lengths[:, k, None])).any():
+                raise IndexError('%s: the steps of an instance are the first ones of the update, '
+                                 'at least one' % who)
+        steps = torch.as_tensor(np.ascontiguousarray(rec).view(np.uint8).reshape(-1),
+                                device=self.device)
+        return steps, lengths, max_len, per
+
+    def compute_gain_batch(self, q_function, action_mask):
+        """memory/pma.py:333-386 on the device (``cobel_pma_gain_batch``): the gain of every
+        one-step backup, index ``a * S + s``.  ``q_function`` is [S, A] (every instance scores the
+        same table) or [N, S, A], NumPy or a device tensor.  Returns NumPy [A * S] for one
+        instance, a float64 device tensor [N, A * S] for several."""
+        assert self._is_bound, _device.NOT_BOUND
+        q, stride = self._q_tables(q_function, 'compute_gain_batch')
+        gain = torch.empty((self.n_envs, self.nb_actions * self.nb_states), dtype=torch.float64,
+                           device=self.device)
+        bits = self._mask_bits(action_mask)
+        m = self._mem(None, bits)
+        _lib.check(_lib.lib().cobel_pma_gain_batch(C.byref(m), _lib.ptr(q), stride, _lib.ptr(gain),
+                                                   _lib.current_stream(self.device)))
+        return gain[0].cpu().numpy() if self.n_envs == 1 else gain
+
+    def compute_gain(self, q_function, action_mask, updates: list):
+        """memory/pma.py:269-331 on the device (``cobel_pma_gain_seq``): the gain of each n-step
+        update of ``updates``, a list of lists of experience dicts whose values are scalars or [N]
+        arrays (per-instance steps; a ``state`` of None or < 0 ends that instance's sequence
+        early).  Returns NumPy [len(updates)] for one instance, a float64 device tensor
+        [N, len(updates)] for several."""
+        assert self._is_bound, _device.NOT_BOUND
+        q, stride = self._q_tables(q_function, 'compute_gain')
+        steps, lengths, max_len, per = self._sequences(updates, 'compute_gain')
+        n_seq = len(updates)
+        gain = torch.empty((self.n_envs, n_seq), dtype=torch.float64, device=self.device)
+        if n_seq == 0:
+            return gain[0].cpu().numpy() if self.n_envs == 1 else gain
+        bits = self._mask_bits(action_mask)
+        m = self._mem(None, bits, max_len)
+        _lib.check(_lib.lib().cobel_pma_gain_seq(
+            C.byref(m), _lib.ptr(q), stride, _lib.ptr(steps), _lib.ptr(lengths), n_seq, max_len,
+            n_seq * max_len if per else 0, _lib.ptr(gain), _lib.current_stream(self.device)))
+        return gain[0].cpu().numpy() if self.n_envs == 1 else gain
+
+    def action_probs_batch(self, q_function, action_mask=None):
+        """memory/pma.py:423-450 on the device (``cobel_pma_action_probs``): the policy's
+        epsilon-greedy probabilities of every row of a [rows, A] table, each row divided by its
+        sum; ``action_mask`` is [rows, A] booleans or None.  NumPy in gives NumPy out, a tensor in
+        a tensor out.  Needs no bound memory."""
+        is_tensor = torch.is_tensor(q_function)
+        if is_tensor and q_function.is_cuda:
+            dev = q_function.device
+        else:
+            dev = self.device or torch.device('cuda', torch.cuda.current_device())
+        if is_tensor:
+            q = q_function.to(device=dev, dtype=torch.float64).contiguous()
+        else:
+            q = torch.as_tensor(np.asarray(q_function, dtype=np.float64), device=dev).contiguous()
+        if q.dim() != 2 or not 1 <= q.shape[1] <= _lib.PMA_MAX_ACTIONS:
+            raise ValueError('action_probs_batch: q_function of shape %s — [rows, A] with up to %d '
+                             'actions is expected' % (tuple(q.shape), _lib.PMA_MAX_ACTIONS))
+        rows, A = int(q.shape[0]), int(q.shape[1])
+        bits = None
+        if action_mask is not None:
+            mask = action_mask.cpu().numpy() if torch.is_tensor(action_mask) else action_mask
+            bits = torch.as_tensor(_device.mask_bits(mask, rows, A), device=dev)
+        probs = torch.empty((rows, A), dtype=torch.float64, device=dev)
+        _lib.check(_lib.lib().cobel_pma_action_probs(
+            _lib.ptr(q), _lib.ptr(bits), rows, A, float(self.policy.epsilon), _lib.ptr(probs),
+            _lib.current_stream(dev)))
+        return probs if is_tensor else probs.cpu().numpy()
+
+    def _update_q_device(self, q, update: list, learning_rate: float, pow_table) -> None:
+        """``cobel_pma_update_q`` IN PLACE on the device tensor ``q`` [N, S, A] with the caller's
+        learning rate and power table (a float64 device tensor, entry k = discount ** k)."""
+        steps, lengths, max_len, per = self._sequences([update], 'update_q')
+        m = self._mem()
+        _lib.check(_lib.lib().cobel_pma_update_q(
+            C.byref(m), _lib.ptr(q), _lib.ptr(steps), _lib.ptr(lengths), max_len,
+            max_len if per else 0, float(learning_rate), pow_table.data_ptr(),
+            int(pow_table.numel()), _lib.current_stream(self.device)))
+
+    def update_q(self, q_function, update: list):
+        """memory/pma.py:452-496 on the device (``cobel_pma_update_q``): the n-step update of
+        ``update`` (experience dicts of scalars or [N] arrays) with ``learning_rate_q`` and
+        ``gamma_q``.  A float64 device tensor [N, S, A] is updated in place and returned; a NumPy
+        array ([S, A] for one instance, [N, S, A]) is updated in place as the reference mutates
+        its argument, and returned."""
+        assert self._is_bound, _device.NOT_BOUND
+        n, S, A = self.n_envs, self.nb_states, self.nb_actions
+        shape = tuple(q_function.shape) if hasattr(q_function, 'shape') else np.shape(q_function)
+        if shape != (n, S, A) and not (n == 1 and shape == (S, A)):
+            raise ValueError('update_q: q_function of shape %s — [%d, %d, %d]%s is expected'
+                             % (shape, n, S, A, ' or [%d, %d]' % (S, A) if n == 1 else ''))
+        pows = self._power_tables(len(update))[1]
+        if torch.is_tensor(q_function):
+            if (q_function.dtype != torch.float64 or q_function.device != self.device
+                    or not q_function.is_contiguous()):
+                raise ValueError('update_q: a tensor is updated in place — a contiguous float64 '
+                                 'tensor on %s is expected' % (self.device,))
+            self._update_q_device(q_function, update, self.learning_rate_q, pows)
+            return q_function
+        q = torch.as_tensor(np.asarray(q_function, dtype=np.float64), device=self.device)
+        q = q.reshape((n, S, A)).contiguous()
+        self._update_q_device(q, update, self.learning_rate_q, pows)
+        if isinstance(q_function, np.ndarray):
+            q_function[...] = q.cpu().numpy().reshape(shape)
+            return q_function
+        return q.cpu().numpy().reshape(shape)
 
     def compute_need(self, current_state=None, instances=None):
         """memory/pma.py:388-411.  ``None``: the unit-2-norm stationary vector of T of

@@ -1345,6 +1345,57 @@ COBEL_API int cobel_pma_stationary_wide(const cobel_pma_mem_t* mem, const int32_
  * COBEL_E_UNSUPPORTED outside 1 .. COBEL_PMA_WIDE_MAX_STATES, with out zeroed. */
 COBEL_API int cobel_pma_plan_need_wide(int32_t n_states, int64_t out[4]);
 
+/* The observables of the memory as calls of their own (csrc/pma_gain.hip): the gain map, the gain
+ * of given n-step updates, the action probabilities of a table and the n-step update_q.  The same
+ * expressions, operation for operation, as cobel_pma_replay evaluates every round.  All four read
+ * their tables in place from device memory, so one form serves 1 .. COBEL_PMA_WIDE_MAX_STATES
+ * states and 1 .. COBEL_PMA_MAX_ACTIONS actions (COBEL_PMA_WIDE in flags is not looked at), draw
+ * no number and move no counter.  Every refusal comes before any launch: COBEL_E_ARG for a NULL
+ * or misaligned argument, a stride that is none of those named, an epsilon outside [0, 1] or power
+ * tables of pow_len <= the longest sequence; COBEL_E_UNSUPPORTED for a state or action count
+ * outside the range and a max_len outside 1 .. COBEL_PMA_MAX_SEQ; COBEL_E_RANGE for n, n_seq or
+ * rows < 0 and a length outside 1 .. max_len.
+ * A sequence is cobel_pma_rec_t[max_len], valid up to its length; states, actions and successors
+ * outside the world are clamped into it.  lengths is [host]: it is checked by the call and
+ * travels to the device in the stream (the call waits for that copy where the array is not
+ * pinned). */
+#define COBEL_PMA_MAX_SEQ 256          /* steps of one sequence of cobel_pma_gain_seq / _update_q */
+/* PMAMemory.compute_gain_batch (memory/pma.py:333-386) per instance: the gain of every one-step
+ * backup, clipped at min_gain.  q [dev] [N][S][A] with q_stride = S * A, or one [S][A] table for
+ * every instance with q_stride = 0; gain [dev] [N][A * S] out, index a * S + s.  Reads
+ * mem->rewards, states, terminals, action_mask, learning_rate_q, gamma_q, min_gain and epsilon;
+ * mem->q and COBEL_PMA_EQUAL_GAIN are not looked at (the reference applies equal_gain in replay). */
+COBEL_API int cobel_pma_gain_batch(const cobel_pma_mem_t* mem, const double* q, int64_t q_stride,
+                                   double* gain, void* stream);
+/* PMAMemory.compute_gain (memory/pma.py:269-331) for n_seq n-step updates per instance.  steps
+ * [dev] [n_seq][max_len] and lengths [host] [n_seq] with inst_stride = 0 (every instance scores the
+ * same list), or [N][n_seq][max_len] and [N][n_seq] with inst_stride = n_seq * max_len; gain [dev]
+ * [N][n_seq] out.  As in the reference the rewards are discounted by mem->gamma_pow (gamma ** k)
+ * and the bootstrap — the unmasked row maximum times the last step's terminal — by
+ * mem->gamma_q_pow (gamma_q ** (n - j)), the policies are not normalised, a step gain is clipped at
+ * min_gain only under COBEL_PMA_GAIN_ORIGINAL, the sum (step 0 first) always. */
+COBEL_API int cobel_pma_gain_seq(const cobel_pma_mem_t* mem, const double* q, int64_t q_stride,
+                                 const cobel_pma_rec_t* steps, const int32_t* lengths,
+                                 int32_t n_seq, int32_t max_len, int64_t inst_stride, double* gain,
+                                 void* stream);
+/* PMAMemory.action_probs_batch (memory/pma.py:423-450): the epsilon-greedy probabilities
+ * (policy/greedy.py:77-86) of every row, divided by the row's sum.  q, probs [dev] [rows][A];
+ * mask_bits [dev] [rows] (bit a = action a allowed) or NULL.  Any row count: the reference calls
+ * it with the tiled [A * S][A] table. */
+COBEL_API int cobel_pma_action_probs(const double* q, const uint8_t* mask_bits, int64_t rows,
+                                     int32_t n_actions, double epsilon, double* probs, void* stream);
+/* The n-step update_q of PMAMemory (memory/pma.py:452-496: learning_rate_q, gamma_q ** k) and of
+ * the PMA agent (agent/pma.py:319-353: learning_rate, gamma ** k), in place on q [dev] [N][S][A]:
+ * one sequence per instance, steps [dev] [N][max_len] and lengths [host] [N] with inst_stride =
+ * max_len, or one for all with inst_stride = 0.  The bootstrap value is read before any write, the
+ * steps are applied in order (a repeated (s, a) sees the earlier write), and a sequence of more
+ * than one step that holds a terminal == 0 changes nothing (:476-489).  pow_table [dev] [pow_len].
+ * Reads mem->n, n_states and n_actions only. */
+COBEL_API int cobel_pma_update_q(const cobel_pma_mem_t* mem, double* q,
+                                 const cobel_pma_rec_t* steps, const int32_t* lengths,
+                                 int32_t max_len, int64_t inst_stride, double learning_rate,
+                                 const double* pow_table, int32_t pow_len, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * The similarity metrics of SFMA (memory/utils/metrics.py:66-268) for stacks of four-action worlds
  * given by their compact successor tables: SR.D = inv(I - gamma T) (:66-105) and DR.D, the same
