@@ -172,6 +172,7 @@ __device__ __forceinline__ void pwg_instance(const pwg_args& A, const int i, con
   const uint32_t* const model32 = reinterpret_cast<const uint32_t*>(model);
   const uint32_t SA = (uint32_t)S * 4u;
   uint16_t* const Mg = A.r.model_index + (size_t)i * SA;
+  const uint32_t* const Mg32 = reinterpret_cast<const uint32_t*>(Mg);
   // Lane constants in vector registers where the compiler would keep lane masks in scalar pairs
   // (the step loop is short of those: masks it spilled were reloaded in every step): lane l reads
   // successor l % 4 of a packed record pair as bfe(bfi(sel, w1, w0), sh, 16).
@@ -239,6 +240,10 @@ __device__ __forceinline__ void pwg_instance(const pwg_args& A, const int i, con
   asm volatile("" : "+v"(seed_v));
   auto seed_now = [&]() -> uint64_t { return seed_v; };
 #endif
+  // (held in a scalar register: read through the argument, it was fetched again — a scalar load
+  //  and its wait — in every step of one build)
+  uint32_t store_always = A.store_always;
+  asm volatile("" : "+s"(store_always));
   double alpha = A.r.alpha, gamma = A.r.gamma;
   float alpha_f = A.alpha_f, gamma_f = A.gamma_f, mlr_f = A.model_lr_f;
   asm volatile("" : "+v"(alpha), "+v"(gamma), "+v"(alpha_f), "+v"(gamma_f), "+v"(mlr_f));
@@ -248,7 +253,10 @@ __device__ __forceinline__ void pwg_instance(const pwg_args& A, const int i, con
   uint4 cand = {0, 0, 0, 0};
   cobel_u4 blk = {0, 0, 0, 0};
   int refresh_in = 0;
-  uint2 mdig = {0u, 0u};   // the four digest entries of the current state (requested a step ahead)
+  // the digest entries of the current state (requested a step ahead): lane l holds the aligned
+  // word with entry l % 4 — the one its successor `succ_of` leads through —, so the entry of the
+  // action taken is a shift by `succ_sh` and ONE readlane, as the successor itself
+  uint32_t mdig = 0u;
   uint32_t fix_sa = ~0u;   // the pair this ticket last stored to ...
   float fix_r = 0.0f;      // ... and its reward estimate
   uint32_t idx_cur = 0, mg_cur = 0;
@@ -273,7 +281,7 @@ __device__ __forceinline__ void pwg_instance(const pwg_args& A, const int i, con
     cw0 = rfl(c.x);
     cw1 = rfl(c.y);
     cand = W4[succ_of(cw0, cw1)];   // (every lane: successor lane % 4; four distinct lines)
-    mdig = *reinterpret_cast<const uint2*>(&Mg[(uint32_t)s * 4u]);
+    mdig = Mg32[(uint32_t)s * 2u + (qlane >> 1)];
   };
   // ---- the start of the NEXT trial, carried ahead ------------------------------------------------
   // Where trial k + 1 starts depends on nothing trial k does: seed, instance, the ENV counter `ce`
@@ -326,7 +334,7 @@ __device__ __forceinline__ void pwg_instance(const pwg_args& A, const int i, con
     cw0 = nx_w0;
     cw1 = nx_w1;
     cand = W4[succ_of(cw0, cw1)];   // (every lane: successor lane % 4; four distinct lines)
-    mdig = *reinterpret_cast<const uint2*>(&Mg[nx_state * 4u]);
+    mdig = Mg32[nx_state * 2u + (qlane >> 1)];
     ce += 1u;
     step = 0;
     trew = 0.0;
@@ -336,7 +344,18 @@ __device__ __forceinline__ void pwg_instance(const pwg_args& A, const int i, con
   // the float64 planning update (NumPy promotion of dyna_q.py:290-299 with a float32 table)
   auto plan_td = [&](float q, float m, float r, uint32_t nt) -> float {
     const double gnt = gamma * (double)nt;
-    double td = (double)r + gnt * (double)m;
+    // (the operand order of this sum is fixed: with a model_lr that is not finite both terms can be
+    //  NaNs of different sign, which of them the sum returns depends on their order, and the
+    //  compiler commutes the operands of a plain `+` from build to build.  Product first is what
+    //  agrees with k_tab_wpi bit for bit; with the reward first ten cells of one instance of
+    //  tests/test_gpu_pwg_step_front.py came out as NaNs of the other sign)
+    const double prod = gnt * (double)m, rd = (double)r;
+    double td;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("v_add_f64 %0, %1, %2" : "=v"(td) : "v"(prod), "v"(rd));
+#else
+    td = prod + rd;
+#endif
     td = td - (double)q;
     return (float)((double)q + alpha * td);
   };
@@ -577,7 +596,7 @@ __device__ __forceinline__ void pwg_instance(const pwg_args& A, const int i, con
   //            keeps (cp - cm) % 4 == 0 for good; calls that draw from one stream alone (replay
   //            between sessions, evaluation) may leave the counters apart, and such an instance
   //            stays with PH = -1.
-  auto env_step = [&](auto ph) __attribute__((always_inline)) -> bool {
+  auto env_step = [&](auto ph) __attribute__((always_inline)) -> uint32_t {
     constexpr int PH = decltype(ph)::value;
     // ---- draws ----------------------------------------------------------------------------------
     uint32_t w0, w1;
@@ -617,6 +636,10 @@ __device__ __forceinline__ void pwg_instance(const pwg_args& A, const int i, con
       qc = Qf[(uint32_t)state * 4u + qlane];
       srow = Qs[succ];
     }
+    // (the draw's part of the selection depends on nothing read from Q: formed here, in front of
+    //  the wait for the reads above, not behind it)
+    unsigned long long passed = __ballot(thr_mine <= cobel_u53(w0, w1));
+    asm volatile("" : "+s"(passed));
     const float smax = max4(srow);
 
     // ---- select (policy/greedy.py:40-88): integer thresholds of the tie pattern's CDF ---------------
@@ -636,12 +659,10 @@ __device__ __forceinline__ void pwg_instance(const pwg_args& A, const int i, con
           : "=&v"(m)
           : "v"(qc));
       const int t = (int)((uint32_t)__ballot(qc == m) & 15u);
-      const uint64_t K = cobel_u53(w0, w1);
-      const unsigned long long passed = __ballot(thr_mine <= K);
       a = __popcll((passed >> (t * 3)) & 7ull);
     }
     // ---- env.step (interface/gridworld.py:115-126) --------------------------------------------------
-    const int ns = (int)next_of(cw0, cw1, a);
+    const int ns = (int)rl(succ, a);   // (lane a holds successor a: no select between the record's words)
     const uint32_t nw0 = rl(cand.x, a), nw1 = rl(cand.y, a);
     const uint32_t r_bits = rl(cand.z, a);
     const float r = __builtin_bit_cast(float, r_bits);
@@ -649,7 +670,7 @@ __device__ __forceinline__ void pwg_instance(const pwg_args& A, const int i, con
     // add and selects in every step).  The reward total: `trew` starts a trial at +0.0, and a sum
     // rounded to nearest that starts there is never -0.0, so adding r = +0.0f changes nothing;
     // -0.0f has bits and is added.
-    uint32_t never = A.store_always;   // (bit 16 where this step's model store cannot be skipped: below)
+    uint32_t never = store_always;   // (bit 16 where this step's model store cannot be skipped: below)
     if (__builtin_expect(r_bits != 0u, 0)) {
       iflags |= 2u;
       trew += (double)r;
@@ -660,10 +681,18 @@ __device__ __forceinline__ void pwg_instance(const pwg_args& A, const int i, con
     const float ns_max = __builtin_bit_cast(float, rl(fbits(smax), a));
     const uint32_t nt = 1u - end;
     const uint32_t sa = (uint32_t)state * 4u + (uint32_t)a;
+    // ---- the step-end word: bit 0 = the trial is over, bit 1 = this step stored its model record ----
+    // ONE scalar word and one test of zero at the step's end; as two conditions the compiler kept
+    // 64-bit lane masks (nine scalar instructions per step).  `left` < 0: the trial's last step,
+    // step + 1 >= steps_per_trial (the launcher requires steps_per_trial > 0, so nothing
+    // overflows); its sign bit goes through an opaque scalar, or the compiler turns the shift back
+    // into a compare and a select.
     // (`step` is the same in every lane, but the compiler does not prove it: said here, because
     //  the callers branch on this between the copies of the step, and a branch taken for divergent
     //  runs the copies under exec masks)
-    const bool trial_over = end || ((int)rfl((uint32_t)step) + 1 >= A.r.steps_per_trial);
+    int left = A.r.steps_per_trial - 2 - (int)rfl((uint32_t)step);
+    asm("" : "+s"(left));
+    uint32_t stepw = ((uint32_t)left >> 31) | end;
     // (everything the previous step requested is consumed BEFORE this step's requests go out: the
     //  wait for a register loaded across the loop edge is a wait for every load in flight)
     // ---- model store (memory/dyna_q.py:92-96) ---------------------------------------------------------
@@ -685,8 +714,33 @@ __device__ __forceinline__ void pwg_instance(const pwg_args& A, const int i, con
     // bit 16 (set again: it stores).  A step that stores takes the estimate of the pair LAST
     // STORED to, however long ago, from `fix_r` — its record may still be on its way, and a
     // skipped step changes no record —, of a flagged pair from the packed record (never read
-    // otherwise: the records' lines stay out of the L2), and +0.0f else.  A skipped step leaves
-    // `fresh_m` = `dold` and `fresh_r` = +0.0f for the planning patches: what it would have written.
+    // otherwise: the records' lines stay out of the L2), and +0.0f else.
+    // The planning patches.  A planning lane whose pair is the step's own (`sa`) must see what the
+    // step stored: (a) in this step's batch, whose entries `mg_cur` were gathered a step ago; (b) in
+    // the estimate of a flagged pair, whose record may still be on its way; (c) in the next
+    // batch's entries, whose gather goes out behind the store and may pass it.  They run only
+    // where a step stored — (a) in the storing block, (b) in the planning lanes' flagged-entry
+    // block against `fix_sa` / `fix_r`, (c) behind bit 1 of the step-end word — because in a
+    // skipped step they would select what the gathers return anyway:
+    //   * Invariant: every store is complete (vmcnt(0), patch (c)'s block) before the step that
+    //     issued it ends.  So a load issued in step t sees every store of the steps before t, and
+    //     may miss only step t's own.
+    //   * Let step t skip: `dold` == `m_skip`, unflagged, no bit 16.  `dold` was requested in step
+    //     t - 1 in front of that step's store, or behind it (begin_carried, enter_state).  If
+    //     step t - 1 stored to `sa` and the request passed that store — the entry that is one
+    //     store old —, then by the argument above step t stores as well: not this case.  So no
+    //     store to `sa` lies between the request for `dold` and the end of step t (step t itself
+    //     stores nothing), and `dold` is what memory holds at `sa` throughout.
+    //   * (a): `mg_cur` of a lane with idx_cur == sa was gathered in step t - 1 behind that step's
+    //     store and patched by its (c) if it stored to `sa`: it is memory's entry, `dold`.
+    //   * (c): the gather of a lane with idx_next == sa goes out in step t: `dold` again.
+    //   * (b): that lane's entry is `dold`, unflagged: it does not enter the flagged-entry block,
+    //     and its estimate is +0.0f, what the skipped step would have written.
+    //   In a step that stores, (a) and (c) put `fresh_m` where the selects of every step did.  (b): an
+    //   unflagged `fresh_m` means Rn has no bits, the lane's +0.0f; a flagged one sends the lane
+    //   into the block, where `fix_sa` == sa and `fix_r` == Rn.  For a pair stored to in an
+    //   EARLIER step `fix_r` is what its record holds (complete by the invariant; only this wave
+    //   writes it), so taking it from the register there changes nothing either.
     // The estimate and the new entry stay in vector registers, as where every step stored: as
     // scalars (a v_readfirstlane behind the arithmetic) agents with fresh tables, which store in
     // many steps, were slower than with a store in every step.
@@ -694,19 +748,16 @@ __device__ __forceinline__ void pwg_instance(const pwg_args& A, const int i, con
     const uint32_t m_new = (uint32_t)ns | (nt << 14);
     uint32_t m_skip = m_new | never;
     asm volatile("" : "+s"(m_skip));
-    const uint32_t dpair = rfl((a & 2) ? mdig.y : mdig.x);
-    const uint32_t dold = (a & 1) ? (dpair >> 16) : (dpair & 0xffffu);
+    const uint32_t dold = rl((mdig >> succ_sh) & 0xffffu, a);
     __builtin_amdgcn_sched_barrier(0);
     // (unconditional: at a trial's end the two requests are wasted — begin_carried asks again — but a
     //  request under a condition merges with the old value, and the merge is a copy behind a wait
     //  for the answer, a memory round trip per step of the global-memory waves: 25.7 -> 32 ms per
     //  launch of those alone in one build of round 6)
     cand = W4[succ_of(nw0, nw1)];
-    const uint2 mdig_next = *reinterpret_cast<const uint2*>(&Mg[(uint32_t)ns * 4u]);
+    const uint32_t mdig_next = Mg32[(uint32_t)ns * 2u + (qlane >> 1)];
 
-    const uint32_t fresh_idx = sa;
-    uint32_t fresh_m = dold;   // (what a skipped step would have written: the planning patches select from them)
-    float fresh_r = 0.0f;
+    uint32_t fresh_m = 0u;   // (the entry a storing step wrote: read only where bit 1 of `stepw` is set)
     if (__builtin_expect(dold != m_skip, 0)) {
       uint32_t Rb = 0u;
       if ((dold & 0x8000u) != 0u) Rb = rfl(model32[2u * sa]);
@@ -714,7 +765,6 @@ __device__ __forceinline__ void pwg_instance(const pwg_args& A, const int i, con
       if (sa == fix_sa) R = fix_r;
       const float d = r - R;
       const float Rn = R + mlr_f * d;
-      fresh_r = Rn;
       fresh_m = m_new | (fbits(Rn) ? 0x8000u : 0u);
       if (lane == 0) {
         NT_ST(cobel_model_pack(Rn, (uint32_t)ns, nt), &model[sa]);
@@ -722,7 +772,9 @@ __device__ __forceinline__ void pwg_instance(const pwg_args& A, const int i, con
       }
       fix_r = Rn;
       fix_sa = sa;
-      asm volatile("" : "+v"(fresh_r));
+      asm volatile("" : "+v"(fix_r));
+      if (idx_cur == sa) mg_cur = fresh_m;   // patch (a): this step's batch was gathered a step ago
+      stepw |= 2u;
     }
     // ---- online TD (agent/dyna_q.py:290-299), float32 ---------------------------------------------------
     const float q_sa = __builtin_bit_cast(float, rl(fbits(qc), a));
@@ -746,7 +798,7 @@ __device__ __forceinline__ void pwg_instance(const pwg_args& A, const int i, con
     {
       // (lanes >= B keep what they had: none of them reads idx_cur / mg_cur outside `lane < B`)
       uint32_t idx_next = idx_cur, mg_next = mg_cur;
-      const uint32_t m = (idx_cur == fresh_idx) ? fresh_m : mg_cur;
+      const uint32_t m = mg_cur;
       if (lane < B) {
         float rj = 0.0f;
         const uint32_t mword = PH < 0 ? cobel_word(blk, (cm + 1u) & 3u)
@@ -760,18 +812,18 @@ __device__ __forceinline__ void pwg_instance(const pwg_args& A, const int i, con
             // (consumed here: a wait for this rare load after the branches have joined would be a
             //  wait for every gather this step has just sent out)
             asm volatile("" : "+v"(rj));
+            if (idx_cur == fix_sa) rj = fix_r;   // patch (b): that record may still be on its way
           }
-          if (idx_cur == fresh_idx) rj = fresh_r;
           const uint32_t nsj = m & 0x3fffu;
           if (QG) {
             // a pair that replays the entry this very step stored plans towards the state just
             // entered: its row is the successor row read above
-            if (__ballot(idx_cur == fresh_idx)) {
+            if (__ballot(idx_cur == sa)) {
               const float4 nrow = {__builtin_bit_cast(float, rl(fbits(srow.x), a)),
                                    __builtin_bit_cast(float, rl(fbits(srow.y), a)),
                                    __builtin_bit_cast(float, rl(fbits(srow.z), a)),
                                    __builtin_bit_cast(float, rl(fbits(srow.w), a))};
-              if (idx_cur == fresh_idx) prow = nrow;
+              if (idx_cur == sa) prow = nrow;
             }
             // the online update wrote Q[s][a] after these registers were loaded
             if (idx_cur == sa) pq = qn_online;
@@ -786,14 +838,25 @@ __device__ __forceinline__ void pwg_instance(const pwg_args& A, const int i, con
             run_batch_lds(idx_cur, nsj, (m >> 14) & 1u, rj);
           }
         }
-        if (idx_next == fresh_idx) mg_next = fresh_m;   // the gather may have passed the store
       }
       idx_cur = idx_next;
       mg_cur = mg_next;
       mdig = mdig_next;
       if constexpr (PH < 0) cm += 1u;
     }
-    return trial_over;
+    // The common step — nothing stored, the trial goes on — leaves through ONE test of zero.
+    if (__builtin_expect(stepw != 0u, 0)) {
+      if (stepw & 2u) {
+        // patch (c): the gather for the next batch went out behind this step's store and may have
+        // passed it.  Every store is complete before the step that issued it ends (as where the
+        // patch, and with it the wait for the gather, stood in every step): the requests of later
+        // steps see it.
+        stores_done();
+        if (idx_cur == sa) mg_cur = fresh_m;
+      }
+      return stepw & 1u;
+    }
+    return 0u;
   };
 
   // ---- the ticket's steps ---------------------------------------------------------------------------
@@ -805,7 +868,7 @@ __device__ __forceinline__ void pwg_instance(const pwg_args& A, const int i, con
   // first trial end; the counters and `refresh_in` are then what generic steps would have left, so
   // the ONE trial-end block below and a generic step behind it go on exactly.
   while (live) {
-    bool trial_over;
+    uint32_t trial_over;
     if (!QG && ((cp | cm) & 3u) == 0u && budget >= 4) {
       // (`budget` step by step: a ticket that ends inside a group at trials_target reports the
       //  steps it ran; the counters once per group)
