@@ -22,6 +22,11 @@
 //     whose position in the block — which lane and word hold the policy's draw, which word the
 //     planning lanes' pair, where the next evaluation falls — is fixed at compile time (env_step,
 //     PH = 0 .. 3); single generic steps (PH = -1) fill in wherever a group does not fit;
+//   * glue the compiler built around single-lane and rare work is kept off the common step: the
+//     online TD value is formed in front of the one-lane store, not inside its exec-mask region;
+//     a flagged digest entry is found with one compare and a branch on its mask; the lanes'
+//     Philox counters, lane words and streams are lane constants, not a divergent select
+//     (scripts/experiments/pwg_common_step/);
 //   * where the NEXT trial starts is worked out when a trial begins and carried, inside a ticket,
 //     as three scalars (the state and its two world record words): a trial end sends the new
 //     trial's requests at once, reads its arguments in one scalar round trip, and waits neither
@@ -265,7 +270,19 @@ __device__ __forceinline__ void pwg_instance(const pwg_args& A, const int i, con
     const cobel_u4 b = cobel_philox(counter >> 2, (uint32_t)lane, g, COBEL_STREAM_MEMORY, seed_now());
     return cobel_word(b, counter & 3u);
   };
+  // Which counter, lane word and stream a lane's block takes, as lane constants (LDS waves): written
+  // as a select per lane — p1 ? .. : (p0 ? .. : mi) — the compiler built a divergent region of
+  // about fourteen scalar instructions around it, at the top of every group's last step.
+  uint32_t pol_mask = lane >= 62 ? 0xffffffffu : 0u, pol_odd = lane == 63 ? 1u : 0u;
+  uint32_t draw_sub = lane >= 62 ? 0u : (uint32_t)lane;
+  uint32_t draw_stream = lane >= 62 ? COBEL_STREAM_POLICY : COBEL_STREAM_MEMORY;
+  asm volatile("" : "+v"(pol_mask), "+v"(pol_odd), "+v"(draw_sub), "+v"(draw_stream));
   auto refresh_draws = [&](uint32_t pq, uint32_t mi) {
+    if (!QG) {
+      blk = cobel_philox(((2u * pq + pol_odd) & pol_mask) | (mi & ~pol_mask), draw_sub, g, draw_stream,
+                         seed_now());
+      return;
+    }
     const bool p0 = lane == 62, p1 = lane == 63;
     blk = cobel_philox(p1 ? 2u * pq + 1u : (p0 ? 2u * pq : mi), (p0 || p1) ? 0u : (uint32_t)lane,
                        g, (p0 || p1) ? COBEL_STREAM_POLICY : COBEL_STREAM_MEMORY, seed_now());
@@ -778,10 +795,14 @@ __device__ __forceinline__ void pwg_instance(const pwg_args& A, const int i, con
     }
     // ---- online TD (agent/dyna_q.py:290-299), float32 ---------------------------------------------------
     const float q_sa = __builtin_bit_cast(float, rl(fbits(qc), a));
-    const float gnt = nt ? gamma_f : 0.0f;
+    // (LDS waves: the value is formed by every lane, in front of the one-lane store — inside its
+    //  exec-mask region the compiler put the whole sum, a scalar address and a branch; `end` is 0 or
+    //  1, so the mask end - 1 keeps gamma's bits or leaves +0.0f, what the select gave)
+    const float gnt = QG ? (nt ? gamma_f : 0.0f) : __builtin_bit_cast(float, fbits(gamma_f) & (end - 1u));
     float td = r + gnt * ns_max;
     td = td - q_sa;
-    const float qn_online = q_sa + alpha_f * td;
+    float qn_online = q_sa + alpha_f * td;
+    if (!QG) asm volatile("" : "+v"(qn_online));
     if (lane == 0) {
       if (QG) Qgf[sa] = qn_online;
       else Qf[sa] = qn_online;
@@ -807,7 +828,9 @@ __device__ __forceinline__ void pwg_instance(const pwg_args& A, const int i, con
         mg_next = (uint32_t)Mg[idx_next];
         if (iflags & 2u) {
           batches += 1u;
-          if (__builtin_expect((m & 0x8000u) != 0u, 0)) {
+          // (one compare for the whole batch and a branch on its mask: an entry has sixteen bits,
+          //  so a flagged one is one above 0x7fff; the rare block sets its own lanes)
+          if (__builtin_expect(__builtin_amdgcn_ballot_w64(m > 0x7fffu) != 0ull, 0) && m > 0x7fffu) {
             rj = __builtin_bit_cast(float, model32[2u * idx_cur]);
             // (consumed here: a wait for this rare load after the branches have joined would be a
             //  wait for every gather this step has just sent out)
