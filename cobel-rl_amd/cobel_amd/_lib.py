@@ -52,6 +52,23 @@ class ParamSet(C.Structure):
     ]
 
 
+class SFMAParamSet(C.Structure):
+    """``cobel_sfma_param_set_t`` (592 bytes; fill with ``cobel_sfma_param_set_fill``)."""
+    _fields_ = [
+        ('agent', ParamSet),
+        ('decay_inhibition', C.c_double), ('decay_strength', C.c_double),
+        ('c_step', C.c_double), ('i_step', C.c_double), ('r_threshold', C.c_double),
+        ('beta', C.c_double),
+        ('reward_modulation', C.c_double), ('blend', C.c_double), ('interp_fwd', C.c_double),
+        ('interp_rev', C.c_double),
+    ]
+
+
+# the ten doubles of a set's memory part, in the order cobel_sfma_param_set_fill takes them
+SFMA_SET_MEMORY = ('decay_inhibition', 'decay_strength', 'c_step', 'i_step', 'r_threshold', 'beta',
+                   'reward_modulation', 'blend', 'interp_fwd', 'interp_rev')
+
+
 class DQNReplay(C.Structure):
     """``cobel_dqn_replay_t``."""
     _fields_ = [
@@ -250,6 +267,7 @@ class SFMARun(C.Structure):
         ('reward_modulation', C.c_double), ('blend', C.c_double), ('interp_fwd', C.c_double),
         ('interp_rev', C.c_double),
         ('seed', C.c_uint64),
+        ('param_sets', C.c_void_p), ('param_index', C.c_void_p), ('n_param_sets', C.c_int32),
     ]
 
 
@@ -280,6 +298,7 @@ class SFMAMem(C.Structure):
         ('reward_modulation', C.c_double), ('blend', C.c_double), ('interp_fwd', C.c_double),
         ('interp_rev', C.c_double),
         ('seed', C.c_uint64),
+        ('param_sets', C.c_void_p), ('param_index', C.c_void_p), ('n_param_sets', C.c_int32),
     ]
 
 
@@ -573,6 +592,8 @@ _SIGNATURES = {
                                          _P]),
     'cobel_param_set_fill': (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_double,
                                        C.POINTER(ParamSet)]),
+    'cobel_sfma_param_set_fill': (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_double,
+                                            C.POINTER(C.c_double * 10), C.POINTER(SFMAParamSet)]),
     'cobel_tab_query': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
                                   C.POINTER(C.c_int32)]),
     'cobel_tab_run': (C.c_int, [_P, C.POINTER(TabRun), _P]),

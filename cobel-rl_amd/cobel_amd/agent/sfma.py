@@ -19,7 +19,7 @@ import torch
 
 from .. import _lib
 from ..memory import _device
-from ..memory.sfma import EVENT
+from ..memory.sfma import EVENT, LAUNCH_WIDE, refuse_arrays
 from ..spaces import Discrete
 from .agent import Callbacks
 from .tabular import TabularAgent
@@ -100,6 +100,11 @@ class SFMA(TabularAgent):
     # -- launch ---------------------------------------------------------------------------------
     def _launch(self, interface, pol, flags, trials_target, steps, budget, batch) -> None:
         M = self.M
+        # (what shapes the launch or switches its code path is one value for all instances)
+        refuse_arrays(M, LAUNCH_WIDE)
+        refuse_arrays(self, ('nb_replays', 'random', 'dynamic', 'start_replay'))
+        if np.ndim(batch) > 0:
+            raise NotImplementedError('batch_size is launch-wide: one value for all instances')
         if M.error_mod_local or M.error_mod:
             raise KeyError('td')       # what the reference's M.store raises inside train()
         run = _lib.SFMARun()     # (monitors, instance and session fields: FusedAgent._fill_run)
@@ -109,7 +114,10 @@ class SFMA(TabularAgent):
         run.sfma_inst = _lib.ptr(M.state)
         run.metric = _lib.ptr(M._metric_on(self.device, interface.handle.n_worlds))
         # (the memory's switches, recency table and parameters: the block its own methods pass)
-        run.sfma_flags = M._fill_params(run) | (_lib.SF_RANDOM if self.random else 0) | \
+        # (with the agent's learning rate and discount and the policy's epsilon: scalars, or one
+        #  table of parameter sets over the agent's four columns and the memory's ten)
+        run.sfma_flags = M._fill_params(run, (self.learning_rate, self.gamma, pol.epsilon)) | \
+            (_lib.SF_RANDOM if self.random else 0) | \
             (_lib.SF_DYNAMIC if self.dynamic else 0) | \
             (_lib.SF_START_REPLAY if self.start_replay else 0)
         if self.random:
@@ -129,7 +137,6 @@ class SFMA(TabularAgent):
             run.trace_cap = self._trace.shape[1] // _lib.SFMA_EVENT_BYTES
         run.flags = flags
         run.batch, run.nb_replays = batch, self.nb_replays
-        run.alpha, run.gamma, run.epsilon = self.learning_rate, self.gamma, pol.epsilon
         # (the memory's own methods, called between sessions, go on in this stream)
         M._session(interface.seed, interface.instance_base, interface.handle.n_worlds)
         M._sync_mode()

@@ -32,6 +32,36 @@ class DeviceMemory:
         self.seed, self.instance_base, self._n_worlds = int(seed), int(instance_base), int(n_worlds)
 
 
+PER_INSTANCE_SHAPE = 'per-instance hyper-parameters need one entry per environment instance'
+
+
+def param_columns(values, n: int):
+    """Scalars or [N] arrays -> float64 arrays, or None if every one of them is a scalar; an
+    array of another shape is an ``AssertionError``."""
+    vals = [np.asarray(v, dtype=np.float64) for v in values]
+    if all(v.ndim == 0 for v in vals):
+        return None
+    for v in vals:
+        assert v.ndim == 0 or v.shape == (n,), PER_INSTANCE_SHAPE
+    return np.stack([np.broadcast_to(v, (n,)) for v in vals], axis=1)
+
+
+def param_sets(cols, key, fill, device):
+    """Per-instance parameter columns [N, K] as parameter sets: the distinct rows become sets
+    (``fill(rows)`` -> a ctypes array of them), every instance gets the uint16 index of its row.
+    Returns ``(key, sets, index, number of sets, row of set 0)`` with the two device tensors, or
+    None if the bytes of the columns are ``key``, those of the tensors the caller holds."""
+    new = cols.tobytes()
+    if new == key:
+        return None
+    uniq, inv = np.unique(cols, axis=0, return_inverse=True)
+    assert len(uniq) <= 65535, 'at most 65535 distinct parameter combinations per launch'
+    raw = np.frombuffer(fill(uniq), dtype=np.uint8).copy()
+    index = np.ascontiguousarray(inv.reshape(-1).astype(np.uint16)).view(np.int16)
+    return (new, torch.as_tensor(raw, device=device), torch.as_tensor(index, device=device),
+            len(uniq), uniq[0])
+
+
 def plan4(entry, *args):
     """The four ints a ``cobel_*_plan`` entry point writes, as the ctypes array."""
     out = (C.c_int32 * 4)()

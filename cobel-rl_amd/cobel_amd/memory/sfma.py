@@ -11,6 +11,13 @@ at ``counter``, where ``train`` left it and where ``train`` goes on afterwards. 
 per-instance argument checks and the decoding of the packed model table are memory/_device.py's,
 shared with ``PMAMemory`` and ``DynaQMemory``; ``_fill_params`` serves the agent's launcher too.
 
+Per-instance parameters.  ``decay_inhibition``, ``decay_strength``, ``learning_rate``, ``beta``,
+``C_step``, ``I_step``, ``R_threshold``, ``reward_modulation``, ``blend``, ``interpolation_fwd``
+and ``interpolation_rev`` take a scalar or one entry per instance, ``mode`` a string or a sequence
+of N strings: a sweep over them rides on the instance axis of one launch
+(``optimizer.grid_search.spread_over_instances``).  The switches and ``decay_recency`` are
+launch-wide; an array there is a ``NotImplementedError``.
+
 This class owns the parameters and the device tables:
 
   ``table``     packed model records [N, S, 4] (float32 reward estimate, next state, nonterminal),
@@ -36,6 +43,23 @@ EXPERIENCE = np.dtype([('state', '<i4'), ('action', '<i4'), ('next_state', '<i4'
                        ('nonterminal', '<i4'), ('reward', '<f8'), ('td', '<f8')])
 EVENT = np.dtype([('sa', '<u4'), ('next', '<u4'), ('reward', '<f4'), ('trial', '<i4'),
                   ('td', '<f8')])
+# the attributes that take a scalar or one entry per instance, in the order of the ten doubles of
+# a cobel_sfma_param_set_t (_lib.SFMA_SET_MEMORY); `learning_rate` is the set's model_lr
+SET_ATTRIBUTES = ('decay_inhibition', 'decay_strength', 'C_step', 'I_step', 'R_threshold', 'beta',
+                  'reward_modulation', 'blend', 'interpolation_fwd', 'interpolation_rev')
+# launch-wide: they change the code path (the switches) or the shape of the launch
+LAUNCH_WIDE = ('deterministic', 'recency', 'C_normalize', 'D_normalize', 'R_normalize',
+               'reward_mod_local', 'reward_mod', 'state_mod', 'error_mod_local', 'error_mod',
+               'decay_recency')
+
+
+def refuse_arrays(obj, names) -> None:
+    """An array where one value serves the whole launch is refused, naming the attribute."""
+    for name in names:
+        if np.ndim(getattr(obj, name)) > 0:
+            raise NotImplementedError(
+                '%s.%s is launch-wide: one value for all instances, not an array'
+                % (type(obj).__name__, name))
 
 
 class SFMAMemory(_device.DeviceMemory, _device.PackedModel):
@@ -69,6 +93,7 @@ class SFMAMemory(_device.DeviceMemory, _device.PackedModel):
         self.seed, self.instance_base, self._n_worlds = 0, 0, 1
         self.launch_flags = 0      # testing: _lib.F_SFMA_STREAM / F_FORCE_WAVE / F_NO_PREFETCH
         self._inhibition = None
+        self._psets = {}           # parameter sets on the device, per caller: key, sets, index, n
 
     # -- device state ---------------------------------------------------------------------------
     def _bind(self, n_envs: int, device) -> None:
@@ -82,8 +107,7 @@ class SFMAMemory(_device.DeviceMemory, _device.PackedModel):
         self.stamp = torch.zeros((n_envs, 4 * S), dtype=torch.int32, device=device)
         self.state = torch.zeros((n_envs, _lib.SI_WORDS), dtype=torch.int32, device=device)
         self.state[:, _lib.SI_FLAGS] = 1       # agent.td starts as a weak Python float
-        self.state[:, _lib.SI_MODE] = self._mode_id()
-        self._mode_seen = self.mode
+        self._write_mode()
         self.counter = torch.zeros(n_envs, dtype=torch.int32, device=device)
 
     def _metric_on(self, device, n_worlds: int):
@@ -138,15 +162,28 @@ class SFMAMemory(_device.DeviceMemory, _device.PackedModel):
                              torch.as_tensor(np.array(vals, dtype=np.float64), device=device))
         return self._recency[1]
 
-    def _mode_id(self) -> int:
+    def _mode_key(self):
+        """``mode`` as a string (all instances) or a tuple of N strings (one per instance)."""
+        return self.mode if isinstance(self.mode, str) else tuple(str(m) for m in self.mode)
+
+    def _mode_id(self):
         # memory/sfma.py:289-307 is an if/elif chain over the known names: any other string
         # (unit_tests/test_sfma.py assigns 'dynamic') leaves the similarity as in 'default'
-        return _lib.SFMA_MODES.index(self.mode) if self.mode in _lib.SFMA_MODES else 0
+        ident = lambda m: _lib.SFMA_MODES.index(m) if m in _lib.SFMA_MODES else 0   # noqa: E731
+        key = self._mode_key()
+        return ident(key) if isinstance(key, str) else [ident(m) for m in key]
+
+    def _write_mode(self) -> None:
+        ids = self._mode_id()
+        if isinstance(ids, list):
+            assert len(ids) == self.state.shape[0], _device.PER_INSTANCE_SHAPE
+            ids = torch.as_tensor(ids, dtype=torch.int32, device=self.state.device)
+        self.state[:, _lib.SI_MODE] = ids
+        self._mode_seen = self._mode_key()
 
     def _sync_mode(self) -> None:
-        if self.mode != self._mode_seen:
-            self.state[:, _lib.SI_MODE] = self._mode_id()
-            self._mode_seen = self.mode
+        if self._mode_key() != self._mode_seen:
+            self._write_mode()
 
     def _read_mode(self) -> None:
         if self.state.shape[0] == 1:
@@ -191,9 +228,14 @@ class SFMAMemory(_device.DeviceMemory, _device.PackedModel):
                 'next_state': s[0, state, action], 'terminal': t[0, state, action]}
 
     # -- the reference's methods as device calls (csrc/sfma_mem.hip) ------------------------------
-    def _fill_params(self, struct) -> int:
-        """The recency table, ``model_lr`` and the eleven doubles of a ``cobel_sfma_run_t`` or
-        ``cobel_sfma_mem_t``; returns the memory's ``SF_*`` switches (the caller ORs in its own)."""
+    def _fill_params(self, struct, agent=None) -> int:
+        """The recency table, ``model_lr`` and the ten doubles of a ``cobel_sfma_run_t`` or
+        ``cobel_sfma_mem_t`` — and, for the agent's launcher, ``agent = (learning rate, gamma,
+        epsilon)`` — as scalars, or, if any of them has one entry per instance, as parameter sets:
+        the distinct rows become ``cobel_sfma_param_set_t`` records, every instance gets the index
+        of its row, and the scalar fields hold set 0's values as placeholders.  Returns the
+        memory's ``SF_*`` switches (the caller ORs in its own)."""
+        refuse_arrays(self, LAUNCH_WIDE)
         sf = 0
         for flag, on in ((_lib.SF_DETERMINISTIC, self.deterministic), (_lib.SF_RECENCY, self.recency),
                          (_lib.SF_C_NORMALIZE, self.C_normalize),
@@ -205,12 +247,35 @@ class SFMAMemory(_device.DeviceMemory, _device.PackedModel):
         if self.recency:
             tab = self._recency_table(self.table.device)
             struct.recency_tab, struct.recency_len = _lib.ptr(tab), tab.numel()
-        struct.model_lr = self.learning_rate
-        struct.decay_inhibition, struct.decay_strength = self.decay_inhibition, self.decay_strength
-        struct.c_step, struct.i_step = self.C_step, self.I_step
-        struct.r_threshold, struct.beta = self.R_threshold, self.beta
-        struct.reward_modulation, struct.blend = self.reward_modulation, self.blend
-        struct.interp_fwd, struct.interp_rev = self.interpolation_fwd, self.interpolation_rev
+        names = (('alpha', 'gamma', 'epsilon') if agent is not None else ()) + \
+            ('model_lr',) + _lib.SFMA_SET_MEMORY
+        vals = (tuple(agent) if agent is not None else ()) + (self.learning_rate,) + \
+            tuple(getattr(self, a) for a in SET_ATTRIBUTES)
+        n = self.table.shape[0]
+        cols = _device.param_columns(vals, n)
+        if cols is None:
+            for name, v in zip(names, vals):
+                setattr(struct, name, float(v))
+            return sf
+        if agent is None:          # the memory's own calls: the agent part at its defaults
+            cols = np.concatenate([np.broadcast_to([0.99, 0.99, 0.0], (n, 3)), cols], axis=1)
+
+        def fill(rows):
+            sets = (_lib.SFMAParamSet * len(rows))()
+            for k, row in enumerate(rows):
+                _lib.check(_lib.lib().cobel_sfma_param_set_fill(
+                    float(row[0]), float(row[1]), float(row[2]), float(row[3]),
+                    C.byref((C.c_double * 10)(*row[4:])), C.byref(sets[k])))
+            return sets
+        who = 'agent' if agent is not None else 'memory'
+        held = self._psets.setdefault(who, dict(key=None, sets=None, index=None, n=0, first=None))
+        new = _device.param_sets(cols, held['key'], fill, self.table.device)
+        if new is not None:
+            held['key'], held['sets'], held['index'], held['n'], held['first'] = new
+        for name, v in zip(names, held['first'][-len(names):]):   # placeholders: set 0's values
+            setattr(struct, name, float(v))
+        struct.param_sets, struct.param_index = _lib.ptr(held['sets']), _lib.ptr(held['index'])
+        struct.n_param_sets = held['n']
         return sf
 
     def _mem(self, mem_flags: int = 0):
@@ -241,6 +306,7 @@ class SFMAMemory(_device.DeviceMemory, _device.PackedModel):
         of ``experience`` are scalars (the same for all) or [N] arrays.  ``'terminal'`` holds what
         the reference's agent puts there, 1 - end_trial.  ``'td'`` is read under ``error_mod`` /
         ``error_mod_local`` only (KeyError without it, as in the reference)."""
+        refuse_arrays(self, LAUNCH_WIDE)
         flags = (_lib.SFM_ERROR_MOD_LOCAL if self.error_mod_local else 0) | \
                 (_lib.SFM_ERROR_MOD if self.error_mod else 0)
         m, dev = self._mem(flags)

@@ -56,6 +56,7 @@ struct sfma_lds {
   uint64_t* thr; // [48] epsilon-greedy thresholds, entry t * 3 + k
   double* epsc;  // [16] masked selection: base[1..4], bonus[1..4] (cobel_policy.h); then blend,
                  //      interp_fwd, interp_rev, decay_inhibition, i_step, alpha, gamma, beta
+                 //      (thr and epsc: the launch's, or those of the instance's parameter set)
 };
 
 constexpr int kFastStates = 32;   // 4 S <= 128 experiences, two per lane
@@ -506,6 +507,34 @@ __device__ __forceinline__ void sfma_body(const sfma_args A,
     L.epsc[14] = A.r.gamma;
     L.epsc[15] = A.r.beta;
   }
+  // Per-instance parameter sets (run.param_index): instance i takes these constants from its set
+  // instead of the launch's scalars — here, at the top, and nowhere else.  The plain-training
+  // instantiation has no such code: cobel_sfma_run sends a launch with an index to the kernel that
+  // serves every value (the conditions of FAST are facts of a set).
+  // (a pointer into global memory by its type: were it a generic one, as the copy of the by-value
+  //  arguments is, the compiler would merge a scalar's two loads — from the arguments, from the
+  //  set — into one load through a selected pointer, and the arguments, 920 B, would then be
+  //  copied into scratch in every lane)
+  typedef const __attribute__((address_space(1))) cobel_sfma_param_set_t* set_ptr;
+  set_ptr PS = nullptr;
+  if constexpr (!FAST) {
+    if (A.r.param_index) {
+      const int k = (int)A.r.param_index[i];
+      PS = (set_ptr)(A.r.param_sets + (k < A.r.n_param_sets ? k : A.r.n_param_sets - 1));
+      if (t < 48) L.thr[t] = PS->agent.eps_thr[t / 3][t % 3];
+      if (t < 8) L.epsc[t] = t < 4 ? PS->agent.eps_base[t + 1] : PS->agent.eps_bonus[t - 3];
+      if (t == 8) {
+        L.epsc[8] = PS->blend;
+        L.epsc[9] = PS->interp_fwd;
+        L.epsc[10] = PS->interp_rev;
+        L.epsc[11] = PS->decay_inhibition;
+        L.epsc[12] = PS->i_step;
+        L.epsc[13] = PS->agent.alpha;
+        L.epsc[14] = PS->agent.gamma;
+        L.epsc[15] = PS->beta;
+      }
+    }
+  }
   if (ns_lds)
     for (int e = t; e < n4; e += NT) {
       if (!BIG) L.C[e] = Cg[e];
@@ -552,6 +581,17 @@ __device__ __forceinline__ void sfma_body(const sfma_args A,
   // that only feed vector arithmetic are pinned to vector registers instead.
   double r_thr = A.r.r_threshold;
   float alpha_f = A.alpha_f, gamma_f = A.gamma_f, mlr_f = A.model_lr_f;
+  // (what M.store takes: read where it is used without sets, this instance's values with them)
+  double dec_str = A.r.decay_strength, c_step = A.r.c_step, rew_mod = A.r.reward_modulation;
+  if (PS) {
+    r_thr = PS->r_threshold;
+    alpha_f = PS->agent.alpha_f;
+    gamma_f = PS->agent.gamma_f;
+    mlr_f = PS->agent.model_lr_f;
+    dec_str = PS->decay_strength;
+    c_step = PS->c_step;
+    rew_mod = PS->reward_modulation;
+  }
   asm volatile("" : "+v"(r_thr), "+v"(alpha_f), "+v"(gamma_f), "+v"(mlr_f));
   // (the constants used once per reactivation or only by some replay modes are read from LDS where
   //  they are used: blend, interp_fwd / _rev, decay_inhibition, i_step, alpha, gamma, beta — L.epsc[8 ..])
@@ -650,14 +690,14 @@ __device__ __forceinline__ void sfma_body(const sfma_args A,
       if (!BIG) L.R[j] = Rnew;
       if (ns_lds) L.NS[j] = (uint16_t)((uint32_t)ns | (nt << 15));
     }
-    if (!FAST && A.r.decay_strength != 1.0) {
-      for (int e = t; e < n4; e += NT) st_c(e, ld_c(e) * A.r.decay_strength);
+    if (!FAST && dec_str != 1.0) {
+      for (int e = t; e < n4; e += NT) st_c(e, ld_c(e) * dec_str);
       bsync();
     }
     clock += 1u;
     if (t == 0) {
-      double c = ld_c(j) + A.r.c_step;
-      if (!FAST && (sf & COBEL_SF_REWARD_MOD_LOCAL)) c = c + rd * A.r.reward_modulation;
+      double c = ld_c(j) + c_step;
+      if (!FAST && (sf & COBEL_SF_REWARD_MOD_LOCAL)) c = c + rd * rew_mod;
       st_c(j, c);
       stamp[j] = clock;
     }
@@ -666,7 +706,7 @@ __device__ __forceinline__ void sfma_body(const sfma_args A,
       const double* const row = Dm + (size_t)state * S;
       for (int e = t; e < n4; e += NT) {
         const int s2 = e % S;
-        st_c(e, ld_c(e) + (rd * row[s2]) * A.r.reward_modulation);
+        st_c(e, ld_c(e) + (rd * row[s2]) * rew_mod);
       }
     }
     if constexpr (MEM == 1) {
@@ -1237,6 +1277,20 @@ __device__ __forceinline__ void sfma_body(const sfma_args A,
     if (A.r.steps_done && executed) atomicAdd(A.r.steps_done, executed);
     if (A.r.replays_done && replayed) atomicAdd(A.r.replays_done, replayed);
   }
+}
+
+// What cobel_sfma_run and the memory's calls refuse of per-instance parameter sets before a launch:
+// an index without sets, a number of sets a 16-bit index cannot address, misaligned pointers.
+// Without an index the other two fields are not looked at.
+inline int sfma_check_sets(const cobel_sfma_param_set_t* sets, const uint16_t* index,
+                           int32_t n_sets, const char* who) {
+  if (!index) return COBEL_OK;
+  COBEL_REQUIRE(sets, COBEL_E_ARG, "%s: param_index given without parameter sets", who);
+  COBEL_REQUIRE(n_sets >= 1 && n_sets <= 65535, COBEL_E_RANGE,
+                "%s: %d parameter sets (1 ... 65535)", who, n_sets);
+  COBEL_REQUIRE(((uintptr_t)sets & 15u) == 0 && ((uintptr_t)index & 1u) == 0, COBEL_E_ARG,
+                "%s: param_sets must be 16-byte, param_index 2-byte aligned", who);
+  return COBEL_OK;
 }
 
 // sfma_big.hip: the streaming form, `threads` (256 or 1 024) per instance

@@ -194,7 +194,10 @@ extern "C" int cobel_sfma_run(const cobel_world_t* world, const cobel_sfma_run_t
                 r.steps_per_trial);
   COBEL_REQUIRE(r.batch >= 0 && r.nb_replays >= 0, COBEL_E_RANGE,
                 "cobel_sfma_run: batch = %d, nb_replays = %d", r.batch, r.nb_replays);
-  COBEL_REQUIRE(r.epsilon >= 0.0 && r.epsilon <= 1.0, COBEL_E_ARG,
+  if (int rc = sfma_check_sets(r.param_sets, r.param_index, r.n_param_sets, "cobel_sfma_run"))
+    return rc;
+  // (with an index the scalars are ignored; a set's epsilon is checked where the set is filled)
+  COBEL_REQUIRE(r.param_index || (r.epsilon >= 0.0 && r.epsilon <= 1.0), COBEL_E_ARG,
                 "cobel_sfma_run: epsilon %g outside [0, 1]", r.epsilon);
   COBEL_REQUIRE(!(r.flags & COBEL_F_MASK_ACTIONS) || r.action_mask, COBEL_E_ARG,
                 "cobel_sfma_run: mask_actions set without an action mask");
@@ -254,7 +257,7 @@ extern "C" int cobel_sfma_run(const cobel_world_t* world, const cobel_sfma_run_t
                       !(r.sfma_flags & slow_sf) && r.nb_replays == 1 && r.decay_strength == 1.0 &&
                       r.beta >= 0.0 && r.beta <= 700.0 && r.r_threshold >= 0.0 &&
                       !r.last_exp && !r.occupancy && !r.replay_trace && !r.lat_trace &&
-                      !world->succ_off;
+                      !world->succ_off && !r.param_index;
     if (fast) {
       hipLaunchKernelGGL(k_sfma_2_fast, dim3(A.r.n), dim3(64), sfma_lds_bytes(kFastStates), st, A);
       COBEL_HIP_TRY(hipGetLastError());

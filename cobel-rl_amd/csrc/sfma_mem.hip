@@ -77,7 +77,7 @@ int check_mem(const cobel_sfma_mem_t* mem, const char* who) {
                 m.n_worlds);
   COBEL_REQUIRE(!(m.sfma_flags & COBEL_SF_RECENCY) || (m.recency_tab && m.recency_len > 0),
                 COBEL_E_ARG, "%s: recency needs recency_tab", who);
-  return COBEL_OK;
+  return sfma_check_sets(m.param_sets, m.param_index, m.n_param_sets, who);
 }
 
 // the body's arguments from the memory's: no world, no agent, no monitors
@@ -109,6 +109,9 @@ int fill_args(const cobel_sfma_mem_t& m, const mem_plan& P, sfma_args* out) {
   A.r.interp_fwd = m.interp_fwd;
   A.r.interp_rev = m.interp_rev;
   A.r.seed = m.seed;
+  A.r.param_sets = m.param_sets;
+  A.r.param_index = m.param_index;
+  A.r.n_param_sets = m.n_param_sets;
   A.model_lr_f = (float)m.model_lr;
   A.big_lds = P.big_lds;
   if (P.form == 1) A.chunk = ((4 * S + P.threads - 1) / P.threads + 3) & ~3;

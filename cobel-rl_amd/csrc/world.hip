@@ -98,6 +98,26 @@ extern "C" int cobel_param_set_fill(double alpha, double gamma, double epsilon, 
   return COBEL_OK;
 }
 
+extern "C" int cobel_sfma_param_set_fill(double alpha, double gamma, double epsilon,
+                                         double model_lr, const double memory[10],
+                                         cobel_sfma_param_set_t* out) {
+  COBEL_REQUIRE(out && memory, COBEL_E_ARG, "cobel_sfma_param_set_fill: NULL memory / out");
+  static_assert(sizeof(cobel_sfma_param_set_t) == 592 && sizeof(cobel_sfma_param_set_t) % 16 == 0,
+                "cobel_sfma_param_set_t layout");
+  if (int rc = cobel_param_set_fill(alpha, gamma, epsilon, model_lr, &out->agent)) return rc;
+  out->decay_inhibition = memory[0];
+  out->decay_strength = memory[1];
+  out->c_step = memory[2];
+  out->i_step = memory[3];
+  out->r_threshold = memory[4];
+  out->beta = memory[5];
+  out->reward_modulation = memory[6];
+  out->blend = memory[7];
+  out->interp_fwd = memory[8];
+  out->interp_rev = memory[9];
+  return COBEL_OK;
+}
+
 extern "C" uint64_t cobel_pack_model(float reward, uint16_t next_state, uint8_t nonterminal) {
   return cobel_model_pack(reward, next_state, nonterminal ? 1u : 0u);
 }

@@ -712,6 +712,29 @@ typedef struct {
   double td;       /* TD error of the update (NaN for start-of-trial replays)                  */
 } cobel_sfma_event_t;
 
+/* Per-instance SFMA parameters: the agent's set (cobel_param_set_t: learning rate, discount,
+ * the policy's epsilon with its derived selection constants, M.learning_rate as model_lr) and the
+ * ten parameters of the memory a sweep varies (memory/sfma.py:40-72).  The reference runs one
+ * simulation per combination; here instance i of ONE launch uses param_sets[param_index[i]] — in
+ * every kernel of cobel_sfma_run except the plain-training one, whose conditions (decay_strength
+ * == 1, 0 <= beta <= 700, r_threshold >= 0) are facts of a set the launcher cannot see: a launch
+ * with an index takes the two-experiences-per-lane kernel that serves every value instead.  The
+ * replay mode is per instance already (sfma_inst[COBEL_SI_MODE]); the switches (COBEL_SF_*),
+ * nb_replays, the recency decay and the replay length stay launch-wide.  Fill a set with
+ * cobel_sfma_param_set_fill, never by hand.  592 bytes, a multiple of 16 as it stands. */
+typedef struct {
+  cobel_param_set_t agent;
+  double decay_inhibition, decay_strength;       /* M.decay_inhibition, M.decay_strength      */
+  double c_step, i_step, r_threshold, beta;      /* M.C_step, M.I_step, M.R_threshold, M.beta */
+  double reward_modulation, blend, interp_fwd, interp_rev;
+} cobel_sfma_param_set_t;
+/* Host only.  The agent part is cobel_param_set_fill(alpha, gamma, epsilon, model_lr) — epsilon
+ * outside [0, 1] is refused (COBEL_E_ARG), as cobel_sfma_run refuses it; memory[10] in the order
+ * of the members above, taken verbatim. */
+COBEL_API int cobel_sfma_param_set_fill(double alpha, double gamma, double epsilon, double model_lr,
+                                        const double memory[10],
+                                        cobel_sfma_param_set_t* out /* [host] */);
+
 typedef struct {
   /* tables, caller-owned device memory */
   float* q;               /* [N][S][4] float32 Q                                              */
@@ -753,6 +776,12 @@ typedef struct {
   double c_step, i_step, r_threshold, beta;      /* M.C_step, M.I_step, M.R_threshold, M.beta */
   double reward_modulation, blend, interp_fwd, interp_rev;
   uint64_t seed;
+  /* optional per-instance parameter sets, as in cobel_tab_run_t: with param_index != NULL
+     instance i uses param_sets[param_index[i]] (index < n_param_sets, 1 .. 65 535 sets) and the
+     fourteen scalars above are ignored; with param_index == NULL the launch is the scalar launch */
+  const cobel_sfma_param_set_t* param_sets; /* [dev] [n_param_sets], 16-byte aligned          */
+  const uint16_t* param_index;              /* [dev] [N]                                      */
+  int32_t n_param_sets;
 } cobel_sfma_run_t;
 
 /* The LDS-resident form: 0 = it serves n_states; fills *lds_bytes with the LDS one instance needs. */
@@ -824,6 +853,12 @@ typedef struct {
   double c_step, i_step, r_threshold, beta;
   double reward_modulation, blend, interp_fwd, interp_rev;
   uint64_t seed;
+  /* optional per-instance parameter sets, as in cobel_sfma_run_t: instance i — every one of its
+     replays in a strided call — uses param_sets[param_index[i]]; of the agent part a store reads
+     model_lr, the rest is unused here */
+  const cobel_sfma_param_set_t* param_sets; /* [dev] [n_param_sets], 16-byte aligned          */
+  const uint16_t* param_index;              /* [dev] [N]                                      */
+  int32_t n_param_sets;
 } cobel_sfma_mem_t;
 
 /* What the memory's calls launch for n_states under `flags`: out = {form (0 LDS-resident, 1
