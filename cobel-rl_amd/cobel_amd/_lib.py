@@ -207,6 +207,19 @@ class TabRun(C.Structure):
     ]
 
 
+POLICY_SOFTMAX, POLICY_EXCLUSIVE, POLICY_RANDOM = 1, 2, 3     # cobel_tab_policy_run_t.policy
+POLICY_MAX_ACTIONS, POLICY_MAX_STATES = 8, 1024
+
+
+class TabPolicyRun(C.Structure):
+    """``cobel_tab_policy_run_t``: a ``cobel_tab_run_t`` held by value, the policy and its parameter."""
+    _fields_ = [
+        ('run', TabRun),
+        ('policy', C.c_int32), ('reserved_', C.c_int32),
+        ('policy_param', C.c_double), ('policy_params', C.c_void_p),
+    ]
+
+
 ROLLOUT_ELEMENT_STORES = 1       # cobel_tab_rollout_t.record_flags (COBEL_ROLLOUT_*)
 
 
@@ -601,6 +614,10 @@ _SIGNATURES = {
     'cobel_q_run': (C.c_int, [_P, C.POINTER(TabRun), _P]),
     'cobel_tab_describe': (C.c_int, [_P, C.POINTER(TabRun), C.POINTER(C.c_int32)]),
     'cobel_tab_scratch_check': (C.c_int, [_P, C.c_int64, _P]),
+    'cobel_tab_policy_run': (C.c_int, [_P, C.POINTER(TabPolicyRun), _P]),
+    'cobel_tab_policy_plan': (C.c_int, [_P, C.POINTER(TabPolicyRun), C.POINTER(C.c_int32 * 4)]),
+    'cobel_policy_select_n': (C.c_int, [C.c_int32, _P, _P, _P, _P, _P, C.c_int32, _P, _P, C.c_int32,
+                                        C.c_int32, _P]),
     'cobel_dynaq_replay': (C.c_int, [_P, C.POINTER(TabRun), C.c_int32, _P]),
     'cobel_dynaq_replay_plan': (C.c_int, [_P, C.POINTER(TabRun), C.c_int32,
                                           C.POINTER(C.c_int32 * 4)]),

@@ -288,6 +288,7 @@ class FusedAgent(Agent):
     ``_fill_run``, where a launcher starts (it adds its tables, flags and hyper-parameters)."""
 
     general_actions = False    # True: the agent also runs on action counts other than four
+    exclusive_policy = False   # True: the agent's launcher serves ExclusiveEpsilonGreedy
 
     def __init__(self, observation_space, action_space, policy, policy_test, custom_callbacks):
         super().__init__(observation_space, action_space, custom_callbacks)
@@ -424,6 +425,11 @@ class FusedAgent(Agent):
 
     def _policy_in(self, pol, interface, test: bool) -> int:
         """Adopt the policy's stream + counter for a run; returns extra flags."""
+        from ..policy.greedy import ExclusiveEpsilonGreedy
+        if isinstance(pol, ExclusiveEpsilonGreedy) and not self.exclusive_policy:
+            # (it carries an `epsilon`: the kernels would quietly select as EpsilonGreedy does)
+            raise NotImplementedError('%s selects with EpsilonGreedy; ExclusiveEpsilonGreedy is '
+                                      'served for QAgent and DynaQ' % type(self).__name__)
         if pol.seed is None:
             pol.seed = interface.seed
         assert pol.seed == interface.seed, \

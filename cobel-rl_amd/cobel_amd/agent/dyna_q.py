@@ -20,6 +20,7 @@ import torch
 from .. import _lib
 from ..memory import _device
 from ..memory.dyna_q import DynaQMemory, _is_array, pack_experiences
+from ..policy.greedy import EpsilonGreedy
 from ..spaces import Discrete
 from .tabular import TabularAgent
 
@@ -76,7 +77,9 @@ class DynaQ(TabularAgent):
         run.n, run.instance_base = self.n_envs, self._instance_base
         run.agent, run.flags, run.batch = self.agent_kind, self.extra_flags, batch
         run.seed = self._seed
-        self._hyper(run, self.learning_rate, self.gamma, self.policy.epsilon, self._model_lr())
+        # (no selection in these calls: a policy without an epsilon hands in none)
+        eps = self.policy.epsilon if type(self.policy) is EpsilonGreedy else 0.0
+        self._hyper(run, self.learning_rate, self.gamma, eps, self._model_lr())
         self._extra(run)
         return run
 

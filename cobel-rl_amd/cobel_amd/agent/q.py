@@ -8,6 +8,9 @@ sized by each ``train`` call).  ``batch_size=0`` disables replay (demo/topology/
 experiences are logged all the same, as in the reference (``log_experiences = False`` skips that).
 Any action count up to 8 (a hexagonal ``Topology`` has six) and any ``batch_size``: runs outside
 what the wavefront kernels cover take the general kernel of ``cobel_tab_run``, same results.
+With a ``Softmax``, an ``ExclusiveEpsilonGreedy`` or a ``RandomDiscrete`` policy the sessions run on
+``cobel_tab_policy_run`` instead (up to 8 actions, 1 024 states, batch 62; ``beta`` / ``epsilon`` a
+scalar or one value per instance), on the same tables.
 
 On a ``Sequence`` (Box observations) ``train`` / ``test`` run through ``QSequence`` (agent/q_seq.py)
 instead: Q keyed by the observation itself, float64, with a ``Softmax`` or an ``EpsilonGreedy``

@@ -36,6 +36,7 @@ class CallbacksSFMA(Callbacks):
 
 class SFMA(TabularAgent):
     CallbacksSFMA = CallbacksSFMA
+    exclusive_policy = False   # (cobel_sfma_run selects with EpsilonGreedy)
     describe_launch = None     # (cobel_tab_describe covers cobel_tab_run; SFMA has its own kernel)
 
     def __init__(self, observation_space, action_space, policy, memory, policy_test=None,

@@ -7,7 +7,16 @@ import numpy as np
 import torch
 
 from .. import _lib
+from ..memory import _device
+from ..policy.greedy import EpsilonGreedy, ExclusiveEpsilonGreedy
+from ..policy.random import RandomDiscrete
+from ..policy.softmax import Softmax
 from .agent import FusedAgent
+
+# the policies cobel_tab_policy_run selects with, and where each keeps its parameter
+_POLICY_KINDS = {Softmax: (_lib.POLICY_SOFTMAX, 'beta'),
+                 ExclusiveEpsilonGreedy: (_lib.POLICY_EXCLUSIVE, 'epsilon'),
+                 RandomDiscrete: (_lib.POLICY_RANDOM, None)}
 
 
 class TabularAgent(FusedAgent):
@@ -16,6 +25,7 @@ class TabularAgent(FusedAgent):
 
     agent_kind = _lib.AGENT_Q
     general_actions = True     # cobel_tab_run's general kernel takes any action count
+    exclusive_policy = True    # (_launch_policy; SFMA, with a launcher of its own, says False)
     force_general = False      # True: always the general kernel (tests, A/B comparisons)
     extra_flags = 0            # COBEL_F_* testing switches ORed into every launch (F_NO_PWG, ...)
 
@@ -28,6 +38,7 @@ class TabularAgent(FusedAgent):
         self._q_host = (np.zeros((self.n_states, self.n_actions), dtype=np.float32)
                         if self.n_states is not None else None)
         self._poses = None      # node poses when the observations are a Topology's (Box)
+        self._ppol = (None,) * 5   # parameter sets of policy runs: key, sets, index, count, policy_params
 
     # -- tables -----------------------------------------------------------------------------
     def _alloc_tables(self) -> None:
@@ -95,6 +106,9 @@ class TabularAgent(FusedAgent):
 
     def _launch(self, interface, pol, flags, trials_target, steps, budget, batch,
                 describe=None, record=None) -> None:
+        if type(pol) is not EpsilonGreedy:
+            return self._launch_policy(interface, pol, flags, trials_target, steps, budget, batch,
+                                       describe, record)
         run = _lib.TabRun()
         self._fill_run(run, interface, flags, trials_target, steps, budget)
         run.q = _lib.ptr(self._q)
@@ -129,6 +143,79 @@ class TabularAgent(FusedAgent):
             pair[1].record()
             ev.append(pair)
 
+    # -- Softmax, ExclusiveEpsilonGreedy, RandomDiscrete ------------------------------------------------
+    def _hyper_policy(self, prun: _lib.TabPolicyRun, pol, attr) -> None:
+        """``_hyper`` for a policy run: the learning rate, the discount, the model's learning rate and
+        the policy's ``beta`` / ``epsilon``, each a scalar or one value per instance.  With an array
+        among them the distinct combinations become parameter sets (their epsilon tables unused)
+        plus the column ``policy_params``, and every instance gets the index of its combination."""
+        run = prun.run
+        param = 0.0 if attr is None else getattr(pol, attr)
+        vals = (self.learning_rate, self.gamma, param, self._model_lr())
+        cols = _device.param_columns(vals, self.n_envs)
+        if cols is None:
+            run.alpha, run.gamma, run.model_lr = float(vals[0]), float(vals[1]), float(vals[3])
+            prun.policy_param = float(param)
+            return
+
+        def fill(rows):
+            sets = (_lib.ParamSet * len(rows))()
+            for k, (a, g, _, m) in enumerate(rows):
+                _lib.check(_lib.lib().cobel_param_set_fill(float(a), float(g), 0.0, float(m),
+                                                           C.byref(sets[k])))
+            self._ppar_rows = np.ascontiguousarray(rows[:, 2], dtype=np.float64)
+            return sets
+        # (sets of their own, apart from the ones an EpsilonGreedy launch of this agent builds)
+        new = _device.param_sets(cols, self._ppol[0], fill, self.device)
+        if new is not None:
+            self._ppol = new[:4] + (torch.as_tensor(self._ppar_rows, device=self.device),)
+        _, sets_dev, index_dev, n_sets, ppar_dev = self._ppol
+        run.alpha, run.gamma, run.model_lr = (float(v) for v in cols[0, [0, 1, 3]])
+        prun.policy_param = float(cols[0, 2])
+        run.param_sets, run.param_index = _lib.ptr(sets_dev), _lib.ptr(index_dev)
+        run.n_param_sets = n_sets
+        prun.policy_params = _lib.ptr(ppar_dev)
+
+    def _launch_policy(self, interface, pol, flags, trials_target, steps, budget, batch,
+                       describe=None, record=None) -> None:
+        """``_launch`` for the policies ``cobel_tab_policy_run`` serves: the same run struct inside a
+        ``cobel_tab_policy_run_t``."""
+        if type(pol) not in _POLICY_KINDS:
+            raise NotImplementedError(
+                '%s selects with EpsilonGreedy, Softmax, ExclusiveEpsilonGreedy or RandomDiscrete; '
+                'got %s' % (type(self).__name__, type(pol).__name__))
+        if record is not None:
+            raise NotImplementedError('rollout records sessions that select with EpsilonGreedy; '
+                                      'got %s' % type(pol).__name__)
+        kind, attr = _POLICY_KINDS[type(pol)]
+        if kind == _lib.POLICY_RANDOM:
+            assert pol.actions == self.n_actions, \
+                'RandomDiscrete(%d) on a world of %d actions' % (pol.actions, self.n_actions)
+        prun = _lib.TabPolicyRun()
+        run = prun.run
+        self._fill_run(run, interface, flags, trials_target, steps, budget)
+        run.q = _lib.ptr(self._q)
+        run.batches_done = _lib.ptr(self.batches_done)
+        run.agent = self.agent_kind
+        run.flags = flags | self.extra_flags
+        run.batch = batch
+        prun.policy = kind
+        self._hyper_policy(prun, pol, attr)
+        self._extra(run)
+        if describe is not None:
+            _lib.check(_lib.lib().cobel_tab_policy_plan(interface.handle.ptr, C.byref(prun), describe))
+            return
+        ev = getattr(self, 'launch_events', None)
+        pair = None
+        if ev is not None:
+            pair = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+            pair[0].record()
+        _lib.check(_lib.lib().cobel_tab_policy_run(interface.handle.ptr, C.byref(prun),
+                                                   _lib.current_stream(self.device)))
+        if pair is not None:
+            pair[1].record()
+            ev.append(pair)
+
     # -- a test session that records ----------------------------------------------------------------
     rollout_element_stores = False   # True: one store per record entry (tests, A/B comparisons)
 
@@ -159,6 +246,9 @@ class TabularAgent(FusedAgent):
             raise NotImplementedError('rollout records sessions on a Gridworld or a Topology')
         if trials < 1 or steps < 1:
             raise IndexError('rollout: trials = %d, steps = %d (both at least 1)' % (trials, steps))
+        if type(self.policy_test) is not EpsilonGreedy:
+            raise NotImplementedError('rollout records sessions that select with EpsilonGreedy; '
+                                      'policy_test is a %s' % type(self.policy_test).__name__)
         pol, flags, first = self._session_begin(interface, trials, False)
         record = TrajectoryRecord(interface, self.n_envs, trials, steps, self.device, first)
         self._one_launch_session(first, trials, lambda: self._launch(
@@ -180,8 +270,15 @@ class TabularAgent(FusedAgent):
         return super().env_steps()
 
     def describe_launch(self, interface, pol, flags, trials_target, steps, budget, batch) -> dict:
-        """Which kernel ``_launch`` would take with these arguments (``cobel_tab_describe``)."""
+        """Which kernel ``_launch`` would take with these arguments (``cobel_tab_describe``); for
+        a Softmax, ExclusiveEpsilonGreedy or RandomDiscrete policy the plan of
+        ``cobel_tab_policy_run`` (``cobel_tab_policy_plan``)."""
         out = (C.c_int32 * 4)()
+        if type(pol) is not EpsilonGreedy:
+            TabularAgent._launch_policy(self, interface, pol, flags, trials_target, steps, budget,
+                                        batch, describe=out)
+            return {'kernel': 'policy', 'lds_bytes': int(out[0]), 'threads_per_workgroup': int(out[1]),
+                    'instances_per_workgroup': int(out[2]), 'workgroups': int(out[3])}
         TabularAgent._launch(self, interface, pol, flags, trials_target, steps, budget, batch,
                              describe=out)
         return {'kernel': int(out[0]), 'lds_bytes': int(out[1]), 'workgroups_per_cu': int(out[2]),

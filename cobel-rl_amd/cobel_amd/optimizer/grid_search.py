@@ -29,8 +29,8 @@ def _file_name(combination: tuple) -> str:
 def spread_over_instances(combinations: list[dict], nb_runs: int) -> tuple[dict, np.ndarray]:
     """Per-instance hyper-parameter arrays for ``len(combinations) * nb_runs`` instances
     (combination-major, run-minor) and, for each instance, the index of its combination.  The
-    arrays go straight into an agent's ``learning_rate`` / ``gamma`` or a policy's ``epsilon`` —
-    and into an ``SFMAMemory``: ``decay_inhibition``, ``decay_strength``, ``learning_rate``,
+    arrays go straight into an agent's ``learning_rate`` / ``gamma`` or a policy's ``epsilon`` /
+    ``Softmax.beta`` — and into an ``SFMAMemory``: ``decay_inhibition``, ``decay_strength``, ``learning_rate``,
     ``beta``, ``C_step``, ``I_step``, ``R_threshold``, ``reward_modulation``, ``blend``,
     ``interpolation_fwd`` / ``_rev`` and ``mode`` (an array of mode names)."""
     which = np.repeat(np.arange(len(combinations)), nb_runs)

@@ -478,6 +478,69 @@ COBEL_API int cobel_tab_describe(const cobel_world_t* world, const cobel_tab_run
 COBEL_API int cobel_tab_scratch_check(const void* scratch /* [dev] */, int64_t scratch_bytes,
                                       void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * QAgent and Dyna-Q with the reference's other discrete policies: Softmax (policy/softmax.py),
+ * ExclusiveEpsilonGreedy (policy/greedy.py:91-147) and RandomDiscrete (policy/random.py:13-75).
+ * A kernel and an entry point of their own (csrc/tabular_policy.hip, one wavefront per instance,
+ * tables in LDS); EpsilonGreedy runs take cobel_tab_run as before.  `run` is a cobel_tab_run_t as
+ * cobel_tab_run takes it — the same q, model, replay_log, inst, monitor, last_exp and counter
+ * formats, the same Philox streams and order of effects as its general kernel, so sessions on
+ * either entry point interleave on the same tables — with run.epsilon and the epsilon tables of the
+ * parameter sets ignored.  Served: worlds of 1 .. 8 actions and up to 1 024 states whose transition
+ * rows are tables; COBEL_AGENT_Q and COBEL_AGENT_DYNAQ (model [N][S][n_actions]); batch 0 ..
+ * COBEL_MAX_BATCH; the flags COBEL_F_LEARN, NO_REPLAY, MASK_ACTIONS and TEST_STREAM.
+ * batches_done counts every batch drawn from a non-empty source (as the general kernel counts).
+ *
+ * Selection is float64 whatever the table dtype and consumes exactly ONE draw of the policy stream:
+ *   Softmax    e_a = exp((v_a - max) * beta) over the allowed actions, summed in action order,
+ *              p_a = e_a / sum
+ *   Exclusive  ties by exact equality; p_a = ((1 - eps) * tie_a) / n_ties, then
+ *              p_a += (eps * !tie_a) / max(n_allowed - n_ties, 1)
+ *              (eps = 1 with every allowed value tied: every probability is 0, as in the
+ *              reference, whose Generator.choice then raises; the action here is 0)
+ *   both      the action is Generator.choice's: sequential cumulative sum, division by the last
+ *              entry, the count of entries <= u (u: the double draw of the counter)
+ *   Random     int(rng.integers(n_actions)): the bounded integer draw of the counter, as
+ *              cobel_rng_bounded; values and mask are ignored, as the reference ignores them
+ * policy_param is beta (Softmax) or epsilon (Exclusive).  With run.param_index instance i uses
+ * policy_params[run.param_index[i]] beside alpha, gamma and model_lr of its parameter set; without
+ * policy_params the launch-wide policy_param applies to every instance.
+ *
+ * COBEL_E_ARG, before any launch: a NULL table, an unknown policy, beta <= 0 or epsilon outside
+ * [0, 1] (policy_param, or an entry of policy_params), an action mask with a row that allows no
+ * action, policy_params without run.param_index.  COBEL_E_UNSUPPORTED, with the limit in the
+ * message: more than 8 actions, more than 1 024 states, batch above COBEL_MAX_BATCH,
+ * COBEL_F_EPISODIC, worlds whose rows are distributions, a log of two words per entry.  (The mask
+ * and policy_params are device memory: checking them copies them to the host and waits for the
+ * stream.) */
+enum { COBEL_POLICY_SOFTMAX = 1, COBEL_POLICY_EXCLUSIVE = 2, COBEL_POLICY_RANDOM = 3 };
+typedef struct {
+  cobel_tab_run_t run;
+  int32_t policy;              /* COBEL_POLICY_*                                              */
+  int32_t reserved_;
+  double policy_param;         /* beta / epsilon of every instance (policy_params == NULL)    */
+  const double* policy_params; /* [dev] [run.n_param_sets] or NULL                            */
+} cobel_tab_policy_run_t;
+COBEL_API int cobel_tab_policy_run(const cobel_world_t* world, const cobel_tab_policy_run_t* run,
+                                   void* stream);
+/* What cobel_tab_policy_run would launch (same checks but the ones that read device memory):
+ * out = {LDS bytes per workgroup, its threads, instances per workgroup, workgroups}; zeros for
+ * n = 0 and where the run is refused. */
+COBEL_API int cobel_tab_policy_plan(const cobel_world_t* world, const cobel_tab_policy_run_t* run,
+                                    int32_t* out /* [host] [4] */);
+/* The three policies as a single call on n rows v[n][A] (float64; A = 1 .. 8; the host classes
+ * round the values to float32 first where the reference's ties are float32 ties), by the device
+ * routine of the run kernel, one group of eight lanes per row; stands beside cobel_softmax_n.
+ * mask_bits: [n] bytes (bit a = action a allowed) or NULL.  Softmax / Exclusive: u[n] the uniform
+ * draws, param[n_param] (n_param = 1 or n) beta / epsilon; k is not read.  Random: k[n] holds the
+ * 32-bit word of each bounded draw in its low half, action = (word * A) >> 32; v, mask_bits, u
+ * and param are not read.  act[n] and probs[n][A] may each be NULL.  Every pointer is device
+ * memory; param and mask_bits are copied back and checked as above before the launch. */
+COBEL_API int cobel_policy_select_n(int32_t policy, const double* v, const uint8_t* mask_bits,
+                                    const double* u_or_null, const uint64_t* k_or_null,
+                                    const double* param, int32_t n_param, uint8_t* act,
+                                    double* probs, int32_t n, int32_t A, void* stream);
+
 /* The additions NumPy's pairwise summation (np.sum over a contiguous float32 vector, agent/sr.py:
  * 302-306 `np.sum(SR[j] * rewards)`) performs on a vector of n elements of which only the k <= 32 at
  * `pos` (ascending) are not zero: step t is value[dst[t]] += value[src[t]] on slots 0..k-1, k - 1
