@@ -25,7 +25,7 @@ class TabularAgent(FusedAgent):
 
     agent_kind = _lib.AGENT_Q
     general_actions = True     # cobel_tab_run's general kernel takes any action count
-    exclusive_policy = True    # (_launch_policy; SFMA, with a launcher of its own, says False)
+    exclusive_policy = True    # (_launch's policy runs; SFMA, with a launcher of its own, says False)
     force_general = False      # True: always the general kernel (tests, A/B comparisons)
     extra_flags = 0            # COBEL_F_* testing switches ORed into every launch (F_NO_PWG, ...)
 
@@ -106,22 +106,51 @@ class TabularAgent(FusedAgent):
 
     def _launch(self, interface, pol, flags, trials_target, steps, budget, batch,
                 describe=None, record=None) -> None:
-        if type(pol) is not EpsilonGreedy:
-            return self._launch_policy(interface, pol, flags, trials_target, steps, budget, batch,
-                                       describe, record)
-        run = _lib.TabRun()
+        """One launch (or, with ``describe``, its plan): an EpsilonGreedy run is a ``cobel_tab_run_t``
+        for ``cobel_tab_run`` / ``cobel_tab_rollout``; the policies of ``_POLICY_KINDS`` take the same
+        run struct inside a ``cobel_tab_policy_run_t`` to ``cobel_tab_policy_run``."""
+        greedy = type(pol) is EpsilonGreedy
+        if not greedy:
+            if type(pol) not in _POLICY_KINDS:
+                raise NotImplementedError(
+                    '%s selects with EpsilonGreedy, Softmax, ExclusiveEpsilonGreedy or RandomDiscrete; '
+                    'got %s' % (type(self).__name__, type(pol).__name__))
+            if record is not None:
+                raise NotImplementedError('rollout records sessions that select with EpsilonGreedy; '
+                                          'got %s' % type(pol).__name__)
+            kind, attr = _POLICY_KINDS[type(pol)]
+            if kind == _lib.POLICY_RANDOM:
+                assert pol.actions == self.n_actions, \
+                    'RandomDiscrete(%d) on a world of %d actions' % (pol.actions, self.n_actions)
+        lib, world = _lib.lib(), interface.handle.ptr
+        call = _lib.TabRun() if greedy else _lib.TabPolicyRun()
+        run = call if greedy else call.run
         self._fill_run(run, interface, flags, trials_target, steps, budget)
         run.q = _lib.ptr(self._q)
         run.batches_done = _lib.ptr(self.batches_done)
-        run.scratch, run.scratch_bytes = _lib.ptr(self._scratch), self._scratch.numel() * 4
         run.agent = self.agent_kind
-        run.flags = flags | self.extra_flags | (_lib.F_TAB_GENERAL if self.force_general else 0)
+        run.flags = flags | self.extra_flags
         run.batch = batch
-        self._hyper(run, self.learning_rate, self.gamma, pol.epsilon, self._model_lr())
+        if greedy:
+            run.scratch, run.scratch_bytes = _lib.ptr(self._scratch), self._scratch.numel() * 4
+            if self.force_general:
+                run.flags |= _lib.F_TAB_GENERAL
+            self._hyper(run, self.learning_rate, self.gamma, pol.epsilon, self._model_lr())
+        else:
+            call.policy = kind
+            self._hyper_policy(call, pol, attr)
         self._extra(run)
         if describe is not None:
-            _lib.check(_lib.lib().cobel_tab_describe(interface.handle.ptr, C.byref(run), describe))
+            plan = lib.cobel_tab_describe if greedy else lib.cobel_tab_policy_plan
+            _lib.check(plan(world, C.byref(call), describe))
             return
+        # (the entry point SURVEY.md section 8b names for this agent: cobel_tab_run with the kind checked)
+        if not greedy:
+            entry = lib.cobel_tab_policy_run
+        elif record is not None:    # rollout(): the same run struct around a trajectory record
+            call, entry = self._rollout_struct(run, record, world), lib.cobel_tab_rollout
+        else:
+            entry = lib.cobel_dynaq_run if self.agent_kind == _lib.AGENT_DYNAQ else lib.cobel_q_run
         # (`launch_events`: a pair of torch.cuda.Event recorded right around the library call —
         #  bench.py times the kernel without the host's preparation of its arguments)
         #  (a LIST that gets one pair appended per launch: a train() call may issue several)
@@ -130,15 +159,7 @@ class TabularAgent(FusedAgent):
         if ev is not None:
             pair = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             pair[0].record()
-        # (the entry point SURVEY.md section 8b names for this agent: cobel_tab_run with the kind checked)
-        if record is not None:      # rollout(): the same run struct around a trajectory record
-            ro = self._rollout_struct(run, record, interface.handle.ptr)
-            _lib.check(_lib.lib().cobel_tab_rollout(interface.handle.ptr, C.byref(ro),
-                                                    _lib.current_stream(self.device)))
-        else:
-            entry = (_lib.lib().cobel_dynaq_run if self.agent_kind == _lib.AGENT_DYNAQ
-                     else _lib.lib().cobel_q_run)
-            _lib.check(entry(interface.handle.ptr, C.byref(run), _lib.current_stream(self.device)))
+        _lib.check(entry(world, C.byref(call), _lib.current_stream(self.device)))
         if pair is not None:
             pair[1].record()
             ev.append(pair)
@@ -175,46 +196,6 @@ class TabularAgent(FusedAgent):
         run.param_sets, run.param_index = _lib.ptr(sets_dev), _lib.ptr(index_dev)
         run.n_param_sets = n_sets
         prun.policy_params = _lib.ptr(ppar_dev)
-
-    def _launch_policy(self, interface, pol, flags, trials_target, steps, budget, batch,
-                       describe=None, record=None) -> None:
-        """``_launch`` for the policies ``cobel_tab_policy_run`` serves: the same run struct inside a
-        ``cobel_tab_policy_run_t``."""
-        if type(pol) not in _POLICY_KINDS:
-            raise NotImplementedError(
-                '%s selects with EpsilonGreedy, Softmax, ExclusiveEpsilonGreedy or RandomDiscrete; '
-                'got %s' % (type(self).__name__, type(pol).__name__))
-        if record is not None:
-            raise NotImplementedError('rollout records sessions that select with EpsilonGreedy; '
-                                      'got %s' % type(pol).__name__)
-        kind, attr = _POLICY_KINDS[type(pol)]
-        if kind == _lib.POLICY_RANDOM:
-            assert pol.actions == self.n_actions, \
-                'RandomDiscrete(%d) on a world of %d actions' % (pol.actions, self.n_actions)
-        prun = _lib.TabPolicyRun()
-        run = prun.run
-        self._fill_run(run, interface, flags, trials_target, steps, budget)
-        run.q = _lib.ptr(self._q)
-        run.batches_done = _lib.ptr(self.batches_done)
-        run.agent = self.agent_kind
-        run.flags = flags | self.extra_flags
-        run.batch = batch
-        prun.policy = kind
-        self._hyper_policy(prun, pol, attr)
-        self._extra(run)
-        if describe is not None:
-            _lib.check(_lib.lib().cobel_tab_policy_plan(interface.handle.ptr, C.byref(prun), describe))
-            return
-        ev = getattr(self, 'launch_events', None)
-        pair = None
-        if ev is not None:
-            pair = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            pair[0].record()
-        _lib.check(_lib.lib().cobel_tab_policy_run(interface.handle.ptr, C.byref(prun),
-                                                   _lib.current_stream(self.device)))
-        if pair is not None:
-            pair[1].record()
-            ev.append(pair)
 
     # -- a test session that records ----------------------------------------------------------------
     rollout_element_stores = False   # True: one store per record entry (tests, A/B comparisons)
@@ -274,12 +255,10 @@ class TabularAgent(FusedAgent):
         a Softmax, ExclusiveEpsilonGreedy or RandomDiscrete policy the plan of
         ``cobel_tab_policy_run`` (``cobel_tab_policy_plan``)."""
         out = (C.c_int32 * 4)()
-        if type(pol) is not EpsilonGreedy:
-            TabularAgent._launch_policy(self, interface, pol, flags, trials_target, steps, budget,
-                                        batch, describe=out)
-            return {'kernel': 'policy', 'lds_bytes': int(out[0]), 'threads_per_workgroup': int(out[1]),
-                    'instances_per_workgroup': int(out[2]), 'workgroups': int(out[3])}
         TabularAgent._launch(self, interface, pol, flags, trials_target, steps, budget, batch,
                              describe=out)
+        if type(pol) is not EpsilonGreedy:
+            return {'kernel': 'policy', 'lds_bytes': int(out[0]), 'threads_per_workgroup': int(out[1]),
+                    'instances_per_workgroup': int(out[2]), 'workgroups': int(out[3])}
         return {'kernel': int(out[0]), 'lds_bytes': int(out[1]), 'workgroups_per_cu': int(out[2]),
                 'instances_per_workgroup': int(out[3])}

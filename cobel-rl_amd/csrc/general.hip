@@ -20,21 +20,12 @@
 
 #include "cobel_common.h"
 #include "cobel_policy.h"
+#include "cobel_tab_session.h"
 
 namespace {
 
 struct gen_args {
-  const cobel_wrec* rec;        // four-action worlds
-  const uint16_t* next_n;       // other action counts: [W][S][A]
-  const float* reward_s;        // [W][S]
-  const uint8_t* terminal_s;    // [W][S]
-  const uint16_t* starts;
-  const int32_t* start_off;
-  // transition rows that are distributions (cobel_world_set_transitions), or NULL
-  const uint32_t* succ_off;
-  const uint16_t* succ_state;
-  const double* succ_cdf;
-  int32_t S, n_worlds, A;
+  cobel_world_view w;
   cobel_tab_run_t r;
   float alpha_f, gamma_f, model_lr_f;
 };
@@ -248,10 +239,11 @@ template <int AGENT, int AMAX>
 __global__ __launch_bounds__(64) void k_tab_general(const gen_args G) {
   const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);   // (blocks of 8 .. 64 lanes, see the launch)
   if (i >= G.r.n) return;
-  const int S = G.S, A = G.A;
+  const cobel_world_view& W = G.w;
+  const int S = W.S, A = W.A;
   const uint32_t g = G.r.instance_base + (uint32_t)i;
-  const size_t wbase = (size_t)(g % (uint32_t)G.n_worlds) * S;
-  const int world = (int)(g % (uint32_t)G.n_worlds);
+  const size_t wbase = (size_t)(g % (uint32_t)W.n_worlds) * S;
+  const int world = (int)(g % (uint32_t)W.n_worlds);
   float* const Q = G.r.q + (size_t)i * S * A;
   uint64_t* const model = AGENT == COBEL_AGENT_DYNAQ ? G.r.model + (size_t)i * S * A : nullptr;
   uint16_t* const mindex =
@@ -265,13 +257,6 @@ __global__ __launch_bounds__(64) void k_tab_general(const gen_args G) {
                              ? G.r.replay_log + (size_t)i * G.r.log_cap * (wide ? 2 : 1)
                              : nullptr;
 
-  auto next_of = [&](int s, int a) -> int {
-    return G.rec ? (int)G.rec[wbase + s].next[a] : (int)G.next_n[(wbase + s) * A + a];
-  };
-  auto reward_of = [&](int s) -> float { return G.rec ? G.rec[wbase + s].reward : G.reward_s[wbase + s]; };
-  auto terminal_of = [&](int s) -> uint32_t {
-    return G.rec ? G.rec[wbase + s].terminal : (uint32_t)G.terminal_s[wbase + s];
-  };
   auto row_max = [&](int s) -> float {
     float m = Q[(size_t)s * A];
     for (int a = 1; a < A; ++a) m = fmaxf(m, Q[(size_t)s * A + a]);
@@ -279,25 +264,14 @@ __global__ __launch_bounds__(64) void k_tab_general(const gen_args G) {
   };
 
   int32_t* const inst = G.r.inst + (size_t)i * COBEL_I_WORDS;
-  int state = inst[COBEL_I_STATE];
-  int step = inst[COBEL_I_STEP];
-  int trial = inst[COBEL_I_TRIAL];
-  uint32_t ce = (uint32_t)inst[COBEL_I_CTR_ENV];
-  uint32_t cp = (uint32_t)inst[COBEL_I_CTR_POLICY];
-  uint32_t cm = (uint32_t)inst[COBEL_I_CTR_MEMORY];
-  uint32_t loglen = (uint32_t)inst[COBEL_I_LOG_LEN];
-  uint32_t iflags = (uint32_t)inst[COBEL_I_FLAGS];
-  double trew = *reinterpret_cast<const double*>(inst + COBEL_I_REWARD_LO);
-  unsigned long long executed = 0, batches = 0;
+  cobel_tab_session R;     // (the state is taken as it was left, unclamped)
+  R.load(inst, W, world);
 
   const uint32_t flags = G.r.flags;
   const bool learn = flags & COBEL_F_LEARN;
-  const uint32_t pol_stream =
-      (flags & COBEL_F_TEST_STREAM) ? COBEL_STREAM_POLICY_TEST : COBEL_STREAM_POLICY;
+  const uint32_t pol_stream = cobel_policy_stream(flags);
   const uint8_t* const amask = (flags & COBEL_F_MASK_ACTIONS) ? G.r.action_mask : nullptr;
   const uint64_t seed = G.r.seed;
-  const int start_lo = G.start_off[world];
-  const uint32_t start_cnt = (uint32_t)(G.start_off[world + 1] - start_lo);
   const int B = G.r.batch;
   const bool wants_replay = learn && !(flags & COBEL_F_NO_REPLAY) && B > 0;
   const bool episodic = AGENT == COBEL_AGENT_DYNAQ && wants_replay && (flags & COBEL_F_EPISODIC);
@@ -305,10 +279,7 @@ __global__ __launch_bounds__(64) void k_tab_general(const gen_args G) {
       wants_replay && (AGENT == COBEL_AGENT_DYNAQ ? !(flags & COBEL_F_EPISODIC) : rlog != nullptr);
   double alpha = G.r.alpha, gamma = G.r.gamma, eps = G.r.epsilon;
   float alpha_f = G.alpha_f, gamma_f = G.gamma_f, mlr_f = G.model_lr_f;
-  if (G.r.param_index) {
-    const int k = (int)G.r.param_index[i];
-    const cobel_param_set_t* const P =
-        G.r.param_sets + (k < G.r.n_param_sets ? k : G.r.n_param_sets - 1);
+  if (const cobel_param_set_t* const P = cobel_pick_param_set(G.r, i)) {
     alpha = P->alpha;
     gamma = P->gamma;
     eps = P->epsilon;
@@ -413,7 +384,7 @@ __global__ __launch_bounds__(64) void k_tab_general(const gen_args G) {
     run_batch(
         [&](int j) -> rec_t {
           const uint32_t idx =
-              cobel_draw_bounded(cm, (uint32_t)j, g, COBEL_STREAM_MEMORY, seed, SA);
+              cobel_draw_bounded(R.cm, (uint32_t)j, g, COBEL_STREAM_MEMORY, seed, SA);
           return rec_t{idx, model[idx], 0ull};
         },
         [&](const rec_t& rc) -> upd_t {
@@ -422,19 +393,14 @@ __global__ __launch_bounds__(64) void k_tab_general(const gen_args G) {
                        __builtin_bit_cast(float, (uint32_t)rc.bits), (hi >> 16) & 1u};
         },
         true);
-    cm += 1u;
+    R.cm += 1u;
   };
 
   int budget = G.r.step_budget > 0 ? G.r.step_budget : 0x7fffffff;
   while (true) {
-    if (!(iflags & 1u)) {
-      if (trial >= G.r.trials_target) break;
-      state = (int)G.starts[start_lo + (int)cobel_draw_bounded(ce, 0u, g, COBEL_STREAM_ENV, seed,
-                                                               start_cnt)];
-      ce += 1u;
-      step = 0;
-      trew = 0.0;
-      iflags |= 1u;
+    if (!(R.iflags & 1u)) {
+      if (R.done(G.r)) break;
+      R.begin_trial(W, G.r, g);
     }
     if (budget == 0) break;
     budget -= 1;
@@ -442,82 +408,66 @@ __global__ __launch_bounds__(64) void k_tab_general(const gen_args G) {
     // ---- select + env.step --------------------------------------------------------------------
     float qv[AMAX];
 #pragma unroll
-    for (int a = 0; a < AMAX; ++a) qv[a] = a < A ? Q[(size_t)state * A + a] : 0.0f;
-    const double u = cobel_draw_u01(cp, 0u, g, pol_stream, seed);
-    cp += 1u;
-    const int a = cobel_eps_greedy_select_n<float, AMAX>(qv, A, mask_word<AMAX>(amask, state), u,
+    for (int a = 0; a < AMAX; ++a) qv[a] = a < A ? Q[(size_t)R.state * A + a] : 0.0f;
+    const double u = cobel_draw_u01(R.cp, 0u, g, pol_stream, seed);
+    R.cp += 1u;
+    const int a = cobel_eps_greedy_select_n<float, AMAX>(qv, A, mask_word<AMAX>(amask, R.state), u,
                                                          eps, nullptr);
     int ns;
-    if (G.succ_off) {   // the successor is drawn from the row of sas (gridworld.py:119-123): one
+    if (W.succ_off) {   // the successor is drawn from the row of sas (gridworld.py:119-123): one
                         // double of the env stream, at the counter the trial starts share
-      const double ue = cobel_draw_u01(ce, COBEL_SUB_DOUBLE, g, COBEL_STREAM_ENV, seed);
-      ce += 1u;
-      ns = cobel_draw_successor(G.succ_off, G.succ_state, G.succ_cdf,
-                                (wbase + (size_t)state) * A + a, ue);
+      const double ue = cobel_draw_u01(R.ce, COBEL_SUB_DOUBLE, g, COBEL_STREAM_ENV, seed);
+      R.ce += 1u;
+      ns = W.drawn_next(wbase, R.state, a, ue);
     } else {
-      ns = next_of(state, a);
+      ns = W.next(wbase, R.state, a);
     }
-    const float r = reward_of(ns);
-    const uint32_t end = terminal_of(ns), nt = 1u - end;
+    const float r = W.reward(wbase, ns);
+    const uint32_t end = W.terminal(wbase, ns), nt = 1u - end;
     float td_online = 0.0f;
     if (learn) {
-      if (AGENT == COBEL_AGENT_DYNAQ) {   // memory/dyna_q.py:92-96, float32
-        const size_t sa = (size_t)state * A + a;
-        const float R = __builtin_bit_cast(float, (uint32_t)model[sa]);
-        const float d = r - R;
-        const float Rn = R + mlr_f * d;
-        model[sa] = cobel_model_pack(Rn, (uint32_t)ns, nt);
-        if (mindex)
-          mindex[sa] = (uint16_t)((uint32_t)ns | (nt << 14) |
-                                  (__builtin_bit_cast(uint32_t, Rn) ? 0x8000u : 0u));
-      }
+      if (AGENT == COBEL_AGENT_DYNAQ)
+        cobel_model_store_f32(model, mindex, (size_t)R.state * A + a, r, (uint32_t)ns, nt, mlr_f);
       {   // online TD, float32
         const float m = row_max(ns);
-        const float qsa = Q[(size_t)state * A + a];
+        const float qsa = Q[(size_t)R.state * A + a];
         const float gnt = nt ? gamma_f : 0.0f;
         float td = r + gnt * m;
         td = td - qsa;
-        Q[(size_t)state * A + a] = qsa + alpha_f * td;
+        Q[(size_t)R.state * A + a] = qsa + alpha_f * td;
         td_online = td;
       }
-      if (rlog && loglen < (uint32_t)G.r.log_cap) {   // q.py:213
+      if (rlog && R.loglen < (uint32_t)G.r.log_cap) {   // q.py:213
         if (wide) {
-          rlog[2u * loglen] = (uint64_t)__builtin_bit_cast(uint32_t, r) |
+          rlog[2u * R.loglen] = (uint64_t)__builtin_bit_cast(uint32_t, r) |
                               ((uint64_t)((uint32_t)a | (nt << 8)) << 32);
-          rlog[2u * loglen + 1u] = (uint64_t)(uint32_t)state | ((uint64_t)(uint32_t)ns << 32);
+          rlog[2u * R.loglen + 1u] = (uint64_t)(uint32_t)R.state | ((uint64_t)(uint32_t)ns << 32);
         } else {
-          rlog[loglen] = cobel_log_pack(r, (uint32_t)state, (uint32_t)a, (uint32_t)ns, nt, A_log);
+          rlog[R.loglen] =
+              cobel_log_pack(r, (uint32_t)R.state, (uint32_t)a, (uint32_t)ns, nt, A_log);
         }
-        loglen += 1u;
+        R.loglen += 1u;
       }
     }
-    if (G.r.last_exp) {
-      int32_t* const e = G.r.last_exp + (size_t)i * 6;
-      e[0] = state;
-      e[1] = a;
-      e[2] = ns;
-      e[3] = (int32_t)nt;
-      e[4] = __builtin_bit_cast(int32_t, r);
-      e[5] = __builtin_bit_cast(int32_t, td_online);
-    }
-    trew += (double)r;
-    executed += 1ull;
+    if (G.r.last_exp) cobel_last_exp_store(G.r.last_exp, i, R.state, a, ns, nt, r, td_online);
+    R.trew += (double)r;
+    R.executed += 1ull;
     if (G.r.occupancy) atomicAdd(G.r.occupancy + wbase + ns, 1ull);
-    const bool trial_over = end || (step + 1 >= G.r.steps_per_trial);
-    state = ns;
+    const bool trial_over = end || (R.step + 1 >= G.r.steps_per_trial);
+    R.state = ns;
 
     // ---- planning / replay, every update in the reference's order -----------------------------
     if (replay_each_step) {
       if (AGENT == COBEL_AGENT_DYNAQ) {
         plan_dynaq();
-        batches += 1ull;
+        R.batches += 1ull;
       } else {
-        if (loglen > 0u) {   // q.py:353-354: idx = rng.choice(len(M), batch_size), one vector draw
-          batches += 1ull;
+        if (R.loglen > 0u) {   // q.py:353-354: idx = rng.choice(len(M), batch_size), one draw
+          R.batches += 1ull;
           run_batch(
               [&](int j) -> rec_t {
                 const uint32_t idx =
-                    cobel_draw_bounded(cm, (uint32_t)j, g, COBEL_STREAM_MEMORY, seed, loglen);
+                    cobel_draw_bounded(R.cm, (uint32_t)j, g, COBEL_STREAM_MEMORY, seed, R.loglen);
                 if (wide) return rec_t{idx, rlog[2u * idx], rlog[2u * idx + 1u]};
                 return rec_t{idx, rlog[idx], 0ull};
               },
@@ -532,42 +482,22 @@ __global__ __launch_bounds__(64) void k_tab_general(const gen_args G) {
               },
               false);
         }
-        cm += 1u;
+        R.cm += 1u;
       }
     }
 
     if (trial_over) {
-      if (trial >= 0 && trial < G.r.trial_cap) {
-        const size_t m = cobel_mon_offset(G.r.mon_stripes, G.r.trial_cap) + (size_t)trial;
-        if (G.r.lat_sum) atomicAdd(G.r.lat_sum + m, (unsigned long long)step);
-        if (G.r.lat_cnt) atomicAdd(G.r.lat_cnt + m, 1ull);
-        if (G.r.reward_sum) atomicAdd(G.r.reward_sum + m, trew);
-        if (G.r.resp_cnt && trew > 0.0) atomicAdd(G.r.resp_cnt + m, 1ull);
-        if (G.r.lat_trace) G.r.lat_trace[(size_t)i * G.r.trial_cap + trial] = step;
-      }
-      trial += 1;
-      iflags &= ~1u;
+      R.end_trial(G.r, i);
       if (episodic) {   // dyna_q.py:210-211
         plan_dynaq();
-        batches += 1ull;
+        R.batches += 1ull;
       }
     } else {
-      step += 1;
+      R.step += 1;
     }
   }
 
-  inst[COBEL_I_STATE] = state;
-  inst[COBEL_I_STEP] = step;
-  inst[COBEL_I_TRIAL] = trial;
-  inst[COBEL_I_CTR_ENV] = (int32_t)ce;
-  inst[COBEL_I_CTR_POLICY] = (int32_t)cp;
-  inst[COBEL_I_CTR_MEMORY] = (int32_t)cm;
-  inst[COBEL_I_LOG_LEN] = (int32_t)loglen;
-  inst[COBEL_I_FLAGS] = (int32_t)iflags;
-  *reinterpret_cast<double*>(inst + COBEL_I_REWARD_LO) = trew;
-  *reinterpret_cast<unsigned long long*>(inst + COBEL_I_STEPS_LO) += executed;
-  if (G.r.steps_done && executed) atomicAdd(G.r.steps_done, executed);
-  if (G.r.batches_done && batches) atomicAdd(G.r.batches_done, batches);
+  R.store(inst, G.r);
 }
 
 // (an if chain: it names the instantiations in the order the code object has always held them in)
@@ -596,24 +526,13 @@ void cobel_tab_general_plan(const cobel_tab_run_t& r, cobel_tab_plan& plan) {
 int cobel_tab_general_launch(const cobel_world* world, const cobel_tab_run_t& r,
                              const cobel_tab_plan& plan, hipStream_t st) {
   gen_args G;
-  G.rec = world->rec;
-  G.next_n = world->next_n;
-  G.reward_s = world->reward_s;
-  G.terminal_s = world->terminal_s;
-  G.starts = world->starts;
-  G.start_off = world->start_off;
-  G.succ_off = world->succ_off;
-  G.succ_state = world->succ_state;
-  G.succ_cdf = world->succ_cdf;
-  G.S = world->n_states;
-  G.n_worlds = world->n_worlds;
-  G.A = world->n_actions;
+  G.w = cobel_world_view_of(world);
   G.r = r;
   G.alpha_f = (float)r.alpha;
   G.gamma_f = (float)r.gamma;
   G.model_lr_f = (float)r.model_lr;
-  const auto kernel = r.agent == COBEL_AGENT_DYNAQ ? general_variant<COBEL_AGENT_DYNAQ>(G.A)
-                                                   : general_variant<COBEL_AGENT_Q>(G.A);
+  const auto kernel = r.agent == COBEL_AGENT_DYNAQ ? general_variant<COBEL_AGENT_DYNAQ>(G.w.A)
+                                                   : general_variant<COBEL_AGENT_Q>(G.w.A);
   COBEL_HIP_TRY(cobel_launch(kernel, dim3((unsigned)((r.n + plan.lpb - 1) / plan.lpb)),
                              dim3(plan.lpb), 0, st, G));
   return COBEL_OK;

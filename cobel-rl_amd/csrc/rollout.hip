@@ -20,20 +20,12 @@
 // launch.  COBEL_ROLLOUT_ELEMENT_STORES keeps the store per entry for comparison.
 #include "cobel_common.h"
 #include "cobel_policy.h"
+#include "cobel_tab_session.h"
 
 namespace {
 
 struct rollout_args {
-  const cobel_wrec* rec;        // four-action worlds
-  const uint16_t* next_n;       // other action counts: [W][S][A]
-  const float* reward_s;        // [W][S]
-  const uint8_t* terminal_s;    // [W][S]
-  const uint16_t* starts;
-  const int32_t* start_off;
-  const uint32_t* succ_off;     // transition rows that are distributions, or NULL
-  const uint16_t* succ_state;
-  const double* succ_cdf;
-  int32_t S, n_worlds, A;
+  cobel_world_view w;
   cobel_tab_rollout_t o;
 };
 
@@ -50,34 +42,24 @@ __global__ __launch_bounds__(64) void k_tab_rollout(const rollout_args G) {
   const cobel_tab_run_t& R = G.o.run;
   const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   if (i >= R.n) return;
-  const int S = G.S, A = G.A;
+  const cobel_world_view& W = G.w;
+  const int S = W.S, A = W.A;
   const uint32_t g = R.instance_base + (uint32_t)i;
-  const int world = (int)(g % (uint32_t)G.n_worlds);
+  const int world = (int)(g % (uint32_t)W.n_worlds);
   const size_t wbase = (size_t)world * S;
   const float* const Q = R.q + (size_t)i * S * A;
 
   int32_t* const inst = R.inst + (size_t)i * COBEL_I_WORDS;
-  int state = min(max(inst[COBEL_I_STATE], 0), S - 1);
-  int step = inst[COBEL_I_STEP];
-  int trial = inst[COBEL_I_TRIAL];
-  uint32_t ce = (uint32_t)inst[COBEL_I_CTR_ENV];
-  uint32_t cp = (uint32_t)inst[COBEL_I_CTR_POLICY];
-  uint32_t iflags = (uint32_t)inst[COBEL_I_FLAGS];
-  double trew = *reinterpret_cast<const double*>(inst + COBEL_I_REWARD_LO);
-  unsigned long long executed = 0;
+  cobel_tab_session X;
+  X.load(inst, W, world);
+  X.state = min(max(X.state, 0), S - 1);
 
   const uint32_t flags = R.flags;
-  const uint32_t pol_stream =
-      (flags & COBEL_F_TEST_STREAM) ? COBEL_STREAM_POLICY_TEST : COBEL_STREAM_POLICY;
+  const uint32_t pol_stream = cobel_policy_stream(flags);
   const uint8_t* const amask = (flags & COBEL_F_MASK_ACTIONS) ? R.action_mask : nullptr;
   const uint64_t seed = R.seed;
-  const int start_lo = G.start_off[world];
-  const uint32_t start_cnt = (uint32_t)(G.start_off[world + 1] - start_lo);
   double eps = R.epsilon;
-  if (R.param_index) {
-    const int k = (int)R.param_index[i];
-    eps = R.param_sets[k < R.n_param_sets ? k : R.n_param_sets - 1].epsilon;
-  }
+  if (const cobel_param_set_t* const P = cobel_pick_param_set(R, i)) eps = P->epsilon;
 
   // the record: session trial t = trial - first, entry e = (i * trials + t) * steps + step
   const int trials = G.o.trials, steps = G.o.steps;
@@ -105,55 +87,49 @@ __global__ __launch_bounds__(64) void k_tab_rollout(const rollout_args G) {
   };
 
   while (true) {
-    if (!(iflags & 1u)) {
-      if (trial >= R.trials_target) break;
-      state = (int)G.starts[start_lo + (int)cobel_draw_bounded(ce, 0u, g, COBEL_STREAM_ENV, seed,
-                                                               start_cnt)];
-      ce += 1u;
-      step = 0;
-      trew = 0.0;
-      iflags |= 1u;
-      if ((unsigned)(trial - first) < (unsigned)trials)
-        G.o.start[(size_t)i * trials + (trial - first)] = (int16_t)state;
+    if (!(X.iflags & 1u)) {
+      if (X.done(R)) break;
+      X.begin_trial(W, R, g);
+      if ((unsigned)(X.trial - first) < (unsigned)trials)
+        G.o.start[(size_t)i * trials + (X.trial - first)] = (int16_t)X.state;
     }
 
     // ---- select + env.step ----------------------------------------------------------------------
     float qv[AMAX];
     if (AMAX == 4) {
-      const float4 row = reinterpret_cast<const float4*>(Q)[state];
+      const float4 row = reinterpret_cast<const float4*>(Q)[X.state];
       qv[0] = row.x;
       qv[1] = row.y;
       qv[2] = row.z;
       qv[3] = row.w;
     } else {
 #pragma unroll
-      for (int a = 0; a < AMAX; ++a) qv[a] = a < A ? Q[(size_t)state * A + a] : 0.0f;
+      for (int a = 0; a < AMAX; ++a) qv[a] = a < A ? Q[(size_t)X.state * A + a] : 0.0f;
     }
-    const double u = cobel_draw_u01(cp, 0u, g, pol_stream, seed);
-    cp += 1u;
-    const int a = cobel_eps_greedy_select_n<float, AMAX>(qv, A, rollout_mask<AMAX>(amask, state), u,
-                                                         eps, nullptr);
+    const double u = cobel_draw_u01(X.cp, 0u, g, pol_stream, seed);
+    X.cp += 1u;
+    const int a = cobel_eps_greedy_select_n<float, AMAX>(qv, A, rollout_mask<AMAX>(amask, X.state),
+                                                         u, eps, nullptr);
     int ns;
-    if (G.succ_off) {   // the successor is drawn from the row (gridworld.py:119-123)
-      const double ue = cobel_draw_u01(ce, COBEL_SUB_DOUBLE, g, COBEL_STREAM_ENV, seed);
-      ce += 1u;
-      ns = cobel_draw_successor(G.succ_off, G.succ_state, G.succ_cdf,
-                                (wbase + (size_t)state) * A + a, ue);
+    if (W.succ_off) {   // the successor is drawn from the row (gridworld.py:119-123)
+      const double ue = cobel_draw_u01(X.ce, COBEL_SUB_DOUBLE, g, COBEL_STREAM_ENV, seed);
+      X.ce += 1u;
+      ns = W.drawn_next(wbase, X.state, a, ue);
     } else {
-      ns = G.rec ? (int)G.rec[wbase + state].next[a] : (int)G.next_n[(wbase + state) * A + a];
+      ns = W.next(wbase, X.state, a);
     }
-    const float r = G.rec ? G.rec[wbase + ns].reward : G.reward_s[wbase + ns];
-    const uint32_t end = G.rec ? G.rec[wbase + ns].terminal : (uint32_t)G.terminal_s[wbase + ns];
-    trew += (double)r;
-    executed += 1ull;
+    const float r = W.reward(wbase, ns);
+    const uint32_t end = W.terminal(wbase, ns);
+    X.trew += (double)r;
+    X.executed += 1ull;
     if (R.occupancy) atomicAdd(R.occupancy + wbase + ns, 1ull);
-    const bool trial_over = end || (step + 1 >= R.steps_per_trial);
+    const bool trial_over = end || (X.step + 1 >= R.steps_per_trial);
 
     // ---- the record -----------------------------------------------------------------------------
     const bool in_record =
-        (unsigned)(trial - first) < (unsigned)trials && (unsigned)step < (unsigned)steps;
+        (unsigned)(X.trial - first) < (unsigned)trials && (unsigned)X.step < (unsigned)steps;
     if (in_record) {
-      const size_t e = ((size_t)i * trials + (size_t)(trial - first)) * steps + (size_t)step;
+      const size_t e = ((size_t)i * trials + (size_t)(X.trial - first)) * steps + (size_t)X.step;
       const int slot = (int)(e & 3u);
       if (fill == 0) e0 = e;
       sacc |= (uint64_t)(uint16_t)ns << (16 * slot);
@@ -161,35 +137,18 @@ __global__ __launch_bounds__(64) void k_tab_rollout(const rollout_args G) {
       fill += 1;
       if (!wide || slot == 3) flush();
     }
-    state = ns;
+    X.state = ns;
 
     if (trial_over) {
       if (fill) flush();
-      if (in_record) G.o.length[(size_t)i * trials + (trial - first)] = step + 1;
-      if (trial >= 0 && trial < R.trial_cap) {
-        const size_t m = cobel_mon_offset(R.mon_stripes, R.trial_cap) + (size_t)trial;
-        if (R.lat_sum) atomicAdd(R.lat_sum + m, (unsigned long long)step);
-        if (R.lat_cnt) atomicAdd(R.lat_cnt + m, 1ull);
-        if (R.reward_sum) atomicAdd(R.reward_sum + m, trew);
-        if (R.resp_cnt && trew > 0.0) atomicAdd(R.resp_cnt + m, 1ull);
-        if (R.lat_trace) R.lat_trace[(size_t)i * R.trial_cap + trial] = step;
-      }
-      trial += 1;
-      iflags &= ~1u;
+      if (in_record) G.o.length[(size_t)i * trials + (X.trial - first)] = X.step + 1;
+      X.end_trial(R, i);
     } else {
-      step += 1;
+      X.step += 1;
     }
   }
 
-  inst[COBEL_I_STATE] = state;
-  inst[COBEL_I_STEP] = step;
-  inst[COBEL_I_TRIAL] = trial;
-  inst[COBEL_I_CTR_ENV] = (int32_t)ce;
-  inst[COBEL_I_CTR_POLICY] = (int32_t)cp;
-  inst[COBEL_I_FLAGS] = (int32_t)iflags;
-  *reinterpret_cast<double*>(inst + COBEL_I_REWARD_LO) = trew;
-  *reinterpret_cast<unsigned long long*>(inst + COBEL_I_STEPS_LO) += executed;
-  if (R.steps_done && executed) atomicAdd(R.steps_done, executed);
+  X.store(inst, R, false);   // (a rollout has no memory: those words are not written)
 }
 
 __global__ __launch_bounds__(256) void k_rollout_visits(const int16_t* __restrict__ states,
@@ -214,7 +173,6 @@ int rollout_plan(const cobel_world_t* world, const cobel_tab_rollout_t* o, int32
   const cobel_tab_run_t& r = o->run;
   COBEL_REQUIRE(o->start && o->states && o->actions && o->length, COBEL_E_ARG,
                 "%s: the record needs start, states, actions and length", who);
-  COBEL_REQUIRE(r.q && r.inst, COBEL_E_ARG, "%s: q and inst are required", who);
   COBEL_REQUIRE(!(r.flags & COBEL_F_LEARN), COBEL_E_ARG,
                 "%s: COBEL_F_LEARN is set: a rollout is a test session, it never writes Q", who);
   COBEL_REQUIRE(r.step_budget == 0, COBEL_E_ARG,
@@ -225,7 +183,6 @@ int rollout_plan(const cobel_world_t* world, const cobel_tab_rollout_t* o, int32
   COBEL_REQUIRE(r.steps_per_trial == o->steps, COBEL_E_ARG,
                 "%s: steps_per_trial = %d, the record keeps %d steps per trial", who,
                 r.steps_per_trial, o->steps);
-  COBEL_REQUIRE(r.n >= 0, COBEL_E_RANGE, "%s: n = %d", who, r.n);
   COBEL_REQUIRE(r.trials_target >= o->trials, COBEL_E_RANGE,
                 "%s: trials_target %d is below the session's %d trials", who, r.trials_target,
                 o->trials);
@@ -237,21 +194,15 @@ int rollout_plan(const cobel_world_t* world, const cobel_tab_rollout_t* o, int32
   COBEL_REQUIRE(((uintptr_t)r.q & (world->n_actions == 4 ? 15u : 3u)) == 0, COBEL_E_ARG,
                 "%s: q is misaligned: rows of %d float32 values must be %d-byte aligned", who,
                 world->n_actions, world->n_actions == 4 ? 16 : 4);
-  COBEL_REQUIRE(((uintptr_t)r.inst & 7u) == 0, COBEL_E_ARG, "%s: inst must be 8-byte aligned", who);
   COBEL_REQUIRE(((uintptr_t)o->states & 7u) == 0 && ((uintptr_t)o->actions & 3u) == 0 &&
                     ((uintptr_t)o->start & 1u) == 0 && ((uintptr_t)o->length & 3u) == 0,
                 COBEL_E_ARG, "%s: the record is misaligned (states 8, actions 4, start 2, length 4 "
                 "bytes)", who);
-  COBEL_REQUIRE(r.epsilon >= 0.0 && r.epsilon <= 1.0, COBEL_E_ARG, "%s: epsilon %g outside [0, 1]",
-                who, r.epsilon);
-  COBEL_REQUIRE(!(r.flags & COBEL_F_MASK_ACTIONS) || r.action_mask, COBEL_E_ARG,
-                "%s: mask_actions set without an action mask", who);
-  COBEL_REQUIRE(world->n_actions <= 8 || !(r.flags & COBEL_F_MASK_ACTIONS) ||
-                    ((uintptr_t)r.action_mask & 3u) == 0,
-                COBEL_E_ARG, "%s: the action masks of a %d-action world are 32-bit words, 4-byte "
-                "aligned", who, world->n_actions);
-  COBEL_REQUIRE(!r.param_index || (r.param_sets && r.n_param_sets > 0), COBEL_E_ARG,
-                "%s: param_index given without parameter sets", who);
+  // (a rollout reads neither the agent kind nor the model, the log or the batch of its run; q's
+  //  alignment was refused above in this entry point's own words, so of the shared q / inst clause
+  //  only the inst half can still fire)
+  if (int rc = cobel_tab_run_check(world, r, who, COBEL_CHECK_EPSILON | COBEL_CHECK_Q_ROWS16))
+    return rc;
   if (int rc = cobel_world_check(world, who)) return rc;
   if (r.n == 0) return COBEL_OK;
   cobel_tab_plan P{};
@@ -278,26 +229,15 @@ extern "C" int cobel_tab_rollout(const cobel_world_t* world, const cobel_tab_rol
   if (!plan[3]) return COBEL_OK;   // n == 0
   hipStream_t st = (hipStream_t)stream;
   rollout_args G;
-  G.rec = world->rec;
-  G.next_n = world->next_n;
-  G.reward_s = world->reward_s;
-  G.terminal_s = world->terminal_s;
-  G.starts = world->starts;
-  G.start_off = world->start_off;
-  G.succ_off = world->succ_off;
-  G.succ_state = world->succ_state;
-  G.succ_cdf = world->succ_cdf;
-  G.S = world->n_states;
-  G.n_worlds = world->n_worlds;
-  G.A = world->n_actions;
+  G.w = cobel_world_view_of(world);
   G.o = *rollout;
   const size_t entries = (size_t)rollout->run.n * (size_t)rollout->trials * (size_t)rollout->steps;
   COBEL_HIP_TRY(hipMemsetAsync(rollout->states, 0xff, entries * sizeof(int16_t), st));
   COBEL_HIP_TRY(hipMemsetAsync(rollout->actions, 0xff, entries, st));
   void (*kernel)(const rollout_args) = &k_tab_rollout<32>;
-  if (G.A == 4) kernel = &k_tab_rollout<4>;
-  else if (G.A <= 8) kernel = &k_tab_rollout<8>;
-  else if (G.A <= 16) kernel = &k_tab_rollout<16>;
+  if (G.w.A == 4) kernel = &k_tab_rollout<4>;
+  else if (G.w.A <= 8) kernel = &k_tab_rollout<8>;
+  else if (G.w.A <= 16) kernel = &k_tab_rollout<16>;
   COBEL_HIP_TRY(cobel_launch(kernel, dim3((unsigned)plan[3]), dim3((unsigned)plan[1]), 0, st, G));
   return COBEL_OK;
 }

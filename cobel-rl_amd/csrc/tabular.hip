@@ -28,6 +28,7 @@
 #include "cobel_common.h"
 #include "cobel_policy.h"
 #include "cobel_tab_batch.h"
+#include "cobel_tab_session.h"
 
 namespace {
 
@@ -1228,37 +1229,15 @@ static int tab_plan(const cobel_world_t* world, const cobel_tab_run_t* run, cobe
   COBEL_REQUIRE(world && run, COBEL_E_ARG, "cobel_tab_run: NULL world/run");
   if (int rc = cobel_world_check(world, "cobel_tab_run")) return rc;
   const cobel_tab_run_t& r = *run;
-  COBEL_REQUIRE(r.q && r.inst, COBEL_E_ARG, "cobel_tab_run: q and inst are required");
-  COBEL_REQUIRE(((uintptr_t)r.q & (world->n_actions == 4 ? 15u : 3u)) == 0 &&
-                    ((uintptr_t)r.inst & 7u) == 0, COBEL_E_ARG,
-                "cobel_tab_run: q must be 16-byte and inst 8-byte aligned");
-  // (model_index: the persistent-workgroup kernel reads the four 16-bit digests of a state as ONE
-  //  64-bit word; model and replay_log hold 64-bit records)
-  COBEL_REQUIRE(((uintptr_t)r.model & 7u) == 0 && ((uintptr_t)r.model_index & 7u) == 0 &&
-                    ((uintptr_t)r.replay_log & 7u) == 0, COBEL_E_ARG,
-                "cobel_tab_run: model, model_index and replay_log must be 8-byte aligned");
-  COBEL_REQUIRE(r.n >= 0, COBEL_E_RANGE, "cobel_tab_run: n = %d", r.n);
-  COBEL_REQUIRE(r.agent == COBEL_AGENT_Q || r.agent == COBEL_AGENT_DYNAQ, COBEL_E_ARG,
-                "cobel_tab_run: unknown agent %d", r.agent);
-  COBEL_REQUIRE(r.agent != COBEL_AGENT_DYNAQ || r.model, COBEL_E_ARG,
-                "cobel_tab_run: Dyna-Q needs the model table");
+  // (q: rows of four values are one 16-byte load; model_index: the persistent-workgroup kernel reads
+  //  the four 16-bit digests of a state as ONE 64-bit word)
+  if (int rc = cobel_tab_run_check(world, r, "cobel_tab_run",
+                                   COBEL_CHECK_EPSILON | COBEL_CHECK_Q_ROWS16 | COBEL_CHECK_TABLES |
+                                       COBEL_CHECK_DIGEST_WORD))
+    return rc;
   COBEL_REQUIRE(r.agent != COBEL_AGENT_DYNAQ || world->n_actions == 4, COBEL_E_UNSUPPORTED,
                 "cobel_tab_run: Dyna-Q model records are laid out for four-action worlds (this one "
                 "has %d); Q-learning takes any action count", world->n_actions);
-  COBEL_REQUIRE(r.batch >= 0, COBEL_E_RANGE, "cobel_tab_run: batch %d", r.batch);
-  COBEL_REQUIRE(r.steps_per_trial > 0, COBEL_E_RANGE, "cobel_tab_run: steps_per_trial = %d",
-                r.steps_per_trial);
-  COBEL_REQUIRE(r.epsilon >= 0.0 && r.epsilon <= 1.0, COBEL_E_ARG,
-                "cobel_tab_run: epsilon %g outside [0, 1]", r.epsilon);
-  COBEL_REQUIRE(!(r.flags & COBEL_F_MASK_ACTIONS) || r.action_mask, COBEL_E_ARG,
-                "cobel_tab_run: mask_actions set without an action mask");
-  COBEL_REQUIRE(world->n_actions <= 8 || !(r.flags & COBEL_F_MASK_ACTIONS) ||
-                    ((uintptr_t)r.action_mask & 3u) == 0,
-                COBEL_E_ARG, "cobel_tab_run: the action masks of a %d-action world are 32-bit words, "
-                "4-byte aligned", world->n_actions);
-  COBEL_REQUIRE(r.trial_cap >= 0 && r.log_cap >= 0, COBEL_E_RANGE, "cobel_tab_run: negative cap");
-  COBEL_REQUIRE(!r.param_index || (r.param_sets && r.n_param_sets > 0), COBEL_E_ARG,
-                "cobel_tab_run: param_index given without parameter sets");
   P.replay = (r.flags & COBEL_F_LEARN) && !(r.flags & COBEL_F_NO_REPLAY) && r.batch > 0 &&
              (r.agent == COBEL_AGENT_DYNAQ || r.replay_log != nullptr);
 

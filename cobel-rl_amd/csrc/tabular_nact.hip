@@ -45,6 +45,7 @@
 #include "cobel_common.h"
 #include "cobel_policy.h"
 #include "cobel_tab_batch.h"
+#include "cobel_tab_session.h"
 
 namespace {
 
@@ -531,27 +532,11 @@ bool cobel_tab_nact_plan(const cobel_world* world, const cobel_tab_run_t& r, cob
   int n_cu = 0;
   size_t lds_cu = 0;
   if (cobel_device_limits(world->device, &n_cu, &lds_cu) != COBEL_OK) return false;
-  // Instances per workgroup where they share the world's copy: the count (1, 2, 4 or 8) that puts the
-  // most wavefronts on a CU — up to four unless eight win (rows of 16 on 256 states: 17.5 KB per
-  // instance + 11 KB of world and masks, eight in ONE workgroup where two workgroups of four miss
-  // the 160 KiB by 2 KB and three of two make six)
-  int wpg = 1;
-  if (shared) {
-    size_t best = 0;
-    for (int w = 1; w <= 8; w <<= 1) {
-      const size_t need = nact_lds_bytes(S, A, w, shared, masked || r.param_index != nullptr);
-      if (need > lds_cu) break;
-      size_t waves = (lds_cu / need) * (size_t)w;
-      if (waves > 16) waves = 16;
-      if (waves > best || (waves == best && w <= 4)) {
-        best = waves;
-        wpg = w;
-      }
-    }
-  }
-  // (few instances: rather a workgroup on every CU than full workgroups on a few of them)
-  while (wpg > 1 && (r.n + wpg - 1) / wpg < n_cu) wpg >>= 1;
-  const size_t lds = nact_lds_bytes(S, A, wpg, shared, masked || r.param_index != nullptr);
+  const auto lds_of = [&](int w) {
+    return nact_lds_bytes(S, A, w, shared, masked || r.param_index != nullptr);
+  };
+  const int wpg = cobel_wave_plan(lds_cu, n_cu, r.n, shared, lds_of);
+  const size_t lds = lds_of(wpg);
   if (lds > lds_cu) return false;
   plan.kind = COBEL_TAB_KERNEL_WQN;
   plan.lds = lds;

@@ -45,6 +45,7 @@
 
 #include "cobel_common.h"
 #include "cobel_tab_batch.h"
+#include "cobel_tab_session.h"
 
 namespace {
 
@@ -448,33 +449,18 @@ int check_param(int policy, double v, const char* who) {
 int check_run(const cobel_world_t* world, const cobel_tab_policy_run_t* run, const char* who) {
   COBEL_REQUIRE(world && run, COBEL_E_ARG, "%s: NULL world/run", who);
   const cobel_tab_run_t& r = run->run;
-  COBEL_REQUIRE(r.q && r.inst, COBEL_E_ARG, "%s: q and inst are required", who);
-  COBEL_REQUIRE(((uintptr_t)r.q & 3u) == 0 && ((uintptr_t)r.inst & 7u) == 0, COBEL_E_ARG,
-                "%s: q must be 4-byte and inst 8-byte aligned", who);
-  COBEL_REQUIRE(((uintptr_t)r.model & 7u) == 0 && ((uintptr_t)r.replay_log & 7u) == 0 &&
-                    ((uintptr_t)r.model_index & 1u) == 0 && ((uintptr_t)run->policy_params & 7u) == 0,
-                COBEL_E_ARG, "%s: model, replay_log and policy_params must be 8-byte aligned", who);
+  // (the table is staged into LDS value by value, epsilon is no parameter of the run)
+  if (int rc = cobel_tab_run_check(world, r, who, COBEL_CHECK_TABLES)) return rc;
+  COBEL_REQUIRE(((uintptr_t)run->policy_params & 7u) == 0, COBEL_E_ARG,
+                "%s: policy_params must be 8-byte aligned", who);
   COBEL_REQUIRE(run->policy == COBEL_POLICY_SOFTMAX || run->policy == COBEL_POLICY_EXCLUSIVE ||
                     run->policy == COBEL_POLICY_RANDOM,
                 COBEL_E_ARG, "%s: unknown policy %d (COBEL_POLICY_SOFTMAX, _EXCLUSIVE, _RANDOM)", who,
                 run->policy);
-  COBEL_REQUIRE(r.agent == COBEL_AGENT_Q || r.agent == COBEL_AGENT_DYNAQ, COBEL_E_ARG,
-                "%s: unknown agent %d", who, r.agent);
-  COBEL_REQUIRE(r.agent != COBEL_AGENT_DYNAQ || r.model, COBEL_E_ARG,
-                "%s: Dyna-Q needs the model table", who);
   COBEL_REQUIRE(!run->policy_params || r.param_index, COBEL_E_ARG,
                 "%s: policy_params given without param_index", who);
-  COBEL_REQUIRE(!r.param_index || (r.param_sets && r.n_param_sets > 0), COBEL_E_ARG,
-                "%s: param_index given without parameter sets", who);
   if (!run->policy_params)
     if (int rc = check_param(run->policy, run->policy_param, who)) return rc;
-  COBEL_REQUIRE(!(r.flags & COBEL_F_MASK_ACTIONS) || r.action_mask, COBEL_E_ARG,
-                "%s: mask_actions set without an action mask", who);
-  COBEL_REQUIRE(r.n >= 0, COBEL_E_RANGE, "%s: n = %d", who, r.n);
-  COBEL_REQUIRE(r.batch >= 0, COBEL_E_RANGE, "%s: batch %d", who, r.batch);
-  COBEL_REQUIRE(r.steps_per_trial > 0, COBEL_E_RANGE, "%s: steps_per_trial = %d", who,
-                r.steps_per_trial);
-  COBEL_REQUIRE(r.trial_cap >= 0 && r.log_cap >= 0, COBEL_E_RANGE, "%s: negative cap", who);
   // what this kernel does not serve
   COBEL_REQUIRE(world->n_actions >= 1 && world->n_actions <= kW, COBEL_E_UNSUPPORTED,
                 "%s: %d actions (a %s run serves 1 to %d)", who, world->n_actions,
@@ -502,39 +488,46 @@ int check_run(const cobel_world_t* world, const cobel_tab_policy_run_t* run, con
 }
 
 // Instances per workgroup (1, 2, 4 or 8; they share the world's copy where there is one world) and the
-// LDS they take, chosen as cobel_tab_nact_plan chooses them.
+// LDS they take (cobel_wave_plan).
 int plan_run(const cobel_world_t* world, const cobel_tab_run_t& r, int& wpg, size_t& lds, const char* who) {
   const int S = world->n_states;
   const bool shared = world->n_worlds == 1;
   int n_cu = 0;
   size_t lds_cu = 0;
   if (int rc = cobel_device_limits(world->device, &n_cu, &lds_cu)) return rc;
-  wpg = 1;
-  if (shared) {
-    size_t best = 0;
-    for (int w = 1; w <= 8; w <<= 1) {
-      const size_t need = pol_lds_bytes(S, w, shared);
-      if (need > lds_cu) break;
-      size_t waves = (lds_cu / need) * (size_t)w;
-      if (waves > 16) waves = 16;
-      if (waves > best || (waves == best && w <= 4)) {
-        best = waves;
-        wpg = w;
-      }
-    }
-  }
-  while (wpg > 1 && (r.n + wpg - 1) / wpg < n_cu) wpg >>= 1;
+  wpg = cobel_wave_plan(lds_cu, n_cu, r.n, shared,
+                        [&](int w) { return pol_lds_bytes(S, w, shared); });
   lds = pol_lds_bytes(S, wpg, shared);
   COBEL_REQUIRE(lds <= lds_cu, COBEL_E_UNSUPPORTED, "%s: %zu bytes of LDS per instance, %zu per CU",
                 who, lds, lds_cu);
   return COBEL_OK;
 }
 
+// What has to be read back to be checked.
 template <typename T>
 int fetch(std::vector<T>& host, const T* dev, size_t count, hipStream_t st) {
   host.resize(count);
   COBEL_HIP_TRY(hipMemcpyAsync(host.data(), dev, count * sizeof(T), hipMemcpyDeviceToHost, st));
   COBEL_HIP_TRY(hipStreamSynchronize(st));
+  return COBEL_OK;
+}
+// no row of `count` action masks may mask all A actions (`row`: what a row is to the caller)
+int check_masks(const uint8_t* mask, int count, int A, const char* row, hipStream_t st,
+                const char* who) {
+  std::vector<uint8_t> rows;
+  if (int rc = fetch(rows, mask, (size_t)count, st)) return rc;
+  const uint32_t all = (1u << A) - 1u;
+  for (int k = 0; k < count; ++k)
+    COBEL_REQUIRE((rows[k] & all) != 0u, COBEL_E_ARG, "%s: the action mask masks all actions of "
+                  "%s %d", who, row, k);
+  return COBEL_OK;
+}
+// every policy parameter of the `count` at `param` is in the policy's range
+int check_params(int policy, const double* param, int count, hipStream_t st, const char* who) {
+  std::vector<double> vals;
+  if (int rc = fetch(vals, param, (size_t)count, st)) return rc;
+  for (double v : vals)
+    if (int rc = check_param(policy, v, who)) return rc;
   return COBEL_OK;
 }
 
@@ -570,21 +563,11 @@ extern "C" int cobel_tab_policy_run(const cobel_world_t* world, const cobel_tab_
   const cobel_tab_run_t& r = run->run;
   if (r.n == 0) return COBEL_OK;
   hipStream_t st = (hipStream_t)stream;
-  // what has to be read back to be checked: the masks and the per-set policy parameters
-  if (run->policy != COBEL_POLICY_RANDOM && (r.flags & COBEL_F_MASK_ACTIONS)) {
-    std::vector<uint8_t> rows;
-    if (int rc = fetch(rows, r.action_mask, (size_t)world->n_states, st)) return rc;
-    const uint32_t all = (1u << world->n_actions) - 1u;
-    for (int s = 0; s < world->n_states; ++s)
-      COBEL_REQUIRE((rows[s] & all) != 0u, COBEL_E_ARG, "%s: the action mask masks all actions of "
-                    "state %d", who, s);
-  }
-  if (run->policy_params) {
-    std::vector<double> vals;
-    if (int rc = fetch(vals, run->policy_params, (size_t)r.n_param_sets, st)) return rc;
-    for (double v : vals)
-      if (int rc = check_param(run->policy, v, who)) return rc;
-  }
+  if (run->policy != COBEL_POLICY_RANDOM && (r.flags & COBEL_F_MASK_ACTIONS))
+    if (int rc = check_masks(r.action_mask, world->n_states, world->n_actions, "state", st, who))
+      return rc;
+  if (run->policy_params)
+    if (int rc = check_params(run->policy, run->policy_params, r.n_param_sets, st, who)) return rc;
   int wpg = 1;
   size_t lds = 0;
   if (int rc = plan_run(world, r, wpg, lds, who)) return rc;
@@ -635,18 +618,9 @@ extern "C" int cobel_policy_select_n(int32_t policy, const double* v, const uint
                 COBEL_E_ARG, "%s: misaligned argument", who);
   hipStream_t st = (hipStream_t)stream;
   if (!random) {
-    std::vector<double> vals;
-    if (int rc = fetch(vals, param, (size_t)n_param, st)) return rc;
-    for (double x : vals)
-      if (int rc = check_param(policy, x, who)) return rc;
-    if (mask_bits) {
-      std::vector<uint8_t> rows;
-      if (int rc = fetch(rows, mask_bits, (size_t)n, st)) return rc;
-      const uint32_t all = (1u << A) - 1u;
-      for (int i = 0; i < n; ++i)
-        COBEL_REQUIRE((rows[i] & all) != 0u, COBEL_E_ARG, "%s: the action mask masks all actions of "
-                      "row %d", who, i);
-    }
+    if (int rc = check_params(policy, param, n_param, st, who)) return rc;
+    if (mask_bits)
+      if (int rc = check_masks(mask_bits, n, A, "row", st, who)) return rc;
   }
   const long long lanes = (long long)n * kW;
   const dim3 grid((unsigned)((lanes + 255) / 256));
