@@ -319,7 +319,19 @@ PMA_MAX_STATES, PMA_MAX_ACTIONS = 128, 8
 PMA_WIDE_MAX_STATES = 1024
 PMA_MAX_SEQ = 256
 (PMA_EQUAL_NEED, PMA_EQUAL_GAIN, PMA_IGNORE_BARRIERS, PMA_ALLOW_LOOPS, PMA_GAIN_ORIGINAL,
- PMA_SHARED_POLICY, PMA_WIDE) = (1 << k for k in range(7))
+ PMA_SHARED_POLICY, PMA_WIDE, PMA_SETS) = (1 << k for k in range(8))
+
+
+PMA_Q_MEMORY, PMA_Q_AGENT = 0, 1
+# the ten doubles of a cobel_pma_param_set_t: the memory's seven, then the agent's three
+PMA_SET_MEMORY = ('learning_rate', 'learning_rate_q', 'learning_rate_T', 'gamma', 'gamma_q',
+                  'min_gain', 'epsilon')
+PMA_SET_AGENT = ('alpha', 'agent_gamma', 'agent_epsilon')
+
+
+class PMAParamSet(C.Structure):
+    """``cobel_pma_param_set_t`` (80 bytes; fill with ``cobel_pma_param_set_fill``)."""
+    _fields_ = [(name, C.c_double) for name in PMA_SET_MEMORY + PMA_SET_AGENT]
 
 
 class PMAMem(C.Structure):
@@ -338,6 +350,16 @@ class PMAMem(C.Structure):
         ('learning_rate_T', C.c_double), ('gamma', C.c_double), ('gamma_q', C.c_double),
         ('min_gain', C.c_double), ('epsilon', C.c_double),
         ('seed', C.c_uint64),
+    ]
+
+
+class PMAMemSets(C.Structure):
+    """``cobel_pma_mem_sets_t``: a ``cobel_pma_mem_t`` with the parameter sets behind it.  Hand
+    ``byref(x.mem)`` to the entry points; they read the tail under ``PMA_SETS`` in ``mem.flags``."""
+    _fields_ = [
+        ('mem', PMAMem),
+        ('param_sets', C.c_void_p), ('param_index', C.c_void_p), ('n_param_sets', C.c_int32),
+        ('reserved_', C.c_int32),
     ]
 
 
@@ -645,6 +667,10 @@ _SIGNATURES = {
     'cobel_sfma_replay': (C.c_int, [C.POINTER(SFMAMem), C.c_int32, C.c_int32, _P, _P, _P, _P, _P,
                                     _P]),
     'cobel_sfma_random_batch': (C.c_int, [C.POINTER(SFMAMem), C.c_int32, _P, _P, _P]),
+    'cobel_pma_param_set_fill': (C.c_int, [C.POINTER(C.c_double * 7), C.c_double, C.c_double,
+                                           C.c_double, C.POINTER(PMAParamSet)]),
+    'cobel_pma_update_q_sets': (C.c_int, [C.POINTER(PMAMem), _P, _P, _P, C.c_int32, C.c_int64,
+                                          C.c_int32, _P, _P]),
     'cobel_pma_plan': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32 * 4)]),
     'cobel_pma_plan_wide': (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32 * 4)]),
     'cobel_pma_replay': (C.c_int, [C.POINTER(PMAMem), C.c_int32, _P, _P, _P, _P, _P]),

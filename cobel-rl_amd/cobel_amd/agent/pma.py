@@ -20,6 +20,11 @@ values.  A wide memory built with a ``need_workspace`` takes ``cobel_pma_station
 place (the elimination on a workspace in device memory), with the same effect.  Host callbacks fire at these boundaries: ``on_replay_end`` of the start
 replay after the trial's kernel, step callbacks not at all.  The head and the tail of a session
 are ``FusedAgent._session_begin`` / ``_session_end``; the loop between them is this agent's.
+
+``learning_rate``, ``gamma`` and the acting policy's ``epsilon`` take a scalar or one entry per
+instance, as the memory's parameters do (memory/pma.py): a sweep rides on the instance axis, the
+trial stays four device calls.  The memory's ``_fill_params`` builds the parameter sets for the
+launcher and for ``update_q``; ``batch_size`` is launch-wide.
 """
 from __future__ import annotations
 
@@ -30,6 +35,8 @@ import torch
 
 from .. import _lib
 from ..spaces import Discrete
+from ..memory import _device
+from ..memory.pma import launch_wide
 from .agent import Callbacks, FusedAgent
 
 
@@ -84,7 +91,9 @@ class PMA(FusedAgent):
     @Q.setter
     def Q(self, value) -> None:
         if self._q is None:
-            self._q_host = np.array(value, dtype=np.float64).reshape(self.n_states, self.n_actions)
+            v = np.array(value, dtype=np.float64)
+            shape = (self.n_states, self.n_actions)
+            self._q_host = v.reshape(shape if v.size == shape[0] * shape[1] else (-1,) + shape)
         else:
             v = value if torch.is_tensor(value) else torch.as_tensor(
                 np.asarray(value, dtype=np.float64))
@@ -106,12 +115,19 @@ class PMA(FusedAgent):
         with the agent's learning rate and ``gamma ** k``, the same bits as the host loop below,
         which serves the agent that has not run yet."""
         if self._q is not None:
-            pows = torch.as_tensor(np.array([self.gamma ** k for k in range(len(update) + 1)],
-                                            dtype=np.float64), device=self.device)
-            self.M._update_q_device(self._q, update, self.learning_rate, pows)
+            self.M._update_q_device(self._q, update,
+                                    (self.learning_rate, self.gamma, self.policy.epsilon))
             return
         q = np.array(self.Q.cpu().numpy() if torch.is_tensor(self.Q) else self.Q)
-        for Q in q.reshape(-1, self.n_states, self.n_actions):
+        q = q.reshape(-1, self.n_states, self.n_actions)
+        # (one entry per instance in learning_rate or gamma: every instance its own table)
+        n = max(len(q), np.size(self.learning_rate), np.size(self.gamma))
+        assert all(np.ndim(v) == 0 or np.shape(v) == (n,) for v in (self.learning_rate, self.gamma)) \
+            and len(q) in (1, n), _device.PER_INSTANCE_SHAPE
+        q = np.array(np.broadcast_to(q, (n,) + q.shape[1:]))
+        rates = np.broadcast_to(np.asarray(self.learning_rate), (n,)).tolist()
+        gammas = np.broadcast_to(np.asarray(self.gamma), (n,)).tolist()
+        for Q, learning_rate, gamma in zip(q, rates, gammas):
             future_value = np.amax(Q[update[-1]['next_state']]) * update[-1]['terminal']
             for s, step in enumerate(update):
                 r, ok = 0.0, True
@@ -119,28 +135,31 @@ class PMA(FusedAgent):
                     if update[s + k]['terminal'] == 0 and s != len(update) - 1:
                         ok = False
                         break
-                    r += update[s + k]['reward'] * (self.gamma ** k)
+                    r += update[s + k]['reward'] * (gamma ** k)
                 if not ok:
                     break
-                td = r + future_value * (self.gamma ** (k + 1))
+                td = r + future_value * (gamma ** (k + 1))
                 td -= Q[step['state']][step['action']]
-                Q[step['state']][step['action']] += self.learning_rate * td
-        self.Q = q.reshape(-1, self.n_states, self.n_actions) if self.n_envs not in (None, 1) else \
-            q.reshape(self.n_states, self.n_actions)
+                Q[step['state']][step['action']] += learning_rate * td
+        self.Q = q if len(q) > 1 else q.reshape(self.n_states, self.n_actions)
 
     # -- launch ---------------------------------------------------------------------------------
     def _launch(self, interface, pol, flags, trials_target, steps, budget, batch) -> None:
         M = self.M
         shared = M.policy is pol
-        mem = M._mem(self._q, self._mask_dev, batch)
+        mem = M._mem(self._q, self._mask_dev, batch,
+                     agent=(self.learning_rate, self.gamma, pol.epsilon))
         run = _lib.PMARun()     # (the mask, the instance count and the seed travel in `mem`)
         self._fill_run(run, interface, flags, trials_target, steps, budget)
         run.last = _lib.ptr(self._last)
         run.replay_out = _lib.ptr(self._start_records)
         run.batch = batch
         run.flags = flags | ((_lib.PMA_SHARED_POLICY << 16) if shared else 0)
-        run.alpha, run.gamma_pow1 = self.learning_rate, self.gamma ** 1
-        run.epsilon = float(pol.epsilon)
+        if M._held is None:
+            run.alpha, run.gamma_pow1 = self.learning_rate, self.gamma ** 1
+            run.epsilon = float(pol.epsilon)
+        else:      # (ignored by a launch with sets: set 0's values as placeholders)
+            run.alpha, run.gamma_pow1, run.epsilon = (float(v) for v in M._held['first'][7:10])
         _lib.check(_lib.lib().cobel_pma_trial(interface.handle.ptr, C.byref(mem), C.byref(run),
                                               _lib.current_stream(self.device)))
 
@@ -201,7 +220,8 @@ class PMA(FusedAgent):
 
     def train(self, interface, trials: int, steps: int, batch_size: int = 32,
               no_replay: bool = False) -> None:
-        self._run(interface, trials, steps, int(batch_size), True, bool(no_replay))
+        self._run(interface, trials, steps, launch_wide(batch_size, 'PMA', 'batch_size'), True,
+                  bool(no_replay))
 
     def test(self, interface, trials: int, steps: int) -> None:
         self._run(interface, trials, steps, 0, False, True)

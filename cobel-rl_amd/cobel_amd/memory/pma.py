@@ -61,6 +61,20 @@ Draws: the memory's generator is stream ``STREAM_PMA_MEMORY`` of (seed, instance
 the extension actions come from the memory's own policy object — stream ``STREAM_PMA_POLICY`` at
 ``policy.counter`` unless that object also acts for an agent.
 
+Per-instance parameter sets.  ``learning_rate``, ``learning_rate_q``, ``learning_rate_T``, ``gamma``,
+``gamma_q``, ``min_gain`` and the policy's ``epsilon`` take a scalar or one entry per instance (any
+other shape is the ``AssertionError`` of ``_device.PER_INSTANCE_SHAPE``): a parameter sweep rides
+on the instance axis of one launch (``optimizer.grid_search.spread_over_instances``).  With an
+array in any of them ``_fill_params`` turns the distinct rows into ``cobel_pma_param_set_t``
+records, gives every instance the index of its row and holds the power tables per set; every
+method that reads a parameter honours them (``store``, ``replay``, ``update_sr``,
+``compute_gain_batch``, ``compute_gain``, ``update_q``; ``action_probs_batch`` then takes
+[N, rows, A]).  The switches (``equal_need``, ``equal_gain``, ``ignore_barriers``, ``allow_loops``,
+``min_gain_mode``, ``wide``, ``need_workspace``, ``offline_need``) and the replay length are
+launch-wide: an array there is a ``NotImplementedError`` naming the attribute.  As in the
+reference the constructor's ``gamma`` gives the initial ``SR`` — an array one host inverse per
+distinct value, [N, S, S] — and a later assignment to ``gamma`` only reaches ``update_sr()``.
+
 Two forms.  The default serves worlds of up to 128 states.  ``PMAMemory(..., wide=True)`` selects the
 wide form of the kernels: up to 1 024 states and whatever fits 160 KiB of LDS (32 x 32 with four
 actions does, with eight it does not), ``update_sr`` by the blocked kernels on the SR in device
@@ -76,6 +90,7 @@ import torch
 
 from .. import _lib
 from . import _device
+from .sfma import refuse_arrays
 
 RECORD = np.dtype([('state', '<i4'), ('action', '<i4'), ('next_state', '<i4'),
                    ('terminal', '<i4'), ('reward', '<f8')])
@@ -83,6 +98,26 @@ RECORD = np.dtype([('state', '<i4'), ('action', '<i4'), ('next_state', '<i4'),
 _TABLES = {'rewards': (torch.float64, np.float64), 'states': (torch.int32, np.int64),
            'terminals': (torch.int32, np.int64), 'T': (torch.float64, np.float64),
            'SR': (torch.float64, np.float64), 'update_mask': (torch.uint8, bool)}
+
+
+# the attributes that take a scalar or one entry per instance, in the order of the memory's seven
+# doubles of a cobel_pma_param_set_t (_lib.PMA_SET_MEMORY); the seventh is the policy's epsilon
+SET_ATTRIBUTES = ('learning_rate', 'learning_rate_q', 'learning_rate_T', 'gamma', 'gamma_q',
+                  'min_gain')
+# launch-wide: they change the code path (the switches) or the shape of the launch
+LAUNCH_WIDE = ('equal_need', 'equal_gain', 'ignore_barriers', 'allow_loops', 'min_gain_mode', 'wide',
+               'need_workspace', 'offline_need')
+# the agent part of a set where the memory is called on its own: PMA's defaults, no exploration
+AGENT_DEFAULTS = (0.9, 0.99, 0.0)
+POW_ROWS = 34      # the least length of a power table: a replay of the default batch and one more
+
+
+def launch_wide(value, owner: str, name: str):
+    """A length (batch, replay length) serves the whole launch: an array is refused by name."""
+    if np.ndim(value) > 0:
+        raise NotImplementedError('%s.%s is launch-wide: one value for all instances, not an array'
+                                  % (owner, name))
+    return int(value)
 
 
 def _table(name: str):
@@ -95,9 +130,10 @@ def _table(name: str):
         return a[0] if a.shape[0] == 1 else a
 
     def put(self, value) -> None:
-        shape = self._host[name].shape
+        shape = self._shapes[name]
         if self._dev is None:
-            self._host[name] = np.array(value, dtype=ndt).reshape(shape)
+            v = np.array(value, dtype=ndt)
+            self._host[name] = v.reshape(shape if v.size == int(np.prod(shape)) else (-1,) + shape)
             return
         t = self._dev[name]
         v = np.asarray(value.cpu().numpy() if torch.is_tensor(value) else value)
@@ -112,8 +148,8 @@ class PMAMemory(_device.DeviceMemory):
                  gamma: float = 0.9, gamma_q: float = 0.9, rng=None, wide: bool = False,
                  need_workspace: int = 0) -> None:
         self.rng = rng
-        self.wide = bool(wide)
-        self.need_workspace = int(need_workspace)
+        self.wide = bool(launch_wide(wide, 'PMAMemory', 'wide'))
+        self.need_workspace = launch_wide(need_workspace, 'PMAMemory', 'need_workspace')
         if self.need_workspace < 0 or (self.need_workspace and not self.wide):
             raise ValueError(
                 'PMAMemory: need_workspace = %d — the number of instances whose elimination '
@@ -148,14 +184,31 @@ class PMAMemory(_device.DeviceMemory):
         self._host = {
             'rewards': np.zeros((S, A)), 'states': states,
             'terminals': np.zeros((S, A)).astype(int), 'T': np.array(T, dtype=np.float64),
-            'SR': np.linalg.inv(np.eye(T.shape[0]) - self.gamma * T),
+            'SR': self._initial_sr(T, self.gamma),
             'update_mask': states.flatten(order='F') != np.tile(np.arange(S), A),
         }
+        self._shapes = {'rewards': (S, A), 'states': (S, A), 'terminals': (S, A), 'T': (S, S),
+                        'SR': (S, S), 'update_mask': (A * S,)}
+        self._psets, self._held, self._tail = {}, None, None
         self._dev = None
         self._need_work = None
         self.counter = None
         self.seed, self.instance_base = 0, 0
         self._pows = None
+
+    @staticmethod
+    def _initial_sr(T, gamma):
+        """memory/pma.py:141 — ``inv(I - gamma T)`` by NumPy on the host from the constructor's
+        gamma: [S, S], or for an array of gammas one inverse per distinct value, [N, S, S] (one
+        entry: [S, S], as every table of one instance)."""
+        eye = np.eye(T.shape[0])
+        if np.ndim(gamma) == 0:
+            return np.linalg.inv(eye - gamma * T)
+        g = np.asarray(gamma, dtype=np.float64)
+        assert g.ndim == 1, _device.PER_INSTANCE_SHAPE
+        inverse = {v: np.linalg.inv(eye - v * T) for v in sorted(set(g.tolist()))}
+        sr = np.array([inverse[v] for v in g.tolist()])
+        return sr[0] if len(sr) == 1 else sr
 
     @staticmethod
     def _check_wide(S: int, A: int) -> None:
@@ -183,6 +236,7 @@ class PMAMemory(_device.DeviceMemory):
 
     @offline_need.setter
     def offline_need(self, value) -> None:
+        launch_wide(0 if np.ndim(value) == 0 else value, 'PMAMemory', 'offline_need')
         if value not in ('host', 'device'):
             raise ValueError("offline_need is 'host' or 'device', not %r" % (value,))
         if value == 'device' and self.wide and not self.need_workspace:
@@ -200,6 +254,7 @@ class PMAMemory(_device.DeviceMemory):
         if self._dev is not None:
             assert self.n_envs == n_envs, 'a memory stays bound to the instance count it first saw'
             return
+        refuse_arrays(self, LAUNCH_WIDE)
         held = min(self.need_workspace, n_envs)
         work = held * self._need_work_bytes() if held else 0
         if self.wide and torch.device(device).type == 'cuda':
@@ -214,7 +269,11 @@ class PMAMemory(_device.DeviceMemory):
         for name, (tdt, _) in _TABLES.items():
             h = np.ascontiguousarray(self._host[name])
             t = torch.as_tensor(h, device=device).to(tdt)
-            dev[name] = t.unsqueeze(0).expand((n_envs,) + tuple(t.shape)).contiguous()
+            if h.ndim == len(self._shapes[name]):
+                t = t.unsqueeze(0)
+            else:       # (a table with an instance axis already: the SR of an array of gammas)
+                assert h.shape[0] == n_envs, _device.PER_INSTANCE_SHAPE
+            dev[name] = t.expand((n_envs,) + self._shapes[name]).contiguous()
         self._dev = dev
         self._need_work = torch.empty(work, dtype=torch.uint8, device=device) if work else None
         self.n_envs = n_envs
@@ -237,11 +296,65 @@ class PMAMemory(_device.DeviceMemory):
         :315, :485, :491): constants, not arithmetic on the data path."""
         key = (float(self.gamma), float(self.gamma_q))
         if self._pows is None or self._pows[0] != key or self._pows[1].shape[1] <= length:
-            n = max(length + 1, 34)
+            n = max(length + 1, POW_ROWS)
             tab = np.array([[self.gamma ** k for k in range(n)],
                             [self.gamma_q ** k for k in range(n)]], dtype=np.float64)
             self._pows = (key, torch.as_tensor(tab, device=self.device))
         return self._pows[1]
+
+    def _fill_params(self, x, length: int = 0, agent=None):
+        """The seven doubles and the two power tables of the ``cobel_pma_mem_t`` at the head of
+        ``x`` (a ``cobel_pma_mem_sets_t``) and the sets in its tail — and, for the
+        agent's launcher and ``PMA.update_q``, ``agent = (learning rate, gamma, epsilon)`` — as
+        scalars, or, if any of them has one entry per instance, as parameter sets: the distinct
+        rows become ``cobel_pma_param_set_t`` records (cached by the bytes of the columns), every
+        instance gets the index of its row, the power tables hold one row per set (regrown when
+        ``length`` exceeds them) and the scalar fields hold set 0's values as placeholders.
+        Returns None for a scalar launch, else what is held: ``first`` (set 0's ten values) and
+        the tables ``gamma_pow``, ``gamma_q_pow`` and ``agent_pow`` (the agent's ``gamma ** k``),
+        [sets, pow_len] each."""
+        refuse_arrays(self, LAUNCH_WIDE)
+        m = x.mem
+        vals = tuple(getattr(self, a) for a in SET_ATTRIBUTES) + (self.policy.epsilon,)
+        cols = _device.param_columns(vals + (tuple(agent) if agent is not None else ()), self.n_envs)
+        if cols is None:
+            for name, v in zip(_lib.PMA_SET_MEMORY, vals):
+                setattr(m, name, float(v))
+            pows = self._power_tables(length)
+            m.gamma_pow, m.gamma_q_pow = pows[0].data_ptr(), pows[1].data_ptr()
+            m.pow_len = pows.shape[1]
+            return None
+        if agent is None:          # the memory's own calls: the agent part at its defaults
+            cols = np.concatenate([cols, np.broadcast_to(AGENT_DEFAULTS, (self.n_envs, 3))], axis=1)
+        who = 'agent' if agent is not None else 'memory'
+        held = self._psets.setdefault(who, dict(key=None, sets=None, index=None, n=0, first=None,
+                                                rows=None, gamma_pow=None, gamma_q_pow=None,
+                                                agent_pow=None))
+
+        def fill(rows):
+            sets = (_lib.PMAParamSet * len(rows))()
+            for k, row in enumerate(rows):
+                _lib.check(_lib.lib().cobel_pma_param_set_fill(
+                    C.byref((C.c_double * 7)(*row[:7])), float(row[7]), float(row[8]),
+                    float(row[9]), C.byref(sets[k])))
+            held['rows'], held['gamma_pow'] = np.array(rows), None
+            return sets
+        new = _device.param_sets(np.ascontiguousarray(cols), held['key'], fill, self.device)
+        if new is not None:
+            held['key'], held['sets'], held['index'], held['n'], held['first'] = new
+        if held['gamma_pow'] is None or held['gamma_pow'].shape[1] <= length:
+            n = max(length + 1, POW_ROWS)     # (Python's **, as _power_tables: constants)
+            for name, c in (('gamma_pow', 3), ('gamma_q_pow', 4), ('agent_pow', 8)):
+                tab = np.array([[float(row[c]) ** k for k in range(n)] for row in held['rows']],
+                               dtype=np.float64)
+                held[name] = torch.as_tensor(tab, device=self.device)
+        for name, v in zip(_lib.PMA_SET_MEMORY, held['first']):     # placeholders: set 0's values
+            setattr(m, name, float(v))
+        m.gamma_pow, m.gamma_q_pow = _lib.ptr(held['gamma_pow']), _lib.ptr(held['gamma_q_pow'])
+        m.pow_len = held['gamma_pow'].shape[1]
+        x.param_sets, x.param_index = _lib.ptr(held['sets']), _lib.ptr(held['index'])
+        x.n_param_sets = held['n']
+        return held
 
     def flags(self) -> int:
         return ((_lib.PMA_EQUAL_NEED if self.equal_need else 0) |
@@ -251,24 +364,25 @@ class PMAMemory(_device.DeviceMemory):
                 (_lib.PMA_GAIN_ORIGINAL if self.min_gain_mode == 'original' else 0) |
                 (_lib.PMA_WIDE if self.wide else 0))
 
-    def _mem(self, q=None, mask_bits=None, length: int = 0):
+    def _mem(self, q=None, mask_bits=None, length: int = 0, agent=None):
+        """The ``cobel_pma_mem_t`` of a call (``_fill_params`` says what ``agent`` is).  It is the
+        head of a ``cobel_pma_mem_sets_t``, which stays in ``self._tail``; with parameter sets its
+        flags carry ``PMA_SETS`` and the entry points read the sets behind it.  What
+        ``_fill_params`` returned stays in ``self._held`` for the caller."""
         assert self._is_bound, _device.NOT_BOUND
         d = self._dev
-        m = _lib.PMAMem()
+        self._tail = x = _lib.PMAMemSets()
+        m = x.mem               # (a view: it shares x's memory and keeps x alive)
         m.q = _lib.ptr(q)
         m.rewards, m.states, m.terminals = (_lib.ptr(d['rewards']), _lib.ptr(d['states']),
                                             _lib.ptr(d['terminals']))
         m.T, m.SR, m.update_mask = _lib.ptr(d['T']), _lib.ptr(d['SR']), _lib.ptr(d['update_mask'])
         m.action_mask = _lib.ptr(mask_bits)
         m.mem_ctr, m.pol_ctr = _lib.ptr(self.counter), _lib.ptr(self._policy_counter())
-        pows = self._power_tables(length)
-        m.gamma_pow, m.gamma_q_pow = pows[0].data_ptr(), pows[1].data_ptr()
-        m.pow_len = pows.shape[1]
+        self._held = self._fill_params(x, length, agent)
         m.n, m.n_states, m.n_actions = self.n_envs, self.nb_states, self.nb_actions
-        m.instance_base, m.flags, m.pol_stream = self.instance_base, self.flags(), self.policy.stream
-        m.learning_rate, m.learning_rate_q = self.learning_rate, self.learning_rate_q
-        m.learning_rate_T, m.gamma, m.gamma_q = self.learning_rate_T, self.gamma, self.gamma_q
-        m.min_gain, m.epsilon = self.min_gain, float(self.policy.epsilon)
+        m.instance_base, m.pol_stream = self.instance_base, self.policy.stream
+        m.flags = self.flags() | (_lib.PMA_SETS if self._held is not None else 0)
         m.seed = self.seed
         return m
 
@@ -386,6 +500,7 @@ class PMAMemory(_device.DeviceMemory):
         ``cobel_pma_stationary`` without leaving the device."""
         assert self._is_bound, _device.NOT_BOUND
         n, S, A = self.n_envs, self.nb_states, self.nb_actions
+        length = launch_wide(replay_length, 'PMAMemory', 'replay_length')
         if torch.is_tensor(q_function):
             q = q_function.to(device=self.device, dtype=torch.float64)
         else:
@@ -401,7 +516,6 @@ class PMAMemory(_device.DeviceMemory):
                 rows = self._need_device(states)
         else:
             rows = self._need_rows(states)
-        length = int(replay_length)
         records = self._replay_device(q, self._mask_bits(action_mask), length, states, rows, ff)
         ups = self.experiences(records, length)
         if n == 1:
@@ -495,7 +609,30 @@ class PMAMemory(_device.DeviceMemory):
         """memory/pma.py:423-450 on the device (``cobel_pma_action_probs``): the policy's
         epsilon-greedy probabilities of every row of a [rows, A] table, each row divided by its
         sum; ``action_mask`` is [rows, A] booleans or None.  NumPy in gives NumPy out, a tensor in
-        a tensor out.  Needs no bound memory."""
+        a tensor out.  Needs no bound memory.  With one epsilon per instance ``q_function`` is
+        [N, rows, A] and the call is made once per distinct epsilon on the rows of its instances."""
+        if np.ndim(self.policy.epsilon) > 0:
+            return self._action_probs_per_instance(q_function, action_mask)
+        return self._action_probs(q_function, action_mask, float(self.policy.epsilon))
+
+    def _action_probs_per_instance(self, q_function, action_mask):
+        eps = np.asarray(self.policy.epsilon, dtype=np.float64)
+        is_tensor = torch.is_tensor(q_function)
+        q = q_function if is_tensor else np.asarray(q_function, dtype=np.float64)
+        assert eps.ndim == 1 and q.ndim == 3 and q.shape[0] == eps.shape[0], \
+            _device.PER_INSTANCE_SHAPE
+        out = torch.empty_like(q, dtype=torch.float64) if is_tensor else np.empty(q.shape)
+        for e in np.unique(eps):
+            sel = np.flatnonzero(eps == e)
+            idx = torch.as_tensor(sel, device=q.device) if is_tensor else sel
+            part = self._action_probs(q[idx].reshape(-1, q.shape[2]),
+                                      None if action_mask is None else
+                                      np.tile(np.asarray(action_mask.cpu() if torch.is_tensor(
+                                          action_mask) else action_mask), (len(sel), 1)), float(e))
+            out[idx] = part.reshape((len(sel),) + tuple(q.shape[1:]))
+        return out
+
+    def _action_probs(self, q_function, action_mask, epsilon: float):
         is_tensor = torch.is_tensor(q_function)
         if is_tensor and q_function.is_cuda:
             dev = q_function.device
@@ -515,19 +652,33 @@ class PMAMemory(_device.DeviceMemory):
             bits = torch.as_tensor(_device.mask_bits(mask, rows, A), device=dev)
         probs = torch.empty((rows, A), dtype=torch.float64, device=dev)
         _lib.check(_lib.lib().cobel_pma_action_probs(
-            _lib.ptr(q), _lib.ptr(bits), rows, A, float(self.policy.epsilon), _lib.ptr(probs),
+            _lib.ptr(q), _lib.ptr(bits), rows, A, epsilon, _lib.ptr(probs),
             _lib.current_stream(dev)))
         return probs if is_tensor else probs.cpu().numpy()
 
-    def _update_q_device(self, q, update: list, learning_rate: float, pow_table) -> None:
-        """``cobel_pma_update_q`` IN PLACE on the device tensor ``q`` [N, S, A] with the caller's
-        learning rate and power table (a float64 device tensor, entry k = discount ** k)."""
+    def _update_q_device(self, q, update: list, agent=None) -> None:
+        """The n-step update IN PLACE on the device tensor ``q`` [N, S, A]: the memory's
+        (``learning_rate_q``, ``gamma_q ** k``) or, with ``agent = (learning rate, gamma,
+        epsilon)``, the agent's (its learning rate, ``gamma ** k``).  ``cobel_pma_update_q`` for
+        scalars, ``cobel_pma_update_q_sets`` where a parameter has one entry per instance."""
         steps, lengths, max_len, per = self._sequences([update], 'update_q')
-        m = self._mem()
+        m = self._mem(length=len(update), agent=agent)
+        stride, stream = max_len if per else 0, _lib.current_stream(self.device)
+        if self._held is not None:
+            which = _lib.PMA_Q_MEMORY if agent is None else _lib.PMA_Q_AGENT
+            _lib.check(_lib.lib().cobel_pma_update_q_sets(
+                C.byref(m), _lib.ptr(q), _lib.ptr(steps), _lib.ptr(lengths), max_len, stride, which,
+                _lib.ptr(self._held['agent_pow']), stream))
+            return
+        if agent is None:
+            rate, table = self.learning_rate_q, self._power_tables(len(update))[1]
+        else:
+            rate = agent[0]
+            table = torch.as_tensor(np.array([agent[1] ** k for k in range(len(update) + 1)],
+                                             dtype=np.float64), device=self.device)
         _lib.check(_lib.lib().cobel_pma_update_q(
-            C.byref(m), _lib.ptr(q), _lib.ptr(steps), _lib.ptr(lengths), max_len,
-            max_len if per else 0, float(learning_rate), pow_table.data_ptr(),
-            int(pow_table.numel()), _lib.current_stream(self.device)))
+            C.byref(m), _lib.ptr(q), _lib.ptr(steps), _lib.ptr(lengths), max_len, stride,
+            float(rate), table.data_ptr(), int(table.numel()), stream))
 
     def update_q(self, q_function, update: list):
         """memory/pma.py:452-496 on the device (``cobel_pma_update_q``): the n-step update of
@@ -541,17 +692,16 @@ class PMAMemory(_device.DeviceMemory):
         if shape != (n, S, A) and not (n == 1 and shape == (S, A)):
             raise ValueError('update_q: q_function of shape %s — [%d, %d, %d]%s is expected'
                              % (shape, n, S, A, ' or [%d, %d]' % (S, A) if n == 1 else ''))
-        pows = self._power_tables(len(update))[1]
         if torch.is_tensor(q_function):
             if (q_function.dtype != torch.float64 or q_function.device != self.device
                     or not q_function.is_contiguous()):
                 raise ValueError('update_q: a tensor is updated in place — a contiguous float64 '
                                  'tensor on %s is expected' % (self.device,))
-            self._update_q_device(q_function, update, self.learning_rate_q, pows)
+            self._update_q_device(q_function, update)
             return q_function
         q = torch.as_tensor(np.asarray(q_function, dtype=np.float64), device=self.device)
         q = q.reshape((n, S, A)).contiguous()
-        self._update_q_device(q, update, self.learning_rate_q, pows)
+        self._update_q_device(q, update)
         if isinstance(q_function, np.ndarray):
             q_function[...] = q.cpu().numpy().reshape(shape)
             return q_function

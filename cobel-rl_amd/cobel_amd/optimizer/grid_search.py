@@ -32,7 +32,10 @@ def spread_over_instances(combinations: list[dict], nb_runs: int) -> tuple[dict,
     arrays go straight into an agent's ``learning_rate`` / ``gamma`` or a policy's ``epsilon`` /
     ``Softmax.beta`` — and into an ``SFMAMemory``: ``decay_inhibition``, ``decay_strength``, ``learning_rate``,
     ``beta``, ``C_step``, ``I_step``, ``R_threshold``, ``reward_modulation``, ``blend``,
-    ``interpolation_fwd`` / ``_rev`` and ``mode`` (an array of mode names)."""
+    ``interpolation_fwd`` / ``_rev`` and ``mode`` (an array of mode names); into a ``PMAMemory``:
+    ``learning_rate``, ``learning_rate_q``, ``learning_rate_T``, ``gamma`` (given to the constructor
+    it also sets each instance's initial SR), ``gamma_q`` and ``min_gain``; and into the ``PMA``
+    agent's ``learning_rate`` / ``gamma`` and the ``epsilon`` of its policies."""
     which = np.repeat(np.arange(len(combinations)), nb_runs)
     keys = list(combinations[0]) if combinations else []
     return {k: np.array([combinations[c][k] for c in which]) for k in keys}, which

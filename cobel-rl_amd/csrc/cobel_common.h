@@ -136,7 +136,33 @@ int cobel_dqn_replay_lds_launch(const cobel_dqn_replay_t& r, hipStream_t st,
                                 unsigned long long* trace /* experiments, or NULL */);
 // pma_sr.hip: PMAMemory.update_sr by the blocked kernels on the SR blocks in global memory (any S;
 // cobel_pma_update_sr, pma.hip, dispatches), and the LDS of their largest workgroup
-int cobel_pma_sr_blocked(const cobel_pma_mem_t& m, hipStream_t st);
+// cobel_pma_mem_t as the PMA kernels take it: with the parameter sets of a cobel_pma_mem_sets_t
+// behind it (the caller's tail under COBEL_PMA_SETS, zeros otherwise)
+struct cobel_pma_mem_x : cobel_pma_mem_t {
+  const cobel_pma_param_set_t* param_sets;
+  const uint16_t* param_index;
+  int32_t n_param_sets, reserved2_;
+};
+inline cobel_pma_mem_x cobel_pma_expand(const cobel_pma_mem_t* mem) {
+  cobel_pma_mem_x x;
+  static_cast<cobel_pma_mem_t&>(x) = *mem;
+  x.param_sets = nullptr;
+  x.param_index = nullptr;
+  x.n_param_sets = x.reserved2_ = 0;
+  if (mem->flags & COBEL_PMA_SETS) {
+    const cobel_pma_mem_sets_t* const t = reinterpret_cast<const cobel_pma_mem_sets_t*>(mem);
+    x.param_sets = t->param_sets;
+    x.param_index = t->param_index;
+    x.n_param_sets = t->n_param_sets;
+  }
+  return x;
+}
+// the head of an entry point that was handed `mem_in`: the NULL refusal, then `mem`, the expanded copy
+#define COBEL_PMA_MEM(who)                                         \
+  COBEL_REQUIRE(mem_in, COBEL_E_ARG, "%s: NULL mem", who);          \
+  const cobel_pma_mem_x mem_x_ = cobel_pma_expand(mem_in);         \
+  const cobel_pma_mem_x* const mem = &mem_x_
+int cobel_pma_sr_blocked(const cobel_pma_mem_x& m, hipStream_t st);
 size_t cobel_pma_sr_blocked_lds();
 int cobel_world_check(const cobel_world* w, const char* who);   // non-NULL, on the current device
 int cobel_world_check4(const cobel_world* w, const char* who);  // ... and a four-action world

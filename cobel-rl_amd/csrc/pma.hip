@@ -16,6 +16,9 @@
 //   update     the n-step update_q: targets by lane, applied in sequence order
 // k_pma_update_sr: one workgroup of 256 lanes per instance, I - gamma T in LDS, in-place
 // Gauss-Jordan without pivoting (up to 128 states; beyond: pma_sr.hip).
+// Per-instance parameter sets (cobel_pma_mem_sets_t.param_index): every kernel here is a template over
+// SETS.  The form with sets stages the instance's parameters from its set at the top of its body
+// (fill_hyper / pma_load_par, cobel_pma.h); the scalar launch takes the form without that code.
 // The replay and trial kernels come in two forms, narrow (the default, up to 128 states) and wide
 // (COBEL_PMA_WIDE, up to 1 024 states): see pma_narrow / pma_wide below.
 //
@@ -83,7 +86,7 @@ __host__ __device__ inline size_t pma_lds_carve(unsigned char* base, int S, int 
 }
 
 struct pma_args {
-  cobel_pma_mem_t m;
+  cobel_pma_mem_x m;
   int32_t L;
   const int32_t* current_state;
   const double* need;
@@ -92,7 +95,7 @@ struct pma_args {
 };
 
 struct pma_trial_args {
-  cobel_pma_mem_t m;
+  cobel_pma_mem_x m;
   cobel_pma_run_t r;
   // the world (general.hip: gen_args)
   const cobel_wrec* rec;
@@ -125,7 +128,8 @@ struct pma_hyper {
   int S, A, SA;
   uint32_t flags, g, pol_stream;
   uint64_t seed;
-  double lrq, gq, mg, eps;
+  double lrq, gq, mg, eps;   // the memory's, of this instance (pma_load_par)
+  double lr, lrT;            // ... what the store takes
   const double *gpow, *gqpow;
 };
 
@@ -317,7 +321,10 @@ __device__ __forceinline__ void pma_replay_body(const pma_lds<F>& l, const pma_h
   }
 }
 
-__device__ __forceinline__ void fill_hyper(const cobel_pma_mem_t& m, int i, pma_hyper* h) {
+// SETS: the form a launch with a param_index takes.  The scalar launch keeps forms without a line
+// of the staging from a set — its kernels are the ones they were.
+template <bool SETS>
+__device__ __forceinline__ void fill_hyper(const cobel_pma_mem_x& m, int i, pma_hyper* h) {
   h->S = m.n_states;
   h->A = m.n_actions;
   h->SA = m.n_states * m.n_actions;
@@ -325,18 +332,23 @@ __device__ __forceinline__ void fill_hyper(const cobel_pma_mem_t& m, int i, pma_
   h->g = m.instance_base + (uint32_t)i;
   h->pol_stream = m.pol_stream;
   h->seed = m.seed;
-  h->lrq = m.learning_rate_q;
-  h->gq = m.gamma_q;
-  h->mg = m.min_gain;
-  h->eps = m.epsilon;
-  h->gpow = m.gamma_pow;
-  h->gqpow = m.gamma_q_pow;
+  // the launch's scalars or the instance's parameter set: here, outside every loop
+  pma_par p;
+  pma_load_par<SETS>(m, i, &p);
+  h->lrq = p.lrq;
+  h->gq = p.gq;
+  h->mg = p.mg;
+  h->eps = p.eps;
+  h->lr = p.lr;
+  h->lrT = p.lrT;
+  h->gpow = p.gpow;
+  h->gqpow = p.gqpow;
 }
 
 // the instance's tables into LDS (states and terminals clamped to what the layout holds: a table
 // edited by hand must not send a row read outside the instance's slice)
 template <class F>
-__device__ __forceinline__ void load_tables(const cobel_pma_mem_t& m, int i, const pma_lds<F>& l,
+__device__ __forceinline__ void load_tables(const cobel_pma_mem_x& m, int i, const pma_lds<F>& l,
                                             const pma_hyper& h, int lane) {
   const size_t off = (size_t)i * h.SA;
   for (int c = lane; c < h.SA; c += 64) {
@@ -365,14 +377,14 @@ __device__ __forceinline__ void store_records(const pma_lds<F>& l, cobel_pma_rec
   }
 }
 
-template <class F>
+template <class F, bool SETS>
 __global__ __launch_bounds__(64) void k_pma_replay(const pma_args P) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   const int lane = (int)threadIdx.x;
   const int i = (int)blockIdx.x;
-  const cobel_pma_mem_t& m = P.m;
+  const cobel_pma_mem_x& m = P.m;
   pma_hyper h;
-  fill_hyper(m, i, &h);
+  fill_hyper<SETS>(m, i, &h);
   pma_lds<F> l;
   pma_lds_carve(lds_raw, h.S, h.A, P.L, &l);
   load_tables(m, i, l, h, lane);
@@ -397,15 +409,15 @@ __global__ __launch_bounds__(64) void k_pma_replay(const pma_args P) {
   }
 }
 
-template <class F>
+template <class F, bool SETS>
 __global__ __launch_bounds__(64) void k_pma_trial(const pma_trial_args G) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   const int lane = (int)threadIdx.x;
   const int i = (int)blockIdx.x;
-  const cobel_pma_mem_t& m = G.m;
+  const cobel_pma_mem_x& m = G.m;
   const cobel_pma_run_t& R = G.r;
   pma_hyper h;
-  fill_hyper(m, i, &h);
+  fill_hyper<SETS>(m, i, &h);
   const int S = h.S, A = h.A;
   const uint32_t flags = R.flags;
   const bool learn = flags & COBEL_F_LEARN;
@@ -415,6 +427,17 @@ __global__ __launch_bounds__(64) void k_pma_trial(const pma_trial_args G) {
   const uint32_t act_stream =
       (flags & COBEL_F_TEST_STREAM) ? COBEL_STREAM_POLICY_TEST : COBEL_STREAM_POLICY;
   if (shared) h.pol_stream = act_stream;
+  // the agent's three values: the run's, or those of the instance's set
+  double alpha = R.alpha, gpow1 = R.gamma_pow1, act_eps = R.epsilon;
+  if constexpr (SETS) {
+    int row;
+    const pma_set_ptr ps = pma_set_of(m, i, &row);
+    if (ps) {
+      alpha = pma_uniform(ps->alpha);
+      gpow1 = pma_uniform(ps->agent_gamma);
+      act_eps = pma_uniform(ps->agent_epsilon);
+    }
+  }
   pma_lds<F> l;
   pma_lds_carve(lds_raw, S, A, L, &l);
   load_tables(m, i, l, h, lane);
@@ -457,7 +480,7 @@ __global__ __launch_bounds__(64) void k_pma_trial(const pma_trial_args G) {
     const double u = cobel_draw_u01(cp, 0u, h.g, act_stream, h.seed);
     cp += 1u;
     const int a = cobel_eps_greedy_select_n<double, kMaxA>(q, A, mask_of(l, h, masked, state), u,
-                                                           R.epsilon, nullptr);
+                                                           act_eps, nullptr);
     int ns;
     if (G.succ_off) {
       const double ue = cobel_draw_u01(ce, COBEL_SUB_DOUBLE, h.g, COBEL_STREAM_ENV, h.seed);
@@ -477,13 +500,13 @@ __global__ __launch_bounds__(64) void k_pma_trial(const pma_trial_args G) {
       const double fv = max_row(l.Q, ns, A) * (double)nt;
       double rs = 0.0;
       rs += r * 1.0;
-      double td = rs + fv * R.gamma_pow1;
+      double td = rs + fv * gpow1;
       const double qv = l.Q[c];
       td -= qv;
-      const double nq = qv + R.alpha * td;
+      const double nq = qv + alpha * td;
       // PMAMemory.store (memory/pma.py:158-166)
       const double rv = l.R[c];
-      const double nr = rv + m.learning_rate * (r - rv);
+      const double nr = rv + h.lr * (r - rv);
       wsync();
       if (lane == 0) {
         l.Q[c] = nq;
@@ -497,7 +520,7 @@ __global__ __launch_bounds__(64) void k_pma_trial(const pma_trial_args G) {
       double* const Trow = m.T + ((size_t)i * S + state) * S;
       for (int j = lane; j < S; j += 64) {
         const double t = Trow[j];
-        Trow[j] = t + m.learning_rate_T * ((j == ns ? 1.0 : 0.0) - t);
+        Trow[j] = t + h.lrT * ((j == ns ? 1.0 : 0.0) - t);
       }
       wsync();
     }
@@ -538,26 +561,29 @@ __global__ __launch_bounds__(64) void k_pma_trial(const pma_trial_args G) {
 }
 
 // PMAMemory.store, one wavefront per instance: lane 0 the record, the lanes the row of T
-__global__ __launch_bounds__(64) void k_pma_store(const cobel_pma_mem_t m,
+template <bool SETS>
+__global__ __launch_bounds__(64) void k_pma_store(const cobel_pma_mem_x m,
                                                   const cobel_pma_exp_t* __restrict__ exps) {
   const int lane = (int)threadIdx.x;
   const int i = (int)blockIdx.x;
   const cobel_pma_exp_t e = exps[i];
   const int S = m.n_states, A = m.n_actions;
+  pma_par p;
+  pma_load_par<SETS>(m, i, &p);
   if (e.state < 0 || e.state >= S || e.action < 0 || e.action >= A || e.next_state < 0 ||
       e.next_state >= S)
     return;
   if (lane == 0) {
     const size_t c = (size_t)i * S * A + (size_t)e.state * A + e.action;
     const double rv = m.rewards[c];
-    m.rewards[c] = rv + m.learning_rate * (e.reward - rv);
+    m.rewards[c] = rv + p.lr * (e.reward - rv);
     m.states[c] = e.next_state;
     m.terminals[c] = e.terminal;
   }
   double* const Trow = m.T + ((size_t)i * S + e.state) * S;
   for (int j = lane; j < S; j += 64) {
     const double t = Trow[j];
-    Trow[j] = t + m.learning_rate_T * ((j == e.next_state ? 1.0 : 0.0) - t);
+    Trow[j] = t + p.lrT * ((j == e.next_state ? 1.0 : 0.0) - t);
   }
 }
 
@@ -565,7 +591,8 @@ __global__ __launch_bounds__(64) void k_pma_store(const cobel_pma_mem_t m,
 // by 1 / pivot (the pivot's own place takes 1 / pivot), every other row i loses f = M[i][k] times
 // it (its column k takes -f / pivot).  No pivoting: the matrix is strictly diagonally dominant by
 // rows, and elimination keeps it so.
-__global__ __launch_bounds__(kSrThreads) void k_pma_update_sr(const cobel_pma_mem_t m) {
+template <bool SETS>
+__global__ __launch_bounds__(kSrThreads) void k_pma_update_sr(const cobel_pma_mem_x m) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   const int S = m.n_states;
   double* const M = reinterpret_cast<double*>(lds_raw);
@@ -573,9 +600,11 @@ __global__ __launch_bounds__(kSrThreads) void k_pma_update_sr(const cobel_pma_me
   double* const row = col + S;
   const int i = (int)blockIdx.x, t = (int)threadIdx.x;
   const double* const T = m.T + (size_t)i * S * S;
+  pma_par p;
+  pma_load_par<SETS>(m, i, &p);
   for (int e = t; e < S * S; e += kSrThreads) {
     const int r = e / S, c = e - r * S;
-    M[e] = (r == c ? 1.0 : 0.0) - m.gamma * T[e];
+    M[e] = (r == c ? 1.0 : 0.0) - p.gamma * T[e];
   }
   __syncthreads();
   for (int k = 0; k < S; ++k) {
@@ -599,7 +628,7 @@ __global__ __launch_bounds__(kSrThreads) void k_pma_update_sr(const cobel_pma_me
 
 size_t sr_lds_bytes(int S) { return 8 * ((size_t)S * S + 2 * (size_t)S); }
 
-bool is_wide(const cobel_pma_mem_t& m) { return (m.flags & COBEL_PMA_WIDE) != 0; }
+bool is_wide(const cobel_pma_mem_x& m) { return (m.flags & COBEL_PMA_WIDE) != 0; }
 size_t carve_bytes(bool wide, int S, int A, int L) {
   return wide ? pma_lds_carve<pma_wide>(nullptr, S, A, L, nullptr)
               : pma_lds_carve<pma_narrow>(nullptr, S, A, L, nullptr);
@@ -612,9 +641,9 @@ bool sr_blocked(int S) {
   return v && !strcmp(v, "blocked");
 }
 
-int check_mem(const cobel_pma_mem_t* mem, const char* who, bool replay) {
+int check_mem(const cobel_pma_mem_x* mem, const char* who, bool replay) {
   COBEL_REQUIRE(mem, COBEL_E_ARG, "%s: NULL mem", who);
-  const cobel_pma_mem_t& m = *mem;
+  const cobel_pma_mem_x& m = *mem;
   if (is_wide(m))
     COBEL_REQUIRE(m.n_states >= 1 && m.n_states <= pma_wide::kMaxS && m.n_actions >= 1 &&
                       m.n_actions <= kMaxA,
@@ -640,13 +669,14 @@ int check_mem(const cobel_pma_mem_t* mem, const char* who, bool replay) {
     COBEL_REQUIRE(m.q && m.update_mask && m.mem_ctr && m.pol_ctr && m.gamma_pow && m.gamma_q_pow,
                   COBEL_E_ARG,
                   "%s: q, update_mask, mem_ctr, pol_ctr and the two power tables are required", who);
-    COBEL_REQUIRE(m.epsilon >= 0.0 && m.epsilon <= 1.0, COBEL_E_ARG, "%s: epsilon %g outside [0, 1]",
-                  who, m.epsilon);
+    // (with an index the scalars are ignored; a set's epsilon is checked where the set is filled)
+    COBEL_REQUIRE(m.param_index || (m.epsilon >= 0.0 && m.epsilon <= 1.0), COBEL_E_ARG,
+                  "%s: epsilon %g outside [0, 1]", who, m.epsilon);
   }
-  return COBEL_OK;
+  return pma_check_sets(m, who);
 }
 
-int replay_lds(const cobel_pma_mem_t& m, int L, const char* who, size_t* lds) {
+int replay_lds(const cobel_pma_mem_x& m, int L, const char* who, size_t* lds) {
   COBEL_REQUIRE(L >= 0, COBEL_E_RANGE, "%s: replay_length = %d", who, L);
   const bool wide = is_wide(m);
   const int limit = wide ? pma_wide::kLdsLimit : pma_narrow::kLdsLimit;
@@ -707,10 +737,11 @@ extern "C" int cobel_pma_plan_wide(int32_t n_states, int32_t n_actions, int32_t 
   return COBEL_OK;
 }
 
-extern "C" int cobel_pma_replay(const cobel_pma_mem_t* mem, int32_t replay_length,
+extern "C" int cobel_pma_replay(const cobel_pma_mem_t* mem_in, int32_t replay_length,
                                 const int32_t* current_state, const double* need,
                                 const int32_t* force_first, cobel_pma_rec_t* records,
                                 void* stream) {
+  COBEL_PMA_MEM("cobel_pma_replay");
   if (int rc = check_mem(mem, "cobel_pma_replay", true)) return rc;
   size_t lds = 0;
   if (int rc = replay_lds(*mem, replay_length, "cobel_pma_replay", &lds)) return rc;
@@ -728,14 +759,18 @@ extern "C" int cobel_pma_replay(const cobel_pma_mem_t* mem, int32_t replay_lengt
   P.need = need;
   P.force_first = force_first;
   P.records = records;
-  COBEL_HIP_TRY(cobel_launch(is_wide(*mem) ? k_pma_replay<pma_wide> : k_pma_replay<pma_narrow>,
-                             dim3((unsigned)mem->n), dim3(64), lds, (hipStream_t)stream, P));
+  const bool sets = mem->param_index != nullptr;
+  COBEL_HIP_TRY(cobel_launch(
+      is_wide(*mem) ? (sets ? k_pma_replay<pma_wide, true> : k_pma_replay<pma_wide, false>)
+                    : (sets ? k_pma_replay<pma_narrow, true> : k_pma_replay<pma_narrow, false>),
+      dim3((unsigned)mem->n), dim3(64), lds, (hipStream_t)stream, P));
   return COBEL_OK;
 }
 
-extern "C" int cobel_pma_trial(const cobel_world_t* world, const cobel_pma_mem_t* mem,
+extern "C" int cobel_pma_trial(const cobel_world_t* world, const cobel_pma_mem_t* mem_in,
                                const cobel_pma_run_t* run, void* stream) {
   if (int rc = cobel_world_check(world, "cobel_pma_trial")) return rc;
+  COBEL_PMA_MEM("cobel_pma_trial");
   if (int rc = check_mem(mem, "cobel_pma_trial", true)) return rc;
   COBEL_REQUIRE(run && run->inst, COBEL_E_ARG, "cobel_pma_trial: run and run->inst are required");
   COBEL_REQUIRE(world->n_states == mem->n_states && world->n_actions == mem->n_actions,
@@ -763,29 +798,61 @@ extern "C" int cobel_pma_trial(const cobel_world_t* world, const cobel_pma_mem_t
   G.succ_state = world->succ_state;
   G.succ_cdf = world->succ_cdf;
   G.n_worlds = world->n_worlds;
-  COBEL_HIP_TRY(cobel_launch(is_wide(*mem) ? k_pma_trial<pma_wide> : k_pma_trial<pma_narrow>,
-                             dim3((unsigned)mem->n), dim3(64), lds, (hipStream_t)stream, G));
+  const bool sets = mem->param_index != nullptr;
+  COBEL_HIP_TRY(cobel_launch(
+      is_wide(*mem) ? (sets ? k_pma_trial<pma_wide, true> : k_pma_trial<pma_wide, false>)
+                    : (sets ? k_pma_trial<pma_narrow, true> : k_pma_trial<pma_narrow, false>),
+      dim3((unsigned)mem->n), dim3(64), lds, (hipStream_t)stream, G));
   return COBEL_OK;
 }
 
 // (the store kernel reads 32-bit states from the experience and writes 32-bit tables: one form)
-extern "C" int cobel_pma_store(const cobel_pma_mem_t* mem, const cobel_pma_exp_t* experiences,
+extern "C" int cobel_pma_store(const cobel_pma_mem_t* mem_in, const cobel_pma_exp_t* experiences,
                                void* stream) {
+  COBEL_PMA_MEM("cobel_pma_store");
   if (int rc = check_mem(mem, "cobel_pma_store", false)) return rc;
   COBEL_REQUIRE(experiences && ((uintptr_t)experiences & 7u) == 0, COBEL_E_ARG,
                 "cobel_pma_store: experiences must be given, 8-byte aligned");
   if (mem->n == 0) return COBEL_OK;
-  hipLaunchKernelGGL(k_pma_store, dim3((unsigned)mem->n), dim3(64), 0, (hipStream_t)stream, *mem,
-                     experiences);
+  hipLaunchKernelGGL(mem->param_index ? k_pma_store<true> : k_pma_store<false>,
+                     dim3((unsigned)mem->n), dim3(64), 0, (hipStream_t)stream, *mem, experiences);
   COBEL_HIP_TRY(hipGetLastError());
   return COBEL_OK;
 }
 
-extern "C" int cobel_pma_update_sr(const cobel_pma_mem_t* mem, void* stream) {
+extern "C" int cobel_pma_update_sr(const cobel_pma_mem_t* mem_in, void* stream) {
+  COBEL_PMA_MEM("cobel_pma_update_sr");
   if (int rc = check_mem(mem, "cobel_pma_update_sr", false)) return rc;
   if (mem->n == 0) return COBEL_OK;
   if (sr_blocked(mem->n_states)) return cobel_pma_sr_blocked(*mem, (hipStream_t)stream);
-  COBEL_HIP_TRY(cobel_launch(k_pma_update_sr, dim3((unsigned)mem->n), dim3(kSrThreads),
+  COBEL_HIP_TRY(cobel_launch(mem->param_index ? k_pma_update_sr<true> : k_pma_update_sr<false>,
+                             dim3((unsigned)mem->n), dim3(kSrThreads),
                              sr_lds_bytes(mem->n_states), (hipStream_t)stream, *mem));
+  return COBEL_OK;
+}
+
+extern "C" int cobel_pma_param_set_fill(const double memory[7], double alpha, double agent_gamma,
+                                        double agent_epsilon, cobel_pma_param_set_t* out) {
+  const char* const who = "cobel_pma_param_set_fill";
+  COBEL_REQUIRE(out && memory, COBEL_E_ARG, "%s: NULL memory / out", who);
+  static_assert(sizeof(cobel_pma_param_set_t) == 80 && sizeof(cobel_pma_param_set_t) % 16 == 0,
+                "cobel_pma_param_set_t layout");
+  COBEL_REQUIRE(memory[6] >= 0.0 && memory[6] <= 1.0, COBEL_E_ARG,
+                "%s: the memory's epsilon %g outside [0, 1]", who, memory[6]);
+  COBEL_REQUIRE(agent_epsilon >= 0.0 && agent_epsilon <= 1.0, COBEL_E_ARG,
+                "%s: the acting policy's epsilon %g outside [0, 1]", who, agent_epsilon);
+  // (update_sr eliminates without pivoting: see k_pma_update_sr)
+  COBEL_REQUIRE(memory[3] >= 0.0 && memory[3] < 1.0, COBEL_E_ARG,
+                "%s: the memory's gamma %g outside [0, 1)", who, memory[3]);
+  out->learning_rate = memory[0];
+  out->learning_rate_q = memory[1];
+  out->learning_rate_T = memory[2];
+  out->gamma = memory[3];
+  out->gamma_q = memory[4];
+  out->min_gain = memory[5];
+  out->epsilon = memory[6];
+  out->alpha = alpha;
+  out->agent_gamma = agent_gamma;
+  out->agent_epsilon = agent_epsilon;
   return COBEL_OK;
 }

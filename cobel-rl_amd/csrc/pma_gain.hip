@@ -17,6 +17,10 @@
 //   k_pma_action_probs  one thread per row
 //   k_pma_update_q      one thread per instance: the bootstrap value first, then the steps in
 //                       order, so a repeated (s, a) sees the earlier step's write
+// With cobel_pma_mem_sets_t.param_index the gain kernels stage the instance's parameters (pma_load_par,
+// cobel_pma.h) at the top of their loop over instances, and cobel_pma_update_q_sets runs
+// k_pma_update_q's second form, which takes the learning rate and the row of powers of each
+// instance's set.
 //
 // Reference behaviour restated (paths relative to the reference's src/cobel):
 //   memory/pma.py:269-331 (compute_gain), :333-386 (compute_gain_batch), :423-450
@@ -34,14 +38,14 @@ constexpr int kThreads = 256;
 constexpr unsigned kMaxGridY = 65535u;
 
 struct gain_args {
-  cobel_pma_mem_t m;
+  cobel_pma_mem_x m;
   const double* q;
   int64_t q_stride;
   double* gain;
 };
 
 struct seq_args {
-  cobel_pma_mem_t m;
+  cobel_pma_mem_x m;
   const double* q;
   int64_t q_stride;
   const cobel_pma_rec_t* steps;
@@ -59,14 +63,21 @@ struct upd_args {
   int64_t inst_stride;
   double learning_rate;
   int32_t n, n_states, n_actions, max_len;
+  // the form with sets: pow_table is [n_sets][pow_len], `agent` says which learning rate
+  const cobel_pma_param_set_t* sets;
+  const uint16_t* index;
+  int32_t n_sets, pow_len, agent;
 };
 
 // (an index from a table or a record edited by hand must not send a row read outside the table)
 __device__ __forceinline__ int clamp_to(int v, int n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
 
-// memory/pma.py:333-386
+// memory/pma.py:333-386.  SETS: the form a launch with a param_index takes; the scalar launch keeps
+// the form without a line of it (here the staging costs five vector registers, and with them a
+// wave per SIMD).
+template <bool SETS>
 __global__ __launch_bounds__(kThreads) void k_pma_gain_batch(const gain_args P) {
-  const cobel_pma_mem_t& m = P.m;
+  const cobel_pma_mem_x& m = P.m;
   const int S = m.n_states, A = m.n_actions, SA = S * A;
   const int idx = (int)blockIdx.x * kThreads + (int)threadIdx.x;
   if (idx >= SA) return;
@@ -76,30 +87,35 @@ __global__ __launch_bounds__(kThreads) void k_pma_gain_batch(const gain_args P) 
   for (int i = (int)blockIdx.y; i < m.n; i += (int)gridDim.y) {
     const double* const Q = P.q + (size_t)i * (size_t)P.q_stride;
     const size_t off = (size_t)i * SA;
+    pma_par p;
+    pma_load_par<SETS>(m, i, &p);
     double q[kMaxA], qn[kMaxA];
     load_row(Q, s, A, q);
     const double mx = max_row(Q, clamp_to(m.states[off + c], S), A);
     const double qa = Q[c];
-    const double inner = (m.rewards[off + c] + (m.gamma_q * mx) * (double)m.terminals[off + c]) - qa;
-    const double qna = qa + m.learning_rate_q * inner;
+    const double inner = (m.rewards[off + c] + (p.gq * mx) * (double)m.terminals[off + c]) - qa;
+    const double qna = qa + p.lrq * inner;
 #pragma unroll
     for (int b = 0; b < kMaxA; ++b) qn[b] = b == a ? qna : q[b];
-    double gain = policy_gain(q, qn, A, mask, m.epsilon, true);
-    gain = gain < m.min_gain ? m.min_gain : gain;
+    double gain = policy_gain(q, qn, A, mask, p.eps, true);
+    gain = gain < p.mg ? p.mg : gain;
     P.gain[off + idx] = gain;
   }
 }
 
 // memory/pma.py:269-331, one update of the list per wavefront
+template <bool SETS>
 __global__ __launch_bounds__(64) void k_pma_gain_seq(const seq_args P) {
   __shared__ double sg[kMaxSeq], rr[kMaxSeq];
-  const cobel_pma_mem_t& m = P.m;
+  const cobel_pma_mem_x& m = P.m;
   const int S = m.n_states, A = m.n_actions;
   const int lane = (int)threadIdx.x;
   const int k = (int)blockIdx.x;
   const bool original = m.flags & COBEL_PMA_GAIN_ORIGINAL;
   for (int i = (int)blockIdx.y; i < m.n; i += (int)gridDim.y) {
     const double* const Q = P.q + (size_t)i * (size_t)P.q_stride;
+    pma_par p;
+    pma_load_par<SETS>(m, i, &p);
     const cobel_pma_rec_t* const st =
         P.steps + (size_t)i * (size_t)P.inst_stride + (size_t)k * P.max_len;
     int n = P.lengths[(P.inst_stride ? (size_t)i * P.n_seq : 0) + k];
@@ -110,21 +126,21 @@ __global__ __launch_bounds__(64) void k_pma_gain_seq(const seq_args P) {
     for (int j = lane; j < n; j += 64) {
       const int s = clamp_to(st[j].state, S), a = clamp_to(st[j].action, A);
       double r = 0.0;
-      for (int kk = 0; kk < n - j; ++kk) r += rr[j + kk] * m.gamma_pow[kk];
-      const double tgt = r + fv * m.gamma_q_pow[n - j];
+      for (int kk = 0; kk < n - j; ++kk) r += rr[j + kk] * p.gpow[kk];
+      const double tgt = r + fv * p.gqpow[n - j];
       double q[kMaxA], qn[kMaxA];
       load_row(Q, s, A, q);
 #pragma unroll
-      for (int b = 0; b < kMaxA; ++b) qn[b] = q[b] + m.learning_rate_q * ((b == a ? tgt : q[b]) - q[b]);
+      for (int b = 0; b < kMaxA; ++b) qn[b] = q[b] + p.lrq * ((b == a ? tgt : q[b]) - q[b]);
       const uint32_t mask = m.action_mask ? (uint32_t)m.action_mask[s] : 0xffu;
-      double sgn = policy_gain(q, qn, A, mask, m.epsilon, false);
-      if (original) sgn = m.min_gain > sgn ? m.min_gain : sgn;
+      double sgn = policy_gain(q, qn, A, mask, p.eps, false);
+      if (original) sgn = p.mg > sgn ? p.mg : sgn;
       sg[j] = sgn;
     }
     wsync();
     double gain = 0.0;
     for (int j = 0; j < n; ++j) gain += sg[j];
-    gain = m.min_gain > gain ? m.min_gain : gain;
+    gain = p.mg > gain ? p.mg : gain;
     if (lane == 0) P.gain[(size_t)i * P.n_seq + k] = gain;
     wsync();
   }
@@ -152,10 +168,21 @@ __global__ __launch_bounds__(kThreads) void k_pma_action_probs(const double* __r
 }
 
 // memory/pma.py:452-496 and agent/pma.py:319-353, which differ in the learning rate and the powers
+// SETS: the learning rate and the row of powers of the instance's parameter set
+template <bool SETS>
 __global__ __launch_bounds__(64) void k_pma_update_q(const upd_args P) {
   const int i = (int)blockIdx.x * 64 + (int)threadIdx.x;
   if (i >= P.n) return;
   const int S = P.n_states, A = P.n_actions;
+  double lr = P.learning_rate;
+  const double* pow_table = P.pow_table;
+  if constexpr (SETS) {
+    int k = (int)((pma_index_ptr)P.index)[i];
+    k = k < P.n_sets ? k : P.n_sets - 1;
+    const pma_set_ptr ps = (pma_set_ptr)(P.sets + k);
+    lr = P.agent ? ps->alpha : ps->learning_rate_q;
+    pow_table = P.pow_table + (size_t)k * P.pow_len;
+  }
   double* const Q = P.q + (size_t)i * S * A;
   const cobel_pma_rec_t* const st = P.steps + (size_t)i * (size_t)P.inst_stride;
   int n = P.lengths[P.inst_stride ? i : 0];
@@ -168,17 +195,17 @@ __global__ __launch_bounds__(64) void k_pma_update_q(const upd_args P) {
   const double fv = max_row(Q, clamp_to(st[n - 1].next_state, S), A) * (double)st[n - 1].terminal;
   for (int j = 0; j < n; ++j) {
     double r = 0.0;
-    for (int kk = 0; kk < n - j; ++kk) r += st[j + kk].reward * P.pow_table[kk];
+    for (int kk = 0; kk < n - j; ++kk) r += st[j + kk].reward * pow_table[kk];
     const int cell = clamp_to(st[j].state, S) * A + clamp_to(st[j].action, A);
     const double qv = Q[cell];
-    double td = r + fv * P.pow_table[n - j];
+    double td = r + fv * pow_table[n - j];
     td -= qv;
-    Q[cell] = qv + P.learning_rate * td;
+    Q[cell] = qv + lr * td;
   }
 }
 
 // what the four calls ask of the memory: its shape, and the tables `tables` says they read
-int check_shape(const cobel_pma_mem_t* mem, const char* who) {
+int check_shape(const cobel_pma_mem_x* mem, const char* who) {
   COBEL_REQUIRE(mem, COBEL_E_ARG, "%s: NULL mem", who);
   COBEL_REQUIRE(mem->n_states >= 1 && mem->n_states <= kMaxS && mem->n_actions >= 1 &&
                     mem->n_actions <= kMaxA,
@@ -189,10 +216,10 @@ int check_shape(const cobel_pma_mem_t* mem, const char* who) {
   return COBEL_OK;
 }
 
-int check_gain(const cobel_pma_mem_t* mem, const double* q, int64_t q_stride, const double* gain,
+int check_gain(const cobel_pma_mem_x* mem, const double* q, int64_t q_stride, const double* gain,
                const char* who) {
   if (int rc = check_shape(mem, who)) return rc;
-  const cobel_pma_mem_t& m = *mem;
+  const cobel_pma_mem_x& m = *mem;
   COBEL_REQUIRE(q, COBEL_E_ARG, "%s: NULL q", who);
   COBEL_REQUIRE(gain, COBEL_E_ARG, "%s: NULL gain", who);
   COBEL_REQUIRE(m.rewards && m.states && m.terminals, COBEL_E_ARG,
@@ -203,9 +230,10 @@ int check_gain(const cobel_pma_mem_t* mem, const double* q, int64_t q_stride, co
   COBEL_REQUIRE((((uintptr_t)q | (uintptr_t)gain | (uintptr_t)m.rewards) & 7u) == 0 &&
                     (((uintptr_t)m.states | (uintptr_t)m.terminals) & 3u) == 0,
                 COBEL_E_ARG, "%s: misaligned table", who);
-  COBEL_REQUIRE(m.epsilon >= 0.0 && m.epsilon <= 1.0, COBEL_E_ARG, "%s: epsilon %g outside [0, 1]",
-                who, m.epsilon);
-  return COBEL_OK;
+  // (with an index the scalars are ignored; a set's epsilon is checked where the set is filled)
+  COBEL_REQUIRE(m.param_index || (m.epsilon >= 0.0 && m.epsilon <= 1.0), COBEL_E_ARG,
+                "%s: epsilon %g outside [0, 1]", who, m.epsilon);
+  return pma_check_sets(m, who);
 }
 
 // lengths [host] [count]: each 1 .. max_len; *longest takes the largest
@@ -245,8 +273,9 @@ unsigned grid_y(int n) { return (unsigned)n < kMaxGridY ? (unsigned)n : kMaxGrid
 
 }  // namespace
 
-extern "C" int cobel_pma_gain_batch(const cobel_pma_mem_t* mem, const double* q, int64_t q_stride,
+extern "C" int cobel_pma_gain_batch(const cobel_pma_mem_t* mem_in, const double* q, int64_t q_stride,
                                     double* gain, void* stream) {
+  COBEL_PMA_MEM("cobel_pma_gain_batch");
   if (int rc = check_gain(mem, q, q_stride, gain, "cobel_pma_gain_batch")) return rc;
   if (mem->n == 0) return COBEL_OK;
   gain_args P;
@@ -255,17 +284,18 @@ extern "C" int cobel_pma_gain_batch(const cobel_pma_mem_t* mem, const double* q,
   P.q_stride = q_stride;
   P.gain = gain;
   const int SA = mem->n_states * mem->n_actions;
-  COBEL_HIP_TRY(cobel_launch(k_pma_gain_batch,
+  COBEL_HIP_TRY(cobel_launch(mem->param_index ? k_pma_gain_batch<true> : k_pma_gain_batch<false>,
                              dim3((unsigned)((SA + kThreads - 1) / kThreads), grid_y(mem->n)),
                              dim3(kThreads), 0, (hipStream_t)stream, P));
   return COBEL_OK;
 }
 
-extern "C" int cobel_pma_gain_seq(const cobel_pma_mem_t* mem, const double* q, int64_t q_stride,
+extern "C" int cobel_pma_gain_seq(const cobel_pma_mem_t* mem_in, const double* q, int64_t q_stride,
                                   const cobel_pma_rec_t* steps, const int32_t* lengths,
                                   int32_t n_seq, int32_t max_len, int64_t inst_stride, double* gain,
                                   void* stream) {
   const char* const who = "cobel_pma_gain_seq";
+  COBEL_PMA_MEM(who);
   if (int rc = check_gain(mem, q, q_stride, gain, who)) return rc;
   COBEL_REQUIRE(n_seq >= 0, COBEL_E_RANGE, "%s: n_seq = %d", who, n_seq);
   if (n_seq == 0 || mem->n == 0) return COBEL_OK;
@@ -297,8 +327,9 @@ extern "C" int cobel_pma_gain_seq(const cobel_pma_mem_t* mem, const double* q, i
   P.max_len = max_len;
   P.inst_stride = inst_stride;
   P.gain = gain;
-  COBEL_HIP_TRY(cobel_launch(k_pma_gain_seq, dim3((unsigned)n_seq, grid_y(mem->n)), dim3(64), 0,
-                             (hipStream_t)stream, P));
+  COBEL_HIP_TRY(cobel_launch(mem->param_index ? k_pma_gain_seq<true> : k_pma_gain_seq<false>,
+                             dim3((unsigned)n_seq, grid_y(mem->n)), dim3(64), 0, (hipStream_t)stream,
+                             P));
   return COBEL_OK;
 }
 
@@ -324,12 +355,19 @@ extern "C" int cobel_pma_action_probs(const double* q, const uint8_t* mask_bits,
   return COBEL_OK;
 }
 
-extern "C" int cobel_pma_update_q(const cobel_pma_mem_t* mem, double* q,
-                                  const cobel_pma_rec_t* steps, const int32_t* lengths,
-                                  int32_t max_len, int64_t inst_stride, double learning_rate,
-                                  const double* pow_table, int32_t pow_len, void* stream) {
-  const char* const who = "cobel_pma_update_q";
+// both forms of the update: the checks, the lengths' copy, the launch
+static int update_q_call(const char* who, const cobel_pma_mem_t* mem_in, double* q,
+                         const cobel_pma_rec_t* steps, const int32_t* lengths, int32_t max_len,
+                         int64_t inst_stride, double learning_rate, const double* pow_table,
+                         int32_t pow_len, bool sets, int32_t agent, void* stream) {
+  COBEL_PMA_MEM(who);
   if (int rc = check_shape(mem, who)) return rc;
+  if (sets) {
+    COBEL_REQUIRE(mem->param_index, COBEL_E_ARG, "%s: the memory carries no param_index", who);
+    if (int rc = pma_check_sets(*mem, who)) return rc;
+    COBEL_REQUIRE(agent == COBEL_PMA_Q_MEMORY || agent == COBEL_PMA_Q_AGENT, COBEL_E_ARG,
+                  "%s: which = %d (COBEL_PMA_Q_MEMORY or COBEL_PMA_Q_AGENT)", who, agent);
+  }
   COBEL_REQUIRE(q && ((uintptr_t)q & 7u) == 0, COBEL_E_ARG, "%s: NULL q, or not 8-byte aligned", who);
   COBEL_REQUIRE(steps && ((uintptr_t)steps & 7u) == 0, COBEL_E_ARG,
                 "%s: steps must be given, 8-byte aligned", who);
@@ -359,7 +397,32 @@ extern "C" int cobel_pma_update_q(const cobel_pma_mem_t* mem, double* q,
   P.n_states = mem->n_states;
   P.n_actions = mem->n_actions;
   P.max_len = max_len;
-  COBEL_HIP_TRY(cobel_launch(k_pma_update_q, dim3((unsigned)((mem->n + 63) / 64)), dim3(64), 0,
-                             (hipStream_t)stream, P));
+  P.sets = sets ? mem->param_sets : nullptr;
+  P.index = sets ? mem->param_index : nullptr;
+  P.n_sets = sets ? mem->n_param_sets : 0;
+  P.pow_len = pow_len;
+  P.agent = agent;
+  COBEL_HIP_TRY(cobel_launch(sets ? k_pma_update_q<true> : k_pma_update_q<false>,
+                             dim3((unsigned)((mem->n + 63) / 64)), dim3(64), 0, (hipStream_t)stream,
+                             P));
   return COBEL_OK;
+}
+
+extern "C" int cobel_pma_update_q(const cobel_pma_mem_t* mem, double* q,
+                                  const cobel_pma_rec_t* steps, const int32_t* lengths,
+                                  int32_t max_len, int64_t inst_stride, double learning_rate,
+                                  const double* pow_table, int32_t pow_len, void* stream) {
+  return update_q_call("cobel_pma_update_q", mem, q, steps, lengths, max_len, inst_stride,
+                       learning_rate, pow_table, pow_len, false, 0, stream);
+}
+
+extern "C" int cobel_pma_update_q_sets(const cobel_pma_mem_t* mem, double* q,
+                                       const cobel_pma_rec_t* steps, const int32_t* lengths,
+                                       int32_t max_len, int64_t inst_stride, int32_t which,
+                                       const double* agent_pow, void* stream) {
+  const char* const who = "cobel_pma_update_q_sets";
+  COBEL_REQUIRE(mem, COBEL_E_ARG, "%s: NULL mem", who);
+  const double* const table = which == COBEL_PMA_Q_AGENT ? agent_pow : mem->gamma_q_pow;
+  return update_q_call(who, mem, q, steps, lengths, max_len, inst_stride, 0.0, table, mem->pow_len,
+                       true, which, stream);
 }

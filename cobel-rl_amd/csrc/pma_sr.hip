@@ -6,6 +6,7 @@
 // Three launches per panel, ordered by the stream (nothing waits inside a kernel): k_pma_sr_tiles,
 // k_pma_sr_lines, k_pma_sr_diag — the instance is the grid's z axis.
 #include "cobel_gj.h"
+#include "cobel_pma.h"
 
 namespace {
 
@@ -17,15 +18,27 @@ struct sr_args {
   double gamma;
   int32_t S, k0, kb, nbr;
   uint32_t inst0;
+  // per-instance parameter sets (cobel_pma_mem_x): with an index, gamma is the instance's
+  const cobel_pma_param_set_t* sets;
+  const uint16_t* index;
+  int32_t n_sets;
 };
 
+// SETS: gamma of the instance's parameter set (the scalar launch keeps the form it had)
+template <bool SETS>
 __global__ __launch_bounds__(kThreads) void k_pma_sr_init(const sr_args P) {
   const int S = P.S;
   const size_t e = (size_t)blockIdx.x * kThreads + threadIdx.x;
   if (e >= (size_t)S * S) return;
-  const size_t off = (size_t)(P.inst0 + blockIdx.z) * S * S;
+  const uint32_t inst = P.inst0 + blockIdx.z;
+  const size_t off = (size_t)inst * S * S;
+  double gamma = P.gamma;
+  if constexpr (SETS) {
+    const int k = (int)((pma_index_ptr)P.index)[inst];
+    gamma = ((pma_set_ptr)(P.sets + (k < P.n_sets ? k : P.n_sets - 1)))->gamma;
+  }
   const int r = (int)(e / (size_t)S), c = (int)(e - (size_t)r * S);
-  P.M[off + e] = (r == c ? 1.0 : 0.0) - P.gamma * P.T[off + e];
+  P.M[off + e] = (r == c ? 1.0 : 0.0) - gamma * P.T[off + e];
 }
 
 __global__ __launch_bounds__(kThreads) void k_pma_sr_tiles(const sr_args P) {
@@ -49,7 +62,7 @@ size_t cobel_pma_sr_blocked_lds() {
   return 8 * (kTileDoubles > kLineDoubles ? kTileDoubles : kLineDoubles);
 }
 
-int cobel_pma_sr_blocked(const cobel_pma_mem_t& m, hipStream_t st) {
+int cobel_pma_sr_blocked(const cobel_pma_mem_x& m, hipStream_t st) {
   const int S = m.n_states;
   const unsigned nt = (unsigned)((S + kTile - 1) / kTile);
   const int nbr = (S + kThreads - 1) / kThreads;
@@ -60,12 +73,16 @@ int cobel_pma_sr_blocked(const cobel_pma_mem_t& m, hipStream_t st) {
     P.M = m.SR;
     P.T = m.T;
     P.gamma = m.gamma;
+    P.sets = m.param_sets;
+    P.index = m.param_index;
+    P.n_sets = m.n_param_sets;
     P.S = S;
     P.k0 = 0;
     P.kb = 0;
     P.nbr = nbr;
     P.inst0 = inst0;
-    COBEL_HIP_TRY(cobel_launch(k_pma_sr_init, dim3(init_blocks, 1, nz), dim3(kThreads), 0, st, P));
+    COBEL_HIP_TRY(cobel_launch(P.index ? k_pma_sr_init<true> : k_pma_sr_init<false>,
+                               dim3(init_blocks, 1, nz), dim3(kThreads), 0, st, P));
     for (int k0 = 0; k0 < S; k0 += kB) {
       P.k0 = k0;
       P.kb = S - k0 < kB ? S - k0 : kB;

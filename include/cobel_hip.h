@@ -1303,9 +1303,34 @@ COBEL_API int cobel_dqn_act(const cobel_world_t* world, const cobel_dqn_act_t* r
 #define COBEL_PMA_GAIN_ORIGINAL 16u    /* PMAMemory.min_gain_mode == 'original'                  */
 #define COBEL_PMA_SHARED_POLICY 32u    /* cobel_pma_trial: the memory's policy IS the agent's: its
                                           extension draws continue inst[COBEL_I_CTR_POLICY]         */
+#define COBEL_PMA_SETS 128u            /* cobel_pma_mem_t.flags: the struct is the head of a
+                                          cobel_pma_mem_sets_t, whose tail the call reads           */
 #define COBEL_PMA_WIDE 64u             /* cobel_pma_mem_t.flags: the wide form (cobel_pma_plan_wide
                                           says what it serves); clear: every call behaves and
                                           refuses as the narrow form does                           */
+
+/* Per-instance PMA parameters: the seven doubles of the memory a sweep varies (memory/pma.py:
+ * 121-137) and the agent's three (agent/pma.py:158-159 and the acting policy's epsilon).  The reference
+ * runs one simulation per combination; here instance i of ONE launch uses
+ * param_sets[param_index[i]] in every entry point that reads a parameter.  The switches
+ * (COBEL_PMA_*) and the replay length stay launch-wide.  Fill a set with
+ * cobel_pma_param_set_fill, never by hand.  80 bytes, a multiple of 16 as it stands. */
+typedef struct {
+  double learning_rate, learning_rate_q, learning_rate_T; /* PMAMemory's                        */
+  double gamma, gamma_q, min_gain;
+  double epsilon;             /* of the memory's policy                                         */
+  double alpha;               /* PMA.learning_rate                                              */
+  double agent_gamma;         /* PMA.gamma (= PMA.gamma ** 1, cobel_pma_run_t.gamma_pow1)       */
+  double agent_epsilon;       /* of the acting policy                                           */
+} cobel_pma_param_set_t;
+/* Host only.  memory[7] in the order of the first seven members, taken verbatim but for the
+ * ranges the kernels rest on: an epsilon (memory[6], agent_epsilon) outside [0, 1] is refused
+ * (COBEL_E_ARG, the value in the message) as the scalar launches refuse it, and so is a memory
+ * gamma (memory[3]) outside [0, 1): update_sr eliminates without pivoting, which rests on
+ * I - gamma T being strictly diagonally dominant.  Nothing else has a range. */
+COBEL_API int cobel_pma_param_set_fill(const double memory[7], double alpha, double agent_gamma,
+                                       double agent_epsilon,
+                                       cobel_pma_param_set_t* out /* [host] */);
 
 typedef struct {
   double* q;                  /* [N][S][A] the Q-function the replay updates                    */
@@ -1318,13 +1343,31 @@ typedef struct {
   const uint8_t* action_mask; /* [S] bit a = action a allowed, or NULL                          */
   uint32_t* mem_ctr;          /* [N] next index on COBEL_STREAM_PMA_MEMORY                      */
   uint32_t* pol_ctr;          /* [N] next index on pol_stream                                   */
-  const double* gamma_pow;    /* [pow_len] gamma ** k, filled by the host                       */
-  const double* gamma_q_pow;  /* [pow_len] gamma_q ** k                                         */
+  const double* gamma_pow;    /* [pow_len] gamma ** k, filled by the host; with parameter sets
+                                 [n_param_sets][pow_len], row k holding set k's powers          */
+  const double* gamma_q_pow;  /* [pow_len] gamma_q ** k; with sets [n_param_sets][pow_len]      */
   int32_t n, n_states, n_actions, pow_len;
   uint32_t instance_base, flags /* COBEL_PMA_* */, pol_stream, reserved_;
   double learning_rate, learning_rate_q, learning_rate_T, gamma, gamma_q, min_gain, epsilon;
   uint64_t seed;
 } cobel_pma_mem_t;
+
+/* cobel_pma_mem_t with the optional per-instance parameter sets behind it.  cobel_pma_mem_t itself
+ * keeps its 192 bytes: a caller that has sets builds THIS struct, sets COBEL_PMA_SETS in mem.flags
+ * and hands &x.mem to the entry points, which read the tail only under that flag (without it the
+ * memory behind the 192 bytes is never looked at).  A zeroed tail is the scalar launch.  With
+ * param_index != NULL instance i uses param_sets[param_index[i]] and row param_index[i] of the two
+ * power tables (an index >= n_param_sets is clamped to the last set); the seven scalars of mem —
+ * and alpha, gamma_pow1 and epsilon of cobel_pma_run_t — are ignored.  1 .. 65 535 sets.
+ * Refused before any launch (COBEL_E_ARG): an index without sets, n_param_sets < 1, param_sets
+ * not 16-byte or param_index not 2-byte aligned, pow_len not above the replay length.
+ * cobel_pma_stationary* and cobel_pma_action_probs read no parameter and do not look here. */
+typedef struct {
+  cobel_pma_mem_t mem;
+  const cobel_pma_param_set_t* param_sets; /* [dev] [n_param_sets], 16-byte aligned             */
+  const uint16_t* param_index;             /* [dev] [N]                                         */
+  int32_t n_param_sets, reserved_;
+} cobel_pma_mem_sets_t;
 
 /* One performed update (memory/pma.py:263), 24 bytes. */
 typedef struct {
@@ -1493,6 +1536,18 @@ COBEL_API int cobel_pma_update_q(const cobel_pma_mem_t* mem, double* q,
                                  const cobel_pma_rec_t* steps, const int32_t* lengths,
                                  int32_t max_len, int64_t inst_stride, double learning_rate,
                                  const double* pow_table, int32_t pow_len, void* stream);
+/* The same update with the learning rate and the powers of each instance's parameter set
+ * (mem->param_index is required).  which = COBEL_PMA_Q_MEMORY: learning_rate_q and the instance's
+ * row of mem->gamma_q_pow (PMAMemory.update_q); COBEL_PMA_Q_AGENT: alpha and the instance's row of
+ * agent_pow [dev] [n_param_sets][mem->pow_len], row k holding set k's agent_gamma ** j (PMA.update_q)
+ * — a pointer argument, so cobel_pma_mem_t carries the memory's two tables only; it is not looked
+ * at under COBEL_PMA_Q_MEMORY.  Reads mem->n, n_states, n_actions, pow_len and the sets. */
+#define COBEL_PMA_Q_MEMORY 0
+#define COBEL_PMA_Q_AGENT 1
+COBEL_API int cobel_pma_update_q_sets(const cobel_pma_mem_t* mem, double* q,
+                                      const cobel_pma_rec_t* steps, const int32_t* lengths,
+                                      int32_t max_len, int64_t inst_stride, int32_t which,
+                                      const double* agent_pow, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * The similarity metrics of SFMA (memory/utils/metrics.py:66-268) for stacks of four-action worlds
