@@ -17,7 +17,7 @@ Reference lines restated (relative to /root/reference/src/cobel):
   epsilon-greedy .......... policy/greedy.py:58, :77-86
   model store / sample .... memory/dyna_q.py:92-96, :137-155
   Dyna-Q loop, TD ......... agent/dyna_q.py:164-215, :290-299, :327-330
-  QAgent loop, replay ..... agent/q.py:183-228, :305-313, :353-354
+  QAgent loop, replay ..... agent/q.py:183-228, :230-270 (test), :305-313, :353-354
   SR loop, update, q ...... agent/sr.py:155-197, :267-284, :302-308
   escape latency .......... monitor/behavior.py:82-85
 Pinned against golden vectors captured from the real reference
@@ -185,8 +185,9 @@ class RefQAgent(_Tabular):
     and this is that line restated so that the masked QAgent runs have a checker."""
 
     def __init__(self, n_states, n_actions, policy, replay_rng, learning_rate=0.9, gamma=0.8,
-                 dtype=np.float64):
+                 dtype=np.float64, policy_test=None):
         self.policy, self.rng = policy, replay_rng
+        self.policy_test = policy if policy_test is None else policy_test
         self.learning_rate, self.gamma = learning_rate, gamma
         self.Q = np.zeros((n_states, n_actions), dtype=dtype)
         self.M: list = []
@@ -214,6 +215,30 @@ class RefQAgent(_Tabular):
                     trace['sarsn'].append(exp)
                     trace['td'].append(float(td))
                     trace['idx'].append(np.asarray(pick))
+                trial_reward += reward
+                if end:
+                    break
+            self.current_trial += 1
+            if trace is not None:
+                trace['steps'].append(step)
+                trace['trial_reward'].append(float(trial_reward))
+                if 'Q_trial' in trace:
+                    trace['Q_trial'].append(self.Q.copy())
+
+    def test(self, env, trials, steps=32, trace=None):
+        """agent/q.py:230-270: ``policy_test`` selects, nothing is stored, learnt or replayed."""
+        for _ in range(trials):
+            state, _ = env.reset()
+            trial_reward = 0.0
+            step = -1
+            for step in range(steps):
+                action = self.policy_test.select_action(
+                    self.Q[state], self.action_mask[state] if self.mask_actions else None)
+                ns, reward, end, _, _ = env.step(action)
+                if trace is not None:
+                    trace['sarsn'].append((state, action, float(reward), ns, 1 - end))
+                    trace['td'].append(0.0)
+                state = ns
                 trial_reward += reward
                 if end:
                     break

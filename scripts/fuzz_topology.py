@@ -24,14 +24,10 @@ sys.path.insert(0, os.path.join(ROOT, 'cobel-rl_amd'))
 SEED = 0xC0BE1
 
 
-def draw_case(seed: int) -> dict:
-    r = np.random.default_rng(9_000_011 * seed + 3)
-    S = int(r.integers(2, 61))
-    A = int(r.choice([1, 2, 3, 4, 4, 5, 6, 6, 7, 8]))
-    if seed >= 1_000_000:   # (seeds from 10^6 on: nine to 32 neighbours — the wide general kernels)
-        A = int(r.choice([9, 10, 12, 13, 16, 17, 20, 24, 31, 32]))
-    if seed >= 2_000_000:   # (round 5: any count, masks)
-        A = int(r.choice([1, 2, 4, 6, 8, 9, 12, 16, 17, 31, 32]))
+def draw_graph(r, S: int, A: int):
+    """A random directed graph of S nodes with A neighbours each, its terminal nodes, rewards and
+    start list (None: every non-terminal node), drawn from ``r`` (scripts/fuzz_tabpol.py draws its
+    graphs here too)."""
     nbr = r.integers(0, S, (S, A))
     stay = r.random((S, A)) < 0.2             # missing neighbours are the node itself
     nbr = np.where(stay, np.arange(S)[:, None], nbr)
@@ -44,6 +40,18 @@ def draw_case(seed: int) -> dict:
     starts = None
     if r.random() < 0.5:
         starts = sorted(set(int(x) for x in r.choice(free, int(r.integers(1, 5)))))
+    return nbr, terminal, reward, starts
+
+
+def draw_case(seed: int) -> dict:
+    r = np.random.default_rng(9_000_011 * seed + 3)
+    S = int(r.integers(2, 61))
+    A = int(r.choice([1, 2, 3, 4, 4, 5, 6, 6, 7, 8]))
+    if seed >= 1_000_000:   # (seeds from 10^6 on: nine to 32 neighbours — the wide general kernels)
+        A = int(r.choice([9, 10, 12, 13, 16, 17, 20, 24, 31, 32]))
+    if seed >= 2_000_000:   # (round 5: any count, masks)
+        A = int(r.choice([1, 2, 4, 6, 8, 9, 12, 16, 17, 31, 32]))
+    nbr, terminal, reward, starts = draw_graph(r, S, A)
     mask = None
     if seed >= 2_000_000 and r.random() < 0.5:
         mask = r.random((S, A)) < 0.6

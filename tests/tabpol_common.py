@@ -70,6 +70,7 @@ class RefPolicy:
     def __init__(self, kind, par, rng, n_actions=None):
         self.kind, self.par, self.rng, self.n_actions = kind, par, rng, n_actions
         self.margin = float('inf')
+        self.underflowed = False
 
     def get_action_probs(self, v, mask=None):
         if self.kind == RANDOM:
@@ -79,7 +80,10 @@ class RefPolicy:
     def select_action(self, v, mask=None):
         if self.kind == RANDOM:
             return int(self.rng.integers(self.n_actions))
-        cdf = cdf_of(self.get_action_probs(v, mask))
+        p = self.get_action_probs(v, mask)
+        if self.kind == SOFTMAX and np.any((p == 0.0) & (True if mask is None else np.asarray(mask, dtype=bool))):
+            self.underflowed = True      # an exponential of an action on offer came out as exact zero
+        cdf = cdf_of(p)
         u = self.rng.random()
         if len(cdf) > 1:
             self.margin = min(self.margin, float(np.abs(cdf[:-1] - u).min()))
@@ -192,11 +196,11 @@ class Restated:
     def __init__(self, tabs, agent, policy, g, seed=SEED, test_policy=None, alpha=None, gamma=None,
                  mask=None):
         S, A = np.asarray(tabs['next']).shape
-        self.S, self.A, self.kind = S, A, agent
+        self.S, self.A, self.kind, self.seed, self.g = S, A, agent, seed, g
         self.env = ref_loop.RefGridworld(tabs, TapeRNG(seed, g, STREAM_ENV))
-        self.pol = make_policy(policy, TapeRNG(seed, g, STREAM_POLICY), A)
-        self.pol_test = None if test_policy is None else \
-            make_policy(test_policy, TapeRNG(seed, g, STREAM_AUX), A)
+        self.policies = []
+        self.pol = self.policy_object(policy, STREAM_POLICY)
+        self.pol_test = None if test_policy is None else self.policy_object(test_policy, STREAM_AUX)
         self.mem_rng = TapeRNG(seed, g, STREAM_MEMORY)
         kw = {}
         if alpha is not None:
@@ -207,10 +211,37 @@ class Restated:
             self.ag = ref_loop.RefDynaQ(S, A, self.pol, self.mem_rng, dtype=np.float32,
                                         policy_test=self.pol_test, **kw)
         else:
-            self.ag = ref_loop.RefQAgent(S, A, self.pol, self.mem_rng, dtype=np.float32, **kw)
+            self.ag = ref_loop.RefQAgent(S, A, self.pol, self.mem_rng, dtype=np.float32,
+                                         policy_test=self.pol_test, **kw)
         if mask is not None:
             self.ag.mask_actions, self.ag.action_mask = True, np.asarray(mask, dtype=bool)
         self.trace = ref_loop.new_trace(with_q=True)
+
+    def policy_object(self, spec, stream):
+        """A further policy object of this instance on a tape of its own from counter 0: STREAM_POLICY
+        for one that trains, STREAM_AUX (the device's STREAM_POLICY_TEST) for a ``policy_test``."""
+        pol = make_policy(spec, TapeRNG(self.seed, self.g, stream), self.A)
+        self.policies.append(pol)
+        return pol
+
+    def session(self, pol, trials, steps, batch, learn, no_replay=False):
+        """One session that selects with the policy object ``pol``, assigned to the agent as
+        ``policy`` (a training session) or ``policy_test`` (a test session) for its duration."""
+        keep = self.ag.policy, self.ag.policy_test
+        if learn:
+            self.ag.policy = pol
+            self.train(trials, steps, batch, no_replay)
+        else:
+            self.ag.policy_test = pol
+            self.test(trials, steps)
+        self.ag.policy, self.ag.policy_test = keep
+
+    def edit_world(self, tabs):
+        """The environment reads its tables at every step and reset: replace them between sessions."""
+        e = self.env
+        assert np.asarray(tabs['next']).shape == (self.S, self.A)
+        e.next, e.reward = np.asarray(tabs['next']), np.asarray(tabs['reward'], dtype=np.float64)
+        e.terminal, e.starts = np.asarray(tabs['terminal']), np.asarray(tabs['starts'])
 
     def train(self, trials, steps, batch, no_replay=False):
         if self.kind == 'dynaq':
@@ -222,8 +253,7 @@ class Restated:
         self.ag.test(self.env, trials, steps, trace=self.trace)
 
     def margin(self) -> float:
-        return min([getattr(p, 'margin', float('inf')) for p in (self.pol, self.pol_test)
-                    if p is not None])
+        return min(getattr(p, 'margin', float('inf')) for p in self.policies)
 
     def record(self) -> dict:
         tr = self.trace
@@ -235,7 +265,8 @@ class Restated:
                  Q_trial=np.array(tr['Q_trial'], dtype=np.float32), Q=np.array(self.ag.Q, dtype=np.float32),
                  ctr_env=np.int64(self.env.rng.index), ctr_policy=np.int64(self.pol.rng.index),
                  ctr_policy_test=np.int64(0 if self.pol_test is None else self.pol_test.rng.index),
-                 ctr_memory=np.int64(self.mem_rng.index), margin=np.float64(self.margin()))
+                 ctr_memory=np.int64(self.mem_rng.index), margin=np.float64(self.margin()),
+                 env_state=np.int64(self.env.current_state))
         if self.kind == 'dynaq':
             d.update(M_rewards=np.array(self.ag.M.rewards, dtype=np.float32),
                      M_states=self.ag.M.states.astype(np.int16),
@@ -262,6 +293,47 @@ def restate_case(name, tabs) -> dict:
 EXACT = ('state', 'action', 'reward', 'next_state', 'nonterminal', 'td', 'steps', 'trial_reward',
          'Q_trial', 'Q', 'ctr_env', 'ctr_policy', 'ctr_policy_test', 'ctr_memory', 'M_rewards',
          'M_states', 'M_terminals', 'log', 'n_train_steps')
+# what the records of a sweep case add (scripts/fuzz_tabpol.py): the carried state and the counters
+# of the further policy objects
+SWEEP_EXACT = EXACT + ('env_state', 'ctr_second', 'ctr_eps_test', 'ctr_eps_train')
+
+
+# -- test sessions on the policy kernel (tests/test_gpu_tabpol_seams.py) ------------------------------------
+# name: agent, training policy, policy_test (None: the default, the training policy's object), instance
+TEST_TRIALS, TEST_STEPS, TEST_BATCH = 3, 12, 8
+TEST_CASES = {
+    'q_test_soft': ('q', (EXCLUSIVE, 0.3), (SOFTMAX, 2.0), 20),
+    'q_test_excl': ('q', (SOFTMAX, 2.0), (EXCLUSIVE, 0.3), 21),
+    'q_test_random': ('q', (SOFTMAX, 2.0), (RANDOM, None), 31),
+    'q_test_default': ('q', (SOFTMAX, 2.0), None, 23),
+    'dynaq_test_soft': ('dynaq', (EXCLUSIVE, 0.3), (SOFTMAX, 2.0), 24),
+    'dynaq_test_excl': ('dynaq', (SOFTMAX, 2.0), (EXCLUSIVE, 0.3), 25),
+    'dynaq_test_random': ('dynaq', (SOFTMAX, 2.0), (RANDOM, None), 26),
+    'dynaq_test_default': ('dynaq', (SOFTMAX, 2.0), None, 27),
+}
+TEST_KEYS = ('agent', 'policy', 'test', 'inst')
+
+
+def session_case(name) -> dict:
+    return dict(zip(TEST_KEYS, TEST_CASES[name]))
+
+
+def restated_test_case(name, tabs, g=None) -> Restated:
+    """A short training session on ``grid4`` (TRIALS x STEPS), then a test session (TEST_TRIALS x
+    TEST_STEPS): the instance after both."""
+    c = session_case(name)
+    r = Restated(tabs, c['agent'], c['policy'], c['inst'] if g is None else g, test_policy=c['test'])
+    r.train(TRIALS, STEPS, TEST_BATCH)
+    r.n_train = len(r.trace['sarsn'])
+    r.test(TEST_TRIALS, TEST_STEPS)
+    return r
+
+
+def restate_test_case(name, tabs) -> dict:
+    r = restated_test_case(name, tabs)
+    d = r.record()
+    d['n_train_steps'] = np.int64(r.n_train)
+    return d
 
 
 # -- the device side -------------------------------------------------------------------------------------------
@@ -403,6 +475,12 @@ def grid4b(tools):
                                 invalid_states=[6], starting_states=[3, 0, 11])
 
 
+def grid4c(tools):
+    """A third one: two walls, a goal with a negative reward beside a rewarded terminal."""
+    return tools.make_gridworld(4, 4, terminals=[0, 10], rewards=np.array([[0, 1.0], [10, -1.0]]),
+                                goals=[0], invalid_states=[9, 2], starting_states=[15, 7])
+
+
 # name: worlds, agent, policy kind, instances, instance_base, batch, trials, steps, per-instance
 # parameters, the instances that are restated (None: all)
 SWEEPS = {
@@ -427,10 +505,25 @@ SWEEPS = {
     'b62_q': (('grid4',), 'q', SOFTMAX, 3, 0, 62, 3, 10, False, None),
 }
 SWEEP_KEYS = ('worlds', 'agent', 'kind', 'n', 'base', 'batch', 'trials', 'steps', 'sets', 'check')
+# the sweeps of tests/test_gpu_tabpol_seams.py: three, five and seven actions (the pad cells of a row
+# at odd widths), nine instances on THREE parameter combinations (``sets`` = 3: instance i runs
+# combination i % 3), three worlds with instance_base 5 (instance i lives in world (5 + i) % 3)
+SEAM_SWEEPS = {
+    'a3_q': (('ring9x3',), 'q', SOFTMAX, 3, 0, 8, 3, 10, False, None),
+    'a3_q_excl': (('ring9x3',), 'q', EXCLUSIVE, 3, 0, 8, 3, 10, False, None),
+    'a5_q': (('ring9x5',), 'q', SOFTMAX, 3, 0, 8, 3, 10, False, None),
+    'a5_q_random': (('ring9x5',), 'q', RANDOM, 3, 0, 8, 3, 10, False, None),
+    'a7_q': (('ring9x7',), 'q', SOFTMAX, 3, 0, 8, 6, 14, False, None),
+    'a7_q_excl': (('ring9x7',), 'q', EXCLUSIVE, 3, 0, 8, 6, 14, False, None),
+    'shared9_dynaq': (('grid4',), 'dynaq', SOFTMAX, 9, 0, 8, 6, 14, 3, None),
+    'shared9_q_excl': (('grid4',), 'q', EXCLUSIVE, 9, 0, 8, 6, 14, 3, None),
+    'three_worlds_base5_dynaq': (('grid4', 'grid4b', 'grid4c'), 'dynaq', SOFTMAX, 6, 5, 8, 6, 14, False, None),
+    'three_worlds_base5_q': (('grid4', 'grid4b', 'grid4c'), 'q', EXCLUSIVE, 6, 5, 8, 6, 14, False, None),
+}
 
 
 def sweep(name) -> dict:
-    return dict(zip(SWEEP_KEYS, SWEEPS[name]))
+    return dict(zip(SWEEP_KEYS, SWEEPS[name] if name in SWEEPS else SEAM_SWEEPS[name]))
 
 
 def sweep_world(wname, grid_tools):
@@ -439,7 +532,7 @@ def sweep_world(wname, grid_tools):
         n_nodes, n_actions = (int(x) for x in wname[4:].split('x'))
         nodes, starts = ring_nodes(n_nodes, n_actions, goal=n_nodes > 1)
         return ('nodes', nodes, starts), node_tables(nodes, starts)
-    world = {'grid4': grid4, 'grid4b': grid4b,
+    world = {'grid4': grid4, 'grid4b': grid4b, 'grid4c': grid4c,
              'open32': lambda t: t.make_open_field(32, 32, 0, 1)}[wname](grid_tools)
     return ('grid', world), world_tables(world)
 
@@ -449,6 +542,8 @@ def sweep_params(s) -> dict:
     discount (distinct values, so that every instance is a parameter set of its own)."""
     n = s['n']
     k = np.arange(n, dtype=np.float64)
+    if s['sets'] is not True and s['sets']:      # a count: that many combinations, shared
+        k = k % int(s['sets'])
     par = None
     if s['kind'] == SOFTMAX:
         par = (0.5 + 0.05 * k) if s['sets'] else 2.0

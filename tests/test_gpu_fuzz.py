@@ -9,7 +9,11 @@ Below it: slices of the sweeps for SFMA, topologies, stochastic worlds, the netw
 kernels.  The sweeps for PMA, AssociativeNetwork, Continuous2D and MFEC have their slices in
 tests/test_gpu_fuzz_agents.py (what those contain: tests/test_host_fuzz_agents.py); several hundred
 seeds of each beyond the slice found no mismatch (docs/MEASUREMENTS.md section 20), so there is no
-regression case of theirs next to test_sweep_regressions."""
+regression case of theirs next to test_sweep_regressions.  The tabular policy kernel (Softmax,
+ExclusiveEpsilonGreedy and RandomDiscrete for QAgent and DynaQ, csrc/tabular_policy.hip), which none
+of the sweeps above reaches — they all build EpsilonGreedy agents —, has scripts/fuzz_tabpol.py:
+its slices are tests/test_gpu_fuzz_tabpol.py (what they contain: tests/test_host_fuzz_tabpol.py),
+its first thousand seeds found no mismatch (docs/MEASUREMENTS.md section 35)."""
 import os
 import sys
 
